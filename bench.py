@@ -27,7 +27,8 @@ The merge:
   --merge exact (bit-identical to one GPU): depth + colour frames are all-gathered, every rank integrates all frames in
                 sequence order into its x-slab of the volume, the slabs are all-gathered.
 (`--merge exact` is a strong-scaling mode by construction: every rank integrates every frame.)
-Rank 0 prints the line.
+Rank 0 prints the line.  `--dump-outputs DIR`: rank 0 also writes what the headline job's last timed step returned -- that batch's depth maps and the
+timed volume's planes, float32, a fixed seeded sample of each past 3 Mi values -- to DIR/<name>.npy, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -66,7 +67,13 @@ def parse_args():
     ap.add_argument("--notes", action="store_true", help="keep the explanatory note strings in the JSON line (default: numbers only -- the notes are DESIGN.md section 6; "
                                                          "the full line is ~10 KB, the compact one ~4 KB, which a log tail does not cut)")
     ap.add_argument("--timed-only", action="store_true", help="profiling runs: only the headline timed job (no roofline / cpu_baseline / extra legs)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline timed job, write what its last step handed the caller to DIR/<name>.npy (float32): `depth` (the last batch's depth "
+                         "maps, metres) and the timed volume's `tsdf`, `weight`, `color` planes; larger arrays as a fixed seeded sample (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def compact(obj, keep_notes=False):
@@ -175,6 +182,27 @@ class FrameFeeder:
 
     def release(self, token, stream=None):
         self.free[token[0]].record(stream or torch.cuda.current_stream())
+
+
+DUMP_VALUES = 3 << 20  # values per dumped array: four arrays of float32 stay under 64 MB
+
+
+def dump_outputs(out_dir, depth_m, vol):
+    """--dump-outputs: the depth maps `DepthFusionStream.step` returned for the last batch and the timed volume's three planes (flat, num_voxels each) as
+    float32 .npy files.  An array of more than DUMP_VALUES values is replaced by its values at the sorted, de-duplicated flat indices of
+    numpy.random.default_rng(seed).integers(0, size, DUMP_VALUES) -- the same sample for every run with the same arguments; the three planes share one draw."""
+    os.makedirs(out_dir, exist_ok=True)
+    tsdf, weight, color = vol.device_tensors()
+    torch.cuda.synchronize()
+    for seed, named in ((1, {"depth": depth_m}), (2, {"tsdf": tsdf, "weight": weight, "color": color})):
+        idx = None
+        for name, t in named.items():
+            if t.numel() > DUMP_VALUES:
+                if idx is None:
+                    idx = torch.from_numpy(np.unique(np.random.default_rng(seed).integers(0, t.numel(), DUMP_VALUES))).to(t.device)
+                t = t.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    del tsdf, weight, color
 
 
 def source_stamp():
@@ -386,6 +414,8 @@ def main():
         cuts = [len(ids) * i // n_b for i in range(n_b + 1)]
         return [ids[a:b] for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
 
+    last_depth = [None]  # --dump-outputs: the depth maps of the newest batch (held only then: the default job keeps no extra buffer alive)
+
     def run_job(stream, strong, first_step, n_steps):
         """All of this rank's batches: upload (one batch ahead) -> depth -> integrate (or, exact mode, keep the depth maps)."""
         ids, counts = job_frames(strong, first_step, n_steps)
@@ -399,7 +429,9 @@ def main():
                 depth_m, _ = stream.depth(fr)
                 kept.append((fr.clone(), depth_m))
             else:
-                stream.step(fr, poses[batch_ids])
+                depth_m = stream.step(fr, poses[batch_ids])
+            last_depth[0] = depth_m if args.dump_outputs else None
+            del depth_m
             feeder.release(token, stream.side if not exact else None)  # the buffer is free once the sweeps that read its colours are done
             token = nxt
         if exact:  # all-gather the frames, integrate every frame of the job in sequence order into this rank's x-slab
@@ -432,10 +464,10 @@ def main():
         chk["frames_expected"] = frames_mine
         return chk
 
-    def timed_job(stream, strong, vol=None):
+    def timed_job(stream, strong, vol=None, dump=False):
         """W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize on both sides; at N > 1 the one merge of the shared volume is
         inside the timed region.  Returns (max-over-ranks seconds, frames of the whole job, sweep launches, sweep kernel ms of this rank, proof-of-work
-        record of the timed volume)."""
+        record of the timed volume).  `dump`: rank 0 writes the last step's outputs (--dump-outputs) after the clock stopped."""
         vol = vol or volume
         tctx = vol._ctx
         for s in range(0, args.warmup):
@@ -476,11 +508,14 @@ def main():
         elapsed = hdist.max_over_ranks(elapsed, device=device if world > 1 else "cpu")
         total = args.steps * B * (1 if strong or world == 1 else world)
         check = volume_check(vol, merged if exact else None, total)
+        if dump and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_depth[0], merged if exact else vol)
+        last_depth[0] = None
         del merged
         return elapsed, total, n_launch, kernel_ms, check
 
     stream = make_stream(args.dtype)
-    elapsed, total_frames, n_launch, kernel_ms, volume_proof = timed_job(stream, headline_strong)
+    elapsed, total_frames, n_launch, kernel_ms, volume_proof = timed_job(stream, headline_strong, dump=True)
 
     if args.timed_only:
         if rank == 0:
