@@ -409,6 +409,339 @@ __global__ __launch_bounds__(256) void window_shift_dev_kernel(int32_t *__restri
     }
 }
 
+
+// ---- _cleanup_with_connected_components (/root/reference/hive/pipeline.py:741-779): floater removal by edge-connected components --------------------
+// trimesh.graph.face_adjacency pairs two faces when they share an edge (unordered vertex pair) that exactly two faces use; the components of that graph --
+// over the faces that have at least one such neighbour -- with at least min_len faces survive: all of them, or (objects) the largest, the one with the
+// smallest face index on a tie.  Six steps, every count and index exact:
+//   edge table   open-addressing hash of the face-edges keyed (min << 32) | max (vertex ids < 2^30, so ~0 is free as the empty key); slot of every face-edge
+//   edge users   per slot: the number of face-edges on it and the smallest face among them (a separate launch: every insert has landed)
+//   union-find   per face-edge on a slot with exactly two users whose smallest face is another face: union the two; roots hook the larger under the smaller
+//                with agent-scope CAS, parents are read through agent-scope atomics (workgroups on other XCDs see the hooks, not their stale L2 lines)
+//   labels       every face's root = the smallest face of its component; per root the faces that have a neighbour (wave-aggregated atomics)
+//   selection    one 64-bit atomicMax of (size << 32) | ~root over the roots whose size passes min_len (the largest; on a tie the smallest root)
+//   compaction   the surviving faces in order, the vertices an input face references in order (trimesh's process=True), faces remapped: the block scans above
+// Every bounded loop that runs out (table full, a CAS that keeps losing) and every out-of-range vertex id sets a bit of the error word instead of spinning.
+constexpr unsigned long long CC_EMPTY = ~0ull;
+constexpr int CC_ERR_TABLE = 1, CC_ERR_VERTEX = 2, CC_ERR_UNION = 4;
+constexpr int CC_CAS_CAP = 1 << 16;
+
+// scalar block of a clean-up (hive_ctx::d_scalars + CC_SCALARS): [0] vertices in, [1] faces in, [2] error word, [4..5] selection (u64),
+// [6] vertices out, [7] faces out, [8..11] the texture window's box (hive_fg_frame_mesh_cc): [0..11] is the frame path's one read-back
+constexpr int CC_SCALARS = 3584;
+
+struct CCParams {
+    const unsigned *counts;       // [0] V, [1] F (device)
+    unsigned *err;
+    unsigned long long *best;
+    long long face_cap, vert_cap;  // the sizes the scratch was laid out for (bounds on the device counts)
+    long long table_cap;           // slots allocated (a power of two)
+    const int32_t *faces;          // [F][3]
+    unsigned long long *keys;      // [table]
+    unsigned *users;               // [table] face-edges on the slot
+    int *first;                    // [table] smallest face on the slot
+    int *slot;                     // [3 F]
+    int *parent;                   // [F] union-find forest
+    int *label;                    // [F] root of every face (a separate array: path halving may still rewrite parent entries behind a finished find)
+    uint8_t *has_nbr;              // [F]
+    unsigned *size;                // [F] faces with a neighbour per root
+    uint8_t *referenced;           // [V]
+    int *vmap;                     // [V] compacted index or -1
+    double min_len;
+    int is_object;
+};
+
+__device__ __forceinline__ long long cc_nf(const CCParams &p) { return min((long long)p.counts[1], p.face_cap); }
+__device__ __forceinline__ long long cc_nv(const CCParams &p) { return min((long long)p.counts[0], p.vert_cap); }
+// slots in use for F faces: the power of two >= 4 F (at most 3 F distinct edges: load <= 3 / 4), at least 64, within what was allocated
+__device__ __forceinline__ unsigned long long cc_table(const CCParams &p) {
+    unsigned long long c = 64;
+    while (c < 4ull * (unsigned long long)cc_nf(p) && (long long)c < p.table_cap) c <<= 1;
+    return c;
+}
+__device__ __forceinline__ unsigned long long cc_hash(unsigned long long k) {  // splitmix64 finaliser
+    k ^= k >> 30;
+    k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27;
+    k *= 0x94d049bb133111ebull;
+    return k ^ (k >> 31);
+}
+__device__ __forceinline__ int cc_load(const int *a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void cc_store(int *a, int v) { __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// root of x with path halving (every parent is an ancestor: parent[x] <= x, a non-root never becomes a root again)
+__device__ __forceinline__ int cc_find(int *parent, int x) {
+    int p = cc_load(parent + x);
+    while (p != x) {
+        const int gp = cc_load(parent + p);
+        if (gp != p) cc_store(parent + x, gp);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(256) void cc_init_kernel(CCParams p) {
+    const unsigned long long table = cc_table(p);
+    const long long nf = cc_nf(p), nv = cc_nv(p);
+    const long long n = max((long long)table, max(nf, nv));
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *p.err = 0;
+        *p.best = 0;
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        if (i < (long long)table) {
+            p.keys[i] = CC_EMPTY;
+            p.users[i] = 0;
+            p.first[i] = 0x7fffffff;
+        }
+        if (i < nf) {
+            p.parent[i] = (int)i;
+            p.has_nbr[i] = 0;
+            p.size[i] = 0;
+        }
+        if (i < nv) p.referenced[i] = nf == 0;  // trimesh keeps every vertex of a mesh without faces
+    }
+}
+
+__global__ __launch_bounds__(256) void cc_insert_kernel(CCParams p) {
+    const unsigned long long mask = cc_table(p) - 1;
+    const long long nf = cc_nf(p), nv = cc_nv(p);
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < 3 * nf; e += (long long)gridDim.x * 256) {
+        const long long f = e / 3;
+        const int k = (int)(e - 3 * f);
+        const int a = p.faces[3 * f + k], b = p.faces[3 * f + (k == 2 ? 0 : k + 1)];
+        p.slot[e] = -1;
+        if (a < 0 || a >= nv || b < 0 || b >= nv) {
+            atomicOr(p.err, (unsigned)CC_ERR_VERTEX);
+            continue;
+        }
+        p.referenced[a] = 1;
+        const unsigned long long key = ((unsigned long long)min(a, b) << 32) | (unsigned)max(a, b);
+        unsigned long long s = cc_hash(key) & mask;
+        int found = -1;
+        for (unsigned long long probe = 0; probe <= mask; ++probe, s = (s + 1) & mask) {
+            const unsigned long long old = atomicCAS(p.keys + s, CC_EMPTY, key);
+            if (old == CC_EMPTY || old == key) {
+                found = (int)s;
+                break;
+            }
+        }
+        if (found < 0) atomicOr(p.err, (unsigned)CC_ERR_TABLE);
+        p.slot[e] = found;
+    }
+}
+
+__global__ __launch_bounds__(256) void cc_users_kernel(CCParams p) {
+    const long long nf = cc_nf(p);
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < 3 * nf; e += (long long)gridDim.x * 256) {
+        const int s = p.slot[e];
+        if (s < 0) continue;
+        atomicAdd(p.users + s, 1u);
+        atomicMin(p.first + s, (int)(e / 3));
+    }
+}
+
+__global__ __launch_bounds__(256) void cc_union_kernel(CCParams p) {
+    const long long nf = cc_nf(p);
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < 3 * nf; e += (long long)gridDim.x * 256) {
+        const int s = p.slot[e];
+        if (s < 0 || p.users[s] != 2) continue;
+        const int f = (int)(e / 3), g = p.first[s];
+        if (g == f) continue;  // the smaller face of the pair (or a face using the edge twice: trimesh drops such self-pairs) does nothing
+        p.has_nbr[f] = 1;
+        p.has_nbr[g] = 1;
+        int a = f, b = g, it = 0;
+        for (; it < CC_CAS_CAP; ++it) {
+            a = cc_find(p.parent, a);
+            b = cc_find(p.parent, b);
+            if (a == b) break;
+            const int hi = max(a, b), lo = min(a, b);
+            int expected = hi;
+            if (__hip_atomic_compare_exchange_strong(p.parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        }
+        if (it == CC_CAS_CAP) atomicOr(p.err, (unsigned)CC_ERR_UNION);
+    }
+}
+
+// labels and per-root sizes of the faces with a neighbour: one atomic per distinct root in a wave
+__global__ __launch_bounds__(256) void cc_label_kernel(CCParams p) {
+    const long long nf = cc_nf(p);
+    const int lane = threadIdx.x & 63;
+    for (long long base = (long long)blockIdx.x * 256; base < nf; base += (long long)gridDim.x * 256) {
+        const long long f = base + threadIdx.x;
+        int root = -1;
+        if (f < nf) {
+            root = cc_find(p.parent, (int)f);
+            p.label[f] = root;
+            if (!p.has_nbr[f]) root = -1;
+        }
+        unsigned long long todo = __ballot(root >= 0);
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int r = __shfl(root, leader);
+            const unsigned long long same = __ballot(root == r);
+            if (lane == leader) atomicAdd(p.size + r, (unsigned)__popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+
+__device__ __forceinline__ bool cc_passes(const CCParams &p, unsigned size) { return size > 0 && (double)size >= p.min_len; }
+
+__global__ __launch_bounds__(256) void cc_select_kernel(CCParams p) {
+    const long long nf = cc_nf(p);
+    unsigned long long best = 0;
+    for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nf; f += (long long)gridDim.x * 256)
+        if (p.label[f] == (int)f && cc_passes(p, p.size[f])) best = max(best, ((unsigned long long)p.size[f] << 32) | (unsigned)~(unsigned)f);
+    for (int off = 32; off > 0; off >>= 1) best = max(best, __shfl_xor(best, off));
+    if ((threadIdx.x & 63) == 0 && best) atomicMax(p.best, best);
+}
+
+__device__ __forceinline__ bool cc_keep(const CCParams &p, long long f, unsigned long long best) {
+    if (!p.has_nbr[f]) return false;
+    const int r = p.label[f];
+    if (!cc_passes(p, p.size[r])) return false;
+    return !p.is_object || (best && (unsigned)~(unsigned)r == (unsigned)best);
+}
+
+// per block of TILE: kept faces -> bf, referenced vertices -> bv (both arrays cover max(face blocks, vertex blocks))
+__global__ __launch_bounds__(256) void cc_count_kernel(CCParams p, unsigned *__restrict__ bv, unsigned *__restrict__ bf) {
+    __shared__ unsigned lds[8];
+    const long long nf = cc_nf(p), nv = cc_nv(p);
+    const unsigned long long best = *p.best;
+    unsigned cv = 0, cf = 0;
+    for (int j = 0; j < TILE / 256; ++j) {
+        const long long i = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
+        if (i < nf) cf += cc_keep(p, i, best);
+        if (i < nv) cv += p.referenced[i];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        cv += (unsigned)__shfl_xor((int)cv, off);
+        cf += (unsigned)__shfl_xor((int)cf, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        lds[threadIdx.x >> 6] = cv;
+        lds[4 + (threadIdx.x >> 6)] = cf;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bv[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+        bf[blockIdx.x] = lds[4] + lds[5] + lds[6] + lds[7];
+    }
+}
+
+// vmap[v] = compacted index of a referenced vertex (else -1); out_vertex_index (optional) = the kept input ids in order
+__global__ __launch_bounds__(256) void cc_vmap_kernel(CCParams p, const unsigned *__restrict__ bv, int32_t *__restrict__ out_vertex_index) {
+    __shared__ unsigned lds[4];
+    const long long nv = cc_nv(p);
+    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
+    bool ok[TILE / 256];
+    unsigned c = 0;
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j) {
+        ok[j] = base + j < nv && p.referenced[base + j];
+        c += ok[j];
+    }
+    long long o = (long long)bv[blockIdx.x] + block_exclusive(c, lds);
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j) {
+        if (base + j >= nv) continue;
+        p.vmap[base + j] = ok[j] ? (int)o : -1;
+        if (ok[j]) {
+            if (out_vertex_index) out_vertex_index[o] = (int32_t)(base + j);
+            ++o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cc_faces_kernel(CCParams p, const unsigned *__restrict__ bf, int32_t *__restrict__ out, long long out_cap) {
+    __shared__ unsigned lds[4];
+    const long long nf = cc_nf(p), nv = cc_nv(p);
+    const unsigned long long best = *p.best;
+    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
+    bool ok[TILE / 256];
+    unsigned c = 0;
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j) {
+        ok[j] = base + j < nf && cc_keep(p, base + j, best);
+        c += ok[j];
+    }
+    long long o = (long long)bf[blockIdx.x] + block_exclusive(c, lds);
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j)
+        if (ok[j]) {  // (an id out of range has set the error word already: the call fails, the read stays in bounds)
+            if (o < out_cap)
+                for (int k = 0; k < 3; ++k) {
+                    const int v = p.faces[3 * (base + j) + k];
+                    out[3 * o + k] = v >= 0 && v < nv ? p.vmap[v] : -1;
+                }
+            ++o;
+        }
+}
+
+// hive_fg_frame_mesh_cc: the pixels' vertex rows through the clean-up's vertex map (vid[i] = vmap[vid[i]], -1 = not written)
+__global__ __launch_bounds__(256) void cc_remap_vid_kernel(int *__restrict__ vid, int n, const int *__restrict__ vmap, const unsigned *__restrict__ n_verts, long long vert_cap) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int v = vid[i];
+    vid[i] = v >= 0 && v < min((long long)*n_verts, vert_cap) ? vmap[v] : -1;
+}
+
+// scratch of a clean-up of at most face_cap faces over at most vert_cap vertices, from `base`; returns the bytes it needs
+size_t cc_layout(char *base, long long face_cap, long long vert_cap, CCParams &p, unsigned **bv, unsigned **bf, int *nb) {
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    long long table = 64;
+    while (table < 4 * face_cap) table <<= 1;
+    *nb = (int)std::max<long long>(1, (std::max(face_cap, vert_cap) + TILE - 1) / TILE);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char *at = base + off;
+        off += align(bytes);
+        return at;
+    };
+    p.face_cap = face_cap;
+    p.vert_cap = vert_cap;
+    p.table_cap = table;
+    p.keys = (unsigned long long *)take((size_t)table * 8);
+    p.users = (unsigned *)take((size_t)table * 4);
+    p.first = (int *)take((size_t)table * 4);
+    p.slot = (int *)take((size_t)face_cap * 12);
+    p.parent = (int *)take((size_t)face_cap * 4);
+    p.label = (int *)take((size_t)face_cap * 4);
+    p.size = (unsigned *)take((size_t)face_cap * 4);
+    p.has_nbr = (uint8_t *)take((size_t)face_cap);
+    p.vmap = (int *)take((size_t)vert_cap * 4);
+    p.referenced = (uint8_t *)take((size_t)vert_cap);
+    *bv = (unsigned *)take((size_t)*nb * 4);
+    *bf = (unsigned *)take((size_t)*nb * 4);
+    return off;
+}
+
+// the clean-up's launches on faces already in device memory (counts in p.counts): scans into scalars[6] (vertices) / [7] (faces), box init at scalars + 8
+void cc_launch(hive_ctx *ctx, const CCParams &p, unsigned *bv, unsigned *bf, int nb, unsigned *scalars, int32_t *out_faces, long long out_face_cap,
+               int32_t *out_vertex_index) {
+    const long long work = std::max<long long>(3 * p.face_cap, std::max<long long>(p.table_cap, p.vert_cap));
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((work + 255) / 256, (long long)ctx->num_cus * 8)));
+    hipLaunchKernelGGL(cc_init_kernel, grid, dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(cc_insert_kernel, grid, dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(cc_users_kernel, grid, dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(cc_union_kernel, grid, dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(cc_label_kernel, grid, dim3(256), 0, ctx->stream, p);
+    if (p.is_object) hipLaunchKernelGGL(cc_select_kernel, grid, dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(cc_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, bv, bf);
+    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, bf, nb, scalars + 6, (int *)(scalars + 8));
+    hipLaunchKernelGGL(cc_vmap_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)bv, out_vertex_index);
+    hipLaunchKernelGGL(cc_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)bf, out_faces, out_face_cap);
+}
+
+int cc_error(hive_ctx *ctx, unsigned err) {
+    if (err & CC_ERR_VERTEX) return hive_fail(ctx, HIVE_ERR_INVALID, "mesh_cleanup_cc: a face references a vertex id outside [0, n_vertices)");
+    if (err & CC_ERR_TABLE) return hive_fail(ctx, HIVE_ERR_STATE, "mesh_cleanup_cc: the edge table ran full");
+    if (err & CC_ERR_UNION) return hive_fail(ctx, HIVE_ERR_STATE, "mesh_cleanup_cc: a union kept losing its compare-and-swap (%d tries)", CC_CAS_CAP);
+    return HIVE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -519,6 +852,144 @@ int hive_fg_frame_mesh(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mas
     bbox[3] = tot[0] ? box[3] + 1 : box[3];
     HIVE_REQUIRE(ctx, (int64_t)tot[0] <= vertex_capacity && (int64_t)tot[1] <= face_capacity, "fg_frame_mesh: %u vertices / %u faces do not fit the buffers (%lld / %lld)",
                  tot[0], tot[1], (long long)vertex_capacity, (long long)face_capacity);
+    return HIVE_OK;
+}
+
+int hive_mesh_cleanup_cc(hive_ctx *ctx, const int32_t *faces, int64_t n_faces, int64_t n_vertices, int is_object, double min_len, int mem, int32_t *out_faces,
+                         int32_t *out_vertex_index, int64_t *n_faces_out, int64_t *n_vertices_out) {
+    HIVE_ENTER(ctx);
+    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
+    HIVE_REQUIRE(ctx, n_faces_out && n_vertices_out, "mesh_cleanup_cc: NULL argument");
+    HIVE_REQUIRE(ctx, n_faces >= 0 && n_faces < (1ll << 29) && n_vertices >= 0 && n_vertices < (1ll << 30), "mesh_cleanup_cc: bad sizes (%lld faces, %lld vertices)",
+                 (long long)n_faces, (long long)n_vertices);
+    HIVE_REQUIRE(ctx, (n_faces == 0 || (faces && out_faces)) && (n_vertices == 0 || out_vertex_index), "mesh_cleanup_cc: NULL argument");
+    HIVE_REQUIRE(ctx, mem == HIVE_MEM_HOST || mem == HIVE_MEM_DEVICE, "mesh_cleanup_cc: bad mem kind %d", mem);
+    *n_faces_out = 0;
+    *n_vertices_out = 0;
+    if (n_vertices == 0) {  // no vertex: a face can only reference ids out of range
+        HIVE_REQUIRE(ctx, n_faces == 0, "mesh_cleanup_cc: a face references a vertex id outside [0, n_vertices)");
+        return HIVE_OK;
+    }
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const long long fcap = std::max<long long>(n_faces, 1);
+    const size_t off_out_faces = align((size_t)fcap * 12), off_out_vi = off_out_faces + align((size_t)fcap * 12);
+    const size_t off_cc = mem == HIVE_MEM_HOST ? off_out_vi + align((size_t)n_vertices * 4) : 0;
+    CCParams p{};
+    unsigned *bv, *bf;
+    int nb;
+    const size_t cc_bytes = cc_layout(nullptr, fcap, n_vertices, p, &bv, &bf, &nb);
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_cc + cc_bytes);
+    if (rc) return rc;
+    char *base = (char *)ctx->d_scratch;
+    cc_layout(base + off_cc, fcap, n_vertices, p, &bv, &bf, &nb);
+    const int32_t *d_faces = faces;
+    int32_t *d_out_faces = out_faces, *d_out_vi = out_vertex_index;
+    if (mem == HIVE_MEM_HOST) {
+        if (n_faces && (rc = hive_upload(ctx, base, faces, (size_t)n_faces * 12))) return rc;
+        d_faces = (const int32_t *)base;
+        d_out_faces = (int32_t *)(base + off_out_faces);
+        d_out_vi = (int32_t *)(base + off_out_vi);
+    }
+    unsigned *sc = ctx->d_scalars + CC_SCALARS;
+    const unsigned counts[2] = {(unsigned)n_vertices, (unsigned)n_faces};
+    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(sc, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream));
+    p.counts = sc;
+    p.err = sc + 2;
+    p.best = (unsigned long long *)(sc + 4);
+    p.faces = d_faces;
+    p.min_len = min_len;
+    p.is_object = is_object ? 1 : 0;
+    cc_launch(ctx, p, bv, bf, nb, sc, d_out_faces, fcap, d_out_vi);
+    HIVE_CHECK_HIP(ctx, hipGetLastError());
+    unsigned back[8];
+    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(back, sc, sizeof(back), hipMemcpyDeviceToHost, ctx->stream));
+    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = cc_error(ctx, back[2]))) return rc;
+    *n_vertices_out = back[6];
+    *n_faces_out = back[7];
+    if (mem == HIVE_MEM_HOST) {
+        if (back[7]) HIVE_CHECK_HIP(ctx, hipMemcpy(out_faces, d_out_faces, (size_t)back[7] * 12, hipMemcpyDeviceToHost));
+        if (back[6]) HIVE_CHECK_HIP(ctx, hipMemcpy(out_vertex_index, d_out_vi, (size_t)back[6] * 4, hipMemcpyDeviceToHost));
+    }
+    return HIVE_OK;
+}
+
+int hive_fg_frame_mesh_cc(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int H, int W, const double Kinv[9], const double K[9], const double R[9],
+                          const double t[3], double max_pixel_distance, double max_depth_distance, int is_object, double min_len, double *d_vertices,
+                          int64_t vertex_capacity, int32_t *d_faces, int64_t face_capacity, int32_t *d_uv, int64_t *n_vertices, int64_t *n_faces, int32_t bbox[4], int64_t before[2]) {
+    HIVE_ENTER(ctx);
+    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
+    HIVE_REQUIRE(ctx, d_depth && Kinv && K && R && t && d_vertices && d_faces && d_uv && n_vertices && n_faces && bbox, "fg_frame_mesh_cc: NULL argument");
+    HIVE_REQUIRE(ctx, H > 0 && W > 0 && (long long)H * W < (1ll << 27), "fg_frame_mesh_cc: bad image size %dx%d", H, W);
+    HIVE_REQUIRE(ctx, vertex_capacity > 0 && face_capacity > 0, "fg_frame_mesh_cc: empty output buffers");
+    const int n = H * W, nb = (n + TILE - 1) / TILE;
+    const long long fcap = (long long)MAX_PIXEL_FACES * n;  // every pixel's faces fit: the grid's faces land in scratch, the survivors in d_faces
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // device scratch: grid block counts x 2 | vid | the grid's faces | the clean-up's tables
+    const size_t off_bf = align((size_t)nb * 4), off_vid = off_bf + align((size_t)nb * 4), off_faces = off_vid + align((size_t)n * 4);
+    const size_t off_cc = off_faces + align((size_t)fcap * 12);
+    CCParams p{};
+    unsigned *cbv, *cbf;
+    int cnb;
+    const size_t cc_bytes = cc_layout(nullptr, fcap, n, p, &cbv, &cbf, &cnb);
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_cc + cc_bytes);
+    if (rc) return rc;
+    char *base = (char *)ctx->d_scratch;
+    cc_layout(base + off_cc, fcap, n, p, &cbv, &cbf, &cnb);
+    unsigned *bv = (unsigned *)base, *bf = (unsigned *)(base + off_bf);
+    int *vid = (int *)(base + off_vid);
+    int32_t *grid_faces = (int32_t *)(base + off_faces);
+    unsigned *sc = ctx->d_scalars + CC_SCALARS;  // [0] = grid vertices, [1] = grid faces, ..., [6] / [7] = vertices / faces kept, [8..11] = the texture window's box
+    GridParams gp{H, W, max_pixel_distance, (float)max_depth_distance};
+    FrameMeshCam cam;
+    memcpy(cam.Kinv, Kinv, sizeof(cam.Kinv));
+    memcpy(cam.R, R, sizeof(cam.R));
+    memcpy(cam.t, t, sizeof(cam.t));
+    WindowParams wp;
+    memcpy(wp.K, K, sizeof(wp.K));
+    memcpy(wp.R, R, sizeof(wp.R));
+    memcpy(wp.t, t, sizeof(wp.t));
+    wp.scale = 1.0;
+    p.counts = sc;
+    p.err = sc + 2;
+    p.best = (unsigned long long *)(sc + 4);
+    p.faces = grid_faces;
+    p.min_len = min_len;
+    p.is_object = is_object ? 1 : 0;
+    // hive_fg_frame_mesh's triangulation + face filter, into scratch
+    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, gp, bv, bf);
+    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, bf, nb, sc, (int *)(sc + 8));
+    hipLaunchKernelGGL(grid_vid_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, n, (const unsigned *)bv, vid);
+    hipLaunchKernelGGL(grid_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, gp, (const unsigned *)bf, (const int *)vid, grid_faces, fcap);
+    // the clean-up: survivors into d_faces, remapped to the referenced vertices; the pixels' vertex rows follow the vertex map
+    cc_launch(ctx, p, cbv, cbf, cnb, sc, d_faces, (long long)face_capacity, nullptr);
+    hipLaunchKernelGGL(cc_remap_vid_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, vid, n, (const int *)p.vmap, (const unsigned *)sc, (long long)n);
+    hipLaunchKernelGGL(grid_vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_depth, (const int *)vid, n, W, cam, d_vertices, (long long)vertex_capacity);
+    // the texture window over the vertices that are left
+    const dim3 wgrid((unsigned)std::min<long long>((std::min<long long>(n, vertex_capacity) + 255) / 256, (long long)ctx->num_cus * 4));
+    hipLaunchKernelGGL(window_project_dev_kernel, wgrid, dim3(256), 0, ctx->stream, (const double *)d_vertices, (const unsigned *)(sc + 6), (long long)vertex_capacity, wp,
+                       d_uv, (int *)(sc + 8));
+    hipLaunchKernelGGL(window_shift_dev_kernel, wgrid, dim3(256), 0, ctx->stream, d_uv, (const unsigned *)(sc + 6), (long long)vertex_capacity, (const int *)(sc + 8));
+    HIVE_CHECK_HIP(ctx, hipGetLastError());
+    // ONE read-back: {grid counts, error word, selection, kept counts, box[4]} through pinned memory
+    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
+    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_pinned_small, sc, 12 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned *back = (const unsigned *)ctx->h_pinned_small;
+    if ((rc = cc_error(ctx, back[2]))) return rc;
+    const int *box = (const int *)(back + 8);
+    *n_vertices = back[6];
+    *n_faces = back[7];
+    bbox[0] = box[0];
+    bbox[1] = box[1];
+    bbox[2] = back[6] ? box[2] + 1 : box[2];
+    bbox[3] = back[6] ? box[3] + 1 : box[3];
+    if (before) {
+        before[0] = back[0];
+        before[1] = back[1];
+    }
+    HIVE_REQUIRE(ctx, (int64_t)back[6] <= vertex_capacity && (int64_t)back[7] <= face_capacity,
+                 "fg_frame_mesh_cc: %u vertices / %u faces do not fit the buffers (%lld / %lld)", back[6], back[7], (long long)vertex_capacity, (long long)face_capacity);
     return HIVE_OK;
 }
 

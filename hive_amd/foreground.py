@@ -1,12 +1,13 @@
 """Foreground per-frame meshing inner loops of ``Pipeline._create_scene`` (/root/reference/hive/pipeline.py:340-483) on the
 MI355X: the steps behind ``point_cloud_from_depth`` that are dense per-pixel work -- triangulation of the valid pixels, the
-face filter, the texture window and UV coordinates.  Decimation (openmesh), connected-component clean-up and atlas packing
-(trimesh / numpy glue) stay with the reference.
+face filter, the connected-component clean-up that removes floaters, the texture window and UV coordinates.  Decimation (openmesh)
+stays with the reference.
 
   ``grid_faces``                 fused ``_triangulate_faces`` + ``_filter_faces`` for one object mask of one frame
   ``triangulate_faces``          ``Pipeline._triangulate_faces(points)`` (:651-667) for lattice points
   ``filter_faces``               ``Pipeline._filter_faces(points2d, depth, faces, options)`` (:670-694), any face list
   ``get_mesh_texture_and_uv``    ``Pipeline._get_mesh_texture_and_uv(...)`` (:782-808)
+  ``cleanup_with_connected_components``  ``Pipeline._cleanup_with_connected_components(...)`` (:741-779)
 
 The triangulation is the implicit one of the pixel grid (csrc/fgmesh.hip): unit squares and triangles of the valid pixels plus the
 (sqrt 2, sqrt 2, 2) triangles with which a lattice Delaunay bridges one-pixel holes -- after the reference's filter (sides <= 2 pixels by
@@ -108,6 +109,40 @@ def get_mesh_texture_and_uv(vertices, image, camera_matrix, rotation=np.eye(3), 
     return texture, uv
 
 
+def cleanup_with_connected_components(vertices, faces, is_object=True, min_components=5, ctx=None):
+    """``Pipeline._cleanup_with_connected_components`` (/root/reference/hive/pipeline.py:741-779) in one library call (``hive_mesh_cleanup_cc``): the
+    components of trimesh's face adjacency (faces sharing an edge that exactly two faces use; a face without such a neighbour is in no component and
+    goes) with at least ``min_components`` faces survive -- only the largest of them (on a tie the one with the smallest face index) when ``is_object``.
+    Returns (vertices, faces) of the same kind as the inputs (numpy arrays or device tensors): the vertices some input face references, in input order
+    (``Trimesh(process=True)`` drops the others before ``update_faces``; it may also reorder and merge coincident vertices, which this does not -- equal up
+    to vertex order), and the surviving faces in order, indexing them.  Without faces every vertex is kept."""
+    validate_shape(vertices, 'vertices', expected_shape=(None, 3))
+    validate_shape(faces, 'faces', expected_shape=(None, 3))
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    n_faces, n_verts = ctypes.c_int64(0), ctypes.c_int64(0)
+    if _is_torch(faces) or _is_torch(vertices):
+        import torch
+        dev = faces.device if _is_torch(faces) else vertices.device
+        ctx = ctx or _lib.default_context(dev.index or 0)
+        ctx.follow_torch_stream()
+        f = (faces if _is_torch(faces) else torch.from_numpy(np.asarray(faces))).to(device=dev, dtype=torch.int32).contiguous()
+        out_f = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        out_vi = torch.empty(nv, dtype=torch.int32, device=dev)
+        ctx.check(ctx.lib.hive_mesh_cleanup_cc(ctx.handle, ptr(f), nf, nv, int(bool(is_object)), float(min_components), MEM_DEVICE, ptr(out_f), ptr(out_vi),
+                                               ctypes.byref(n_faces), ctypes.byref(n_verts)))
+        keep = out_vi[:n_verts.value].long()
+        v = vertices if _is_torch(vertices) else torch.from_numpy(np.asarray(vertices)).to(dev)
+        out_dtype = faces.dtype if _is_torch(faces) else torch.int32
+        return v.index_select(0, keep.to(v.device)), out_f[:n_faces.value].to(out_dtype)
+    ctx = ctx or _lib.default_context()
+    f = np.ascontiguousarray(faces, dtype=np.int32)
+    out_f = np.empty((nf, 3), np.int32)
+    out_vi = np.empty(nv, np.int32)
+    ctx.check(ctx.lib.hive_mesh_cleanup_cc(ctx.handle, ptr(f), nf, nv, int(bool(is_object)), float(min_components), MEM_HOST, ptr(out_f), ptr(out_vi),
+                                           ctypes.byref(n_faces), ctypes.byref(n_verts)))
+    return np.asarray(vertices)[out_vi[:n_verts.value]], out_f[:n_faces.value].astype(np.asarray(faces).dtype, copy=False)
+
+
 class FrameMeshBuffers:
     """Device buffers of worst-case size for ``frame_mesh`` (H W vertices, 4 H W faces), reused from frame to frame."""
 
@@ -121,14 +156,18 @@ class FrameMeshBuffers:
 
 
 def frame_mesh(depth, mask, image, camera_matrix, rotation=np.eye(3), translation=np.zeros((3, 1)), options: MeshFilteringOptions = None, ctx=None,
-               buffers: FrameMeshBuffers = None):
+               buffers: FrameMeshBuffers = None, enable_cc_analysis=False, is_object=True, min_components=5):
     """One object of one frame, device-resident, in ONE library call (``hive_fg_frame_mesh``): what the loop body of ``process_frame``
-    (/root/reference/hive/pipeline.py:383-461) computes between the binary mask and the texture atlas, minus its CPU-library stages (decimation, connected
-    components, billboard) --
+    (/root/reference/hive/pipeline.py:383-461) computes between the binary mask and the texture atlas, minus its CPU-library stages (decimation, billboard) --
 
         vertices = point_cloud_from_depth(depth, mask, K, R, t)             (:386)
         faces    = _filter_faces(points2d, depth[valid], _triangulate_faces(points2d), options)   (:402-408)
+        vertices, faces = _cleanup_with_connected_components(vertices, faces, is_object, min_components)   (:431-437; only with enable_cc_analysis)
         texture, uv = _get_mesh_texture_and_uv(vertices, rgb, K, R, t)      (:453)
+
+    With ``enable_cc_analysis`` the call is ``hive_fg_frame_mesh_cc``: the floaters go as in ``cleanup_with_connected_components``, the vertices are the ones
+    the filtered faces reference (renumbered) and the texture window covers them; the dict also carries ``before`` = (point-cloud vertices, filtered faces),
+    the counts the reference tests before the clean-up.  Off (the default), the result is ``hive_fg_frame_mesh``'s.
 
     ``depth`` float32 (H, W), ``mask`` bool / uint8 (H, W) or None, ``image`` uint8 (H, W, 3): device tensors (numpy arrays are uploaded).  Returns a dict of
     device tensors -- ``vertices`` float64 (V, 3), ``faces`` int32 (F, 3), ``uv`` int32 (V, 2), ``texture`` uint8 crop -- and ``bbox`` (min_u, min_v, max_u, max_v);
@@ -155,15 +194,27 @@ def frame_mesh(depth, mask, image, camera_matrix, rotation=np.eye(3), translatio
     t = np.ascontiguousarray(translation, dtype=np.float64).reshape(3)
     nv, nf = ctypes.c_int64(0), ctypes.c_int64(0)
     box = np.zeros(4, np.int32)
-    ctx.check(ctx.lib.hive_fg_frame_mesh(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
-                                         float(options.max_depth_distance), ptr(buffers.vertices), buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0],
-                                         ptr(buffers.uv), ctypes.byref(nv), ctypes.byref(nf), ptr(box)))
+    before = None
+    if enable_cc_analysis:
+        counts = np.zeros(2, np.int64)
+        ctx.check(ctx.lib.hive_fg_frame_mesh_cc(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
+                                                float(options.max_depth_distance), int(bool(is_object)), float(min_components), ptr(buffers.vertices),
+                                                buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0], ptr(buffers.uv), ctypes.byref(nv),
+                                                ctypes.byref(nf), ptr(box), ptr(counts)))
+        before = (int(counts[0]), int(counts[1]))
+    else:
+        ctx.check(ctx.lib.hive_fg_frame_mesh(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
+                                             float(options.max_depth_distance), ptr(buffers.vertices), buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0],
+                                             ptr(buffers.uv), ctypes.byref(nv), ctypes.byref(nf), ptr(box)))
     min_u, min_v, max_u, max_v = (int(b) for b in box)
     texture = None
     if nv.value and img is not None:
         texture = img[max(min_v, 0):max_v, max(min_u, 0):max_u, :].clone()  # `image[min_v:max_v, min_u:max_u, :].copy()` (pipeline.py:805)
-    return {"vertices": buffers.vertices[:nv.value], "faces": buffers.faces[:nf.value], "uv": buffers.uv[:nv.value], "texture": texture,
-            "bbox": (min_u, min_v, max_u, max_v)}
+    out = {"vertices": buffers.vertices[:nv.value], "faces": buffers.faces[:nf.value], "uv": buffers.uv[:nv.value], "texture": texture,
+           "bbox": (min_u, min_v, max_u, max_v)}
+    if before is not None:
+        out["before"] = before
+    return out
 
 
 def pack_textures_row(textures, uvs):
@@ -192,12 +243,14 @@ def pack_textures_row(textures, uvs):
 
 
 def process_frame(rgb, depth, mask_encoded, camera_matrix, pose, dilation_options=None, filtering_options: MeshFilteringOptions = None,
-                  disable_coverage_constraint=False, ctx=None, buffers: FrameMeshBuffers = None):
+                  disable_coverage_constraint=False, ctx=None, buffers: FrameMeshBuffers = None, enable_cc_analysis=False):
     """The body of ``process_frame`` in ``Pipeline._create_scene`` (/root/reference/hive/pipeline.py:340-483) for the dynamic objects of ONE frame, device-resident:
     for every object id 1 .. mask_encoded.max(): the binary mask, dilated (``dilate_mask``, :369-370); skipped when it covers less than 1 % of the frame (:374-379); its
     mesh in one library call (``frame_mesh``: point cloud, triangulation + face filter, texture window); skipped with fewer than 9 vertices or no face (:388-391, 410-413);
-    the objects' vertices stacked, their faces offset by the vertices in front, their textures packed in one atlas row (:463-468, 811-866).  The reference's CPU-library
-    stages in between -- decimation (openmesh), connected components (trimesh), billboard -- are outside this build's scope and are NOT applied.
+    the objects' vertices stacked, their faces offset by the vertices in front, their textures packed in one atlas row (:463-468, 811-866).  With ``enable_cc_analysis``
+    (the reference's ``Pipeline.process_frame`` keyword; off by default here) every object goes through the connected-component clean-up (:431-437) with
+    ``filtering_options.min_num_components`` between the face filter and the texture window; an object whose faces all go is still stacked (its vertices and texture,
+    no face), as in the reference.  Decimation (openmesh) and billboard are outside this build's scope and are NOT applied.
 
     ``rgb`` uint8 (H, W, 3+), ``depth`` float32 (H, W), ``mask_encoded`` uint8 (H, W) instance ids (0 = background), ``pose`` the frame's 4 x 4 world-to-camera transform
     (``dataset.camera_trajectory.to_homogenous_transforms()[index]``).  Numpy arrays or device tensors.  Returns None for a frame without a surviving object (the reference
@@ -230,8 +283,10 @@ def process_frame(rgb, depth, mask_encoded, camera_matrix, pose, dilation_option
             mask = grown
         if float(mask.float().mean().item()) < 0.01 and not disable_coverage_constraint:
             continue
-        mesh = frame_mesh(depth_d, mask, rgb_d, camera_matrix, rotation, translation, filtering_options, ctx=ctx, buffers=buffers)
-        if mesh["vertices"].shape[0] < 9 or mesh["faces"].shape[0] < 1:
+        mesh = frame_mesh(depth_d, mask, rgb_d, camera_matrix, rotation, translation, filtering_options, ctx=ctx, buffers=buffers,
+                          enable_cc_analysis=enable_cc_analysis, is_object=True, min_components=filtering_options.min_num_components)
+        n_points, n_filtered = mesh.get("before", (mesh["vertices"].shape[0], mesh["faces"].shape[0]))
+        if n_points < 9 or n_filtered < 1:
             continue
         vertices.append(mesh["vertices"].clone())
         faces.append(mesh["faces"].to(torch.int64) + vertex_count)

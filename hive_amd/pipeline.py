@@ -1,8 +1,9 @@
-"""The background (static scene) half of HIVE's pipeline -- the part the dense-compute path serves:
-dataset -> key frames -> TSDF fusion -> mesh (/root/reference/hive/pipeline.py:258-286, 871-901).
+"""HIVE's pipeline for the part the dense-compute path serves: dataset -> key frames -> TSDF fusion -> background mesh
+(/root/reference/hive/pipeline.py:258-286, 871-901), then the per-frame foreground meshes (``_create_scene``, :309-497) with the
+connected-component clean-up and decimation disabled.
 
-The foreground per-frame meshing, glTF export, draco compression and the WebXR viewer of the reference's
-``Pipeline`` are outside the scope of this build.
+glTF export, draco compression, scene centring and the WebXR viewer of the reference's ``Pipeline`` are outside the scope of this
+build; meshes are written as PLY.
 """
 import argparse
 import json
@@ -12,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from hive_amd import fusion
+from hive_amd import foreground, fusion
 from hive_amd.dataset_adaptors import get_dataset
 from hive_amd.io import HiveDataset
 from hive_amd.options import (BackgroundMeshOptions, COLMAPOptions, ForegroundTrajectorySmoothingOptions, MaskDilationOptions, MeshDecimationOptions,
@@ -20,8 +21,9 @@ from hive_amd.options import (BackgroundMeshOptions, COLMAPOptions, ForegroundTr
 from hive_amd.utils import timed_block
 
 
-def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None):
-    """Binary little-endian PLY (trimesh, which the reference exports glb with, is not a dependency here)."""
+def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None, *, vertex_uv=None, texture_file=None):
+    """Binary little-endian PLY (trimesh, which the reference exports glb with, is not a dependency here).  ``vertex_uv`` (V, 2) adds float
+    ``texture_u`` / ``texture_v`` vertex properties and ``texture_file`` a ``comment TextureFile <name>`` header line (the form MeshLab reads)."""
     vertices = np.asarray(vertices, np.float32)
     faces = np.asarray(faces, np.int32)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
@@ -29,6 +31,8 @@ def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None):
         fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if vertex_colors is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if vertex_uv is not None:
+        fields += [("texture_u", "<f4"), ("texture_v", "<f4")]
     v = np.empty(len(vertices), dtype=fields)
     v["x"], v["y"], v["z"] = vertices.T
     if vertex_normals is not None:
@@ -36,11 +40,17 @@ def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None):
     if vertex_colors is not None:
         c = np.asarray(vertex_colors)
         v["red"], v["green"], v["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    if vertex_uv is not None:
+        uv = np.asarray(vertex_uv, np.float32)
+        v["texture_u"], v["texture_v"] = uv[:, 0], uv[:, 1]
     f = np.empty(len(faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     f["n"], f["i"] = 3, faces
     names = {"<f4": "float", "u1": "uchar"}
     with open(path, "wb") as out:
-        header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+        header = ["ply", "format binary_little_endian 1.0"]
+        if texture_file is not None:
+            header += [f"comment TextureFile {texture_file}"]
+        header += [f"element vertex {len(v)}"]
         header += [f"property {names[t]} {n}" for n, t in fields]
         header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
         out.write(("\n".join(header) + "\n").encode())
@@ -50,9 +60,9 @@ def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None):
 
 class Pipeline:
     """The reference's ``Pipeline`` (/root/reference/hive/pipeline.py:59-262) for the part this build serves: dataset -> key frames
-    -> TSDF fusion -> background mesh.  Constructor, ``from_command_line`` and ``run`` take the reference's arguments; the stages
-    behind the other option groups (foreground meshes, decimation, glTF / draco export, WebXR) are outside this build's scope
-     and ``run`` says so where the reference would run them."""
+    -> TSDF fusion -> background mesh -> per-frame foreground meshes.  Constructor, ``from_command_line`` and ``run`` take the reference's
+    arguments; the stages behind the other option groups (decimation, billboard, trajectory smoothing, glTF / draco export, WebXR) are
+    outside this build's scope and ``run`` says so where the reference would run them."""
     mesh_folder = "mesh"
     bundle_fusion_folder = "bundle_fusion"
 
@@ -120,9 +130,42 @@ class Pipeline:
         logging.info(f"Creating background mesh from {len(frame_set)} key frames...")
         return fusion.tsdf_fusion(dataset, options, num_frames=num_frames, frame_set=frame_set)
 
+    def create_foreground_meshes(self, dataset: HiveDataset, num_frames: int, folder: str):
+        """``_create_scene`` (pipeline.py:309-497) for the dynamic objects of frames 0 .. num_frames - 1: every frame through ``foreground.process_frame``
+        with the connected-component clean-up on; a frame with a surviving object gives ``<folder>/%06d.ply`` (vertices in the frame of bg.ply, atlas uv)
+        and ``<folder>/%06d.png`` (its texture atlas).  Decimation, billboard and trajectory smoothing are not applied."""
+        from PIL import Image
+        not_applied = []
+        if self.decimation_options.num_faces_object > 0:
+            not_applied.append("decimation")
+        if self.options.billboard:
+            not_applied.append("billboard")
+        if self.fts_options.num_epochs > 0:
+            not_applied.append("trajectory_smoothing")
+        self.profiling.setdefault("foreground_reconstruction", {})["not_applied"] = not_applied
+        if not_applied:
+            logging.info(f"Foreground meshes: {', '.join(not_applied)} outside this build's scope, not applied.")
+        os.makedirs(folder, exist_ok=True)
+        poses = dataset.camera_trajectory.to_homogenous_transforms()
+        buffers = None
+        for i in range(num_frames):
+            depth = dataset.depth_dataset[i]
+            if buffers is None:
+                buffers = foreground.FrameMeshBuffers(*depth.shape[:2])
+            mesh = foreground.process_frame(dataset.rgb_dataset[i], depth, dataset.mask_dataset[i], dataset.camera_matrix, poses[i], self.dilation_options,
+                                            self.filtering_options, disable_coverage_constraint=self.options.disable_coverage_constraint, buffers=buffers,
+                                            enable_cc_analysis=True)
+            if mesh is None:
+                continue
+            name = f"{i:06d}.png"
+            Image.fromarray(mesh["texture"].cpu().numpy()).save(os.path.join(folder, name))
+            write_ply(os.path.join(folder, f"{i:06d}.ply"), mesh["vertices"].cpu().numpy(), mesh["faces"].cpu().numpy(),
+                      vertex_uv=mesh["uv"].cpu().numpy(), texture_file=name)
+
     def run(self, dataset=None, adaptor=None, compress=True, *, estimate_depth=None):
-        """pipeline.py:172-262 up to the background mesh: load (or convert) the dataset, fuse the static scene, write
-        ``<output>/mesh/bg.ply`` (vertex colours in sRGB as pipeline.py:281-282) and ``profiling.json``; returns the mesh.
+        """pipeline.py:172-262: load (or convert) the dataset, fuse the static scene, write ``<output>/mesh/bg.ply`` (vertex colours in sRGB as
+        pipeline.py:281-282), then -- unless ``background_only`` -- the foreground meshes of every frame (``create_foreground_meshes``: ``mesh/fg/``),
+        and ``profiling.json``; returns the background mesh.
 
         Reference form: ``run(dataset: Optional[HiveDataset] = None, adaptor: Optional[DatasetAdaptor] = None, compress=True)`` with the
         paths in ``storage_options``.  Shorthand of earlier rounds: ``run(dataset_path, output_path, estimate_depth=False)``."""
@@ -144,9 +187,6 @@ class Pipeline:
             n = dataset.num_frames if self.num_frames == -1 else min(self.num_frames, dataset.num_frames)
         with timed_block("Created background mesh in", self.profiling, ("timing", "background_reconstruction", "total")):
             mesh = self.create_static_mesh(dataset, num_frames=n, options=self.background_mesh_options)
-        if not self.options.background_only:
-            logging.info("Foreground meshes, decimation, glTF / draco export and the WebXR viewer are outside this build's scope: "
-                         "the background mesh is written as PLY.")
         # vertex colours -> sRGB as pipeline.py:281-282
         colors = np.asarray(mesh.visual.vertex_colors)[:, :3]
         colors = (255 * np.power(colors / 255, 2.2)).astype(np.uint8)
@@ -154,6 +194,9 @@ class Pipeline:
         os.makedirs(out, exist_ok=True)
         with timed_block("Wrote mesh data in", self.profiling, ("timing", "mesh_export")):
             write_ply(os.path.join(out, "bg.ply"), mesh.vertices, mesh.faces, colors, mesh.vertex_normals)
+        if not self.options.background_only:
+            with timed_block("Created foreground meshes in", self.profiling, ("timing", "foreground_reconstruction", "total")):
+                self.create_foreground_meshes(dataset, n, os.path.join(out, "fg"))
         with open(os.path.join(dataset.base_path, "profiling.json"), "w") as f:  # pipeline.py:251
             json.dump(self.profiling, f, indent=2)
         return mesh

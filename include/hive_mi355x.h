@@ -263,6 +263,23 @@ int hive_grid_mesh(hive_ctx *ctx, const float *depth, const uint8_t *mask, int H
 int hive_fg_frame_mesh(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int H, int W, const double Kinv[9], const double K[9], const double R[9],
                        const double t[3], double max_pixel_distance, double max_depth_distance, double *d_vertices, int64_t vertex_capacity, int32_t *d_faces,
                        int64_t face_capacity, int32_t *d_uv, int64_t *n_vertices, int64_t *n_faces, int32_t bbox[4]);
+/* _cleanup_with_connected_components (:741-779, trimesh 3.9's face_adjacency + graph.connected_components): two faces are adjacent when they share an
+ * edge (unordered vertex pair) that exactly two faces use; a face without an adjacent face belongs to no component and is always removed; a component
+ * survives with at least min_len faces; is_object != 0 keeps only the largest survivor (on a tie the one whose smallest face index is smallest), 0 keeps
+ * all of them.  Survivors keep their order.  Vertices: those at least one INPUT face references (Trimesh(process=True) drops the others before any face
+ * goes), in input order -- out_vertex_index i32 [n_vertices_out] lists their input ids, out_faces i32 [n_faces_out][3] index that list (no merging of
+ * coincident vertices, so the result equals trimesh's up to vertex order).  Without faces every vertex is kept.  faces i32 [n_faces][3] with ids in
+ * [0, n_vertices), n_vertices < 2^30, n_faces < 2^29; out_faces room for n_faces rows, out_vertex_index for n_vertices; mem = where all three live. */
+int hive_mesh_cleanup_cc(hive_ctx *ctx, const int32_t *faces, int64_t n_faces, int64_t n_vertices, int is_object, double min_len, int mem,
+                         int32_t *out_faces, int32_t *out_vertex_index, int64_t *n_faces_out, int64_t *n_vertices_out);
+/* hive_fg_frame_mesh with the clean-up above between the face filter and the texture window (pipeline.py:402-453 with decimation off): the faces that
+ * survive hive_mesh_cleanup_cc(is_object, min_len) in d_faces, the vertices the filtered faces reference in d_vertices (renumbered in row-major pixel
+ * order), uv and bbox over those vertices.  before (optional) = {valid pixels, faces after the filter}: the counts the reference tests before the
+ * clean-up (pipeline.py:388, 410).  Same buffers and one read-back; H W < 2^27.  hive_fg_frame_mesh itself is unchanged. */
+int hive_fg_frame_mesh_cc(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int H, int W, const double Kinv[9], const double K[9], const double R[9],
+                          const double t[3], double max_pixel_distance, double max_depth_distance, int is_object, double min_len, double *d_vertices,
+                          int64_t vertex_capacity, int32_t *d_faces, int64_t face_capacity, int32_t *d_uv, int64_t *n_vertices, int64_t *n_faces, int32_t bbox[4],
+                          int64_t before[2]);
 /* _filter_faces (:670-694) for an explicit face list of any triangulation: points2d i32 [n][2] (u, v), depth f32 [n], faces i32
  * [F][3] -> the faces whose three edges pass both limits, order preserved, into out_faces (capacity F). */
 int hive_filter_faces(hive_ctx *ctx, const int32_t *points2d, const float *depth, int64_t n_points, const int32_t *faces,
