@@ -2,7 +2,7 @@
 """Headline benchmark: frames/sec of the hot path (DPT-Hybrid depth + TSDF integrate) at 640 x 480 into a
 512^3 volume (BASELINE.json `metric`; configs[1] at N = 1, configs[2] at N > 1).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +12,15 @@ SURVEY.md 8d) -> preprocess -> DPT-Hybrid (seeded random weights of the real arc
 has surfaces inside the volume; bf16 or --dtype fp16, HIP engine) -> f32 depth tail
 + uint16-mm hand-off -> TSDF integrate.
 
-One run prints ONE JSON line that covers the BASELINE configurations this command can reach:
+One run prints ONE JSON line.  A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+`value` / `ms_per_step` with the timed volume's own counters (`timed_volume_check`, read after the clock stopped).  `--full` adds everything else: the line
+then covers the BASELINE configurations this command can reach, the rooflines, the recount behind `timed_volume_check.pass` and the CPU baseline:
   N = 1: the headline (configs[1], `value`), the same job in float16 -- the reference's own type -- as `value_fp16` (with `small_batch`: the network object at
          batches of 1 and 8 in that type, the reference's literal one-frame loop), and a bounded `config4` leg
          (configs[3]: 1920 x 1080 frames, DPT-Large at the reference's 864 x 480 network size, 1024^3 volume).
   N > 1: frames are independent units.  The headline `value` is the WEAK job ("scaling": "weak": N * K * B frames, a contiguous block of K
          steps per rank, per-GPU work = the N = 1 job, no collective on the data path, the shared volume merged ONCE inside the timed
-         region), and the same run also times BASELINE configs[2] literally under the key `strong`: the SAME K * B frames split in
+         region), and a --full run also times BASELINE configs[2] literally under the key `strong`: the SAME K * B frames split in
          contiguous blocks over the ranks, one merge (fixed total work; the merge weighs more the shorter the per-rank share).
          `--scaling strong` swaps the two (headline = strong, the weak job under `weak`).
 The merge:
@@ -62,8 +64,10 @@ def parse_args():
     ap.add_argument("--merge", default="sum", choices=["sum", "exact"], help="N > 1: how the shared volume is merged")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"], help="16-bit type of the headline network (north_star: bf16; the reference runs fp16)")
     ap.add_argument("--no-overlap", action="store_true", help="TSDF sweeps on the network's stream (default: on a second stream, under the next batch's network)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the legs beside the headline job (fp16 job, config4, the other scaling mode at N > 1)")
+    ap.add_argument("--full", action="store_true", help="after the headline job, also the legs beside it (fp16 job, no-overlap job, config4, the other scaling "
+                                                        "mode at N > 1), the rooflines, the mesh, the weight-sum recount and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full without the legs beside the headline job (fp16 job, config4, the other scaling mode at N > 1)")
     ap.add_argument("--notes", action="store_true", help="keep the explanatory note strings in the JSON line (default: numbers only -- the notes are DESIGN.md section 6; "
                                                          "the full line is ~10 KB, the compact one ~4 KB, which a log tail does not cut)")
     ap.add_argument("--timed-only", action="store_true", help="profiling runs: only the headline timed job (no roofline / cpu_baseline / extra legs)")
@@ -101,6 +105,48 @@ def host_cores():
         pass
     env = os.environ.get("HIVE_BENCH_CPU_THREADS")
     return int(env) if env else min(cores, 64)
+
+
+def make_sequence(num_frames, height, width, seed=1234, yaw_step_deg=2.4):
+    """hive_amd.synthetic.make_sequence with its default room, bit for bit, the frames' ray casts and colour patterns on a thread pool (numpy lets go of
+    the GIL inside them).  The seeded draws stay on this thread in the library's order -- per frame the colour noise, then the invalid-pixel mask -- and
+    each frame's worker is handed its own.  One frame after another, the 150 frames of the headline job take ~12 s of host time before the first step;
+    tests/test_bench_cpu.py holds the two to the same arrays."""
+    from concurrent.futures import ThreadPoolExecutor
+    from hive_amd import synthetic
+    size, margin, invalid = 5.12, 0.32, 0.02  # make_sequence's defaults: volume_size, room_margin, invalid_fraction
+    rng = np.random.default_rng(seed)
+    K = synthetic.scaled_intrinsics(height, width)
+    poses = synthetic.circular_trajectory(num_frames, size, yaw_step_deg=yaw_step_deg)
+    color = np.empty((num_frames, height, width, 3), np.uint8)
+    depth = np.empty((num_frames, height, width), np.float32)
+
+    class Drawn:  # the generator room_colour draws its noise from: hands back what this thread drew for the frame
+        def __init__(self, noise):
+            self.noise = noise
+
+        def normal(self, loc, scale, size):
+            assert self.noise.shape == tuple(size)
+            return self.noise
+
+    def frame(i, noise, uniform):
+        d, pts = synthetic.raycast_room_depth(poses[i], K, height, width, margin, size - margin)
+        color[i] = synthetic.room_colour(pts, Drawn(noise), size)
+        d = d.copy()
+        d[uniform < invalid] = 0.0
+        depth[i] = d
+
+    workers = min(host_cores(), 16)
+    with ThreadPoolExecutor(workers) as pool:
+        pending = []
+        for i in range(num_frames):
+            noise = rng.normal(0.0, 4.0, size=(height, width, 3))
+            pending.append(pool.submit(frame, i, noise, rng.random((height, width))))
+            if len(pending) >= 2 * workers:  # (bounded: a 1080p frame's draws are 65 MB)
+                pending.pop(0).result()
+        for f in pending:
+            f.result()
+    return {"color": color, "depth": depth, "K": K, "poses": poses}
 
 
 def cpu_baseline(seq, voxel, K, budget_s=20.0):
@@ -238,7 +284,7 @@ def config4_leg(device, ctx, steps=2, batch=48, overlap=True, prefetch=True, uni
     H, W, T = 1080, 1920, min(unique_frames, batch * (steps + 1))  # (the job wraps around a short sequence, as the headline job does: ray-casting a 1080p frame on the host takes a second)
     frame_ids = lambda i: [(i * batch + j) % T for j in range(batch)]
     net_h, net_w = depth_mod.network_size(H, W)
-    seq = synthetic.make_sequence(num_frames=T, height=H, width=W, yaw_step_deg=2.4)
+    seq = make_sequence(T, H, W, yaw_step_deg=2.4)
     model = DPTDepthModel(path=None, scale=depth_mod.DPT_SCALE, shift=depth_mod.DPT_SHIFT, invert=True, backbone="vitl16_384", engine="hip")
     seeded_init(model, seed=1234)
     model = model.eval().to(memory_format=torch.channels_last).to(torch.bfloat16).to(device)
@@ -374,7 +420,7 @@ def main():
     headline_strong = world > 1 and (args.scaling == "strong" or exact)  # (exact: every rank integrates every frame -- fixed total work by construction)
     extra_legs = not (args.no_extra_legs or args.timed_only)
     # the synthetic sequence: the same one on every rank (the job is a stretch of its wrapping frame index)
-    seq = synthetic.make_sequence(num_frames=T, height=H, width=W, seed=1234, yaw_step_deg=360.0 / T)
+    seq = make_sequence(T, H, W, seed=1234, yaw_step_deg=360.0 / T)
     K = seq["K"]
     poses = seq["poses"]
     frames_host = torch.from_numpy(seq["color"]).pin_memory()  # uint8 [T, H, W, 3]
@@ -522,6 +568,47 @@ def main():
             print(json.dumps({"value": total_frames / elapsed, "unit": "frames/s", "ms_per_step": elapsed / args.steps * 1e3,
                               "avg_integrate_us": kernel_ms / max(n_launch, 1) * 1e3, "integrate_launches": n_launch, "tsdf_overlap": overlap,
                               "timed_volume_check": volume_proof, "note": "--timed-only: no roofline / cpu_baseline / extra legs"}))
+        return
+
+    def headline(n_upd=None):
+        """The line's head: the headline job's figures and configuration (`n_upd`: the measured N_upd mean and fraction, --full)."""
+        dim_list = [int(d) for d in (merger.dims if exact else volume.vol_dim)]
+        dims = "x".join(str(d) for d in dim_list)
+        vol_name = f"{dim_list[0]}^3" if len(set(dim_list)) == 1 else dims  # (the real dims: --voxel changes them)
+        merge_note = ""
+        scaling = "strong" if headline_strong else "weak"  # (N = 1: the weak job's one-rank case -- per-GPU work fixed as N grows)
+        if world > 1:
+            share = (f"the same {args.steps} x {B} frames split in contiguous blocks over the ranks" if headline_strong
+                     else f"{world} x {args.steps} x {B} frames, a contiguous block of {args.steps} steps per rank")
+            merge_note = (f", {share}, frames all-gathered, every rank integrates all frames into its x-slab (bit-identical to 1 GPU), slabs all-gathered"
+                          if exact else f", frame-sharded ({share}), shared volume merged once by reduce-scatter of the 5 accumulator planes + all-gather of the 3 "
+                                        f"volumes (RCCL), inside the timed region")
+        return {
+            "metric": f"frames/sec (depth+TSDF integrate) @{W}x{H}, {vol_name} vol" + ("" if world == 1 else f", {world} GPUs, {scaling} scaling ({total_frames} frames)"),
+            "value": total_frames / elapsed,
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {
+                "workload": f"synthetic {W}x{H}x{T} RGB (seeded room trajectory), host-resident uint8 frames uploaded in the timed region, DPT-Hybrid depth "
+                            f"(seeded random weights: depth 1-7 m, {args.dtype}, {args.engine} engine) + {dims} TSDF integrate, {B} frames/step" + merge_note,
+                "frames_per_step": B, "frames_total": total_frames, "image": [H, W], "volume": dims, "voxel_m": args.voxel,
+                **(n_upd or {}), "merge": (args.merge if world > 1 else None), "tsdf_overlap": overlap, "scaling_mode": scaling,
+            },
+        }
+
+    if not args.full:
+        if rank == 0:
+            out = headline()
+            out["timed_volume_check"] = volume_proof
+            print(json.dumps(compact(out, args.notes)))
         return
 
     # ---- the other scaling mode at N > 1 (BASELINE configs[2] literally when the headline is the weak job) -------------------------------------
@@ -759,39 +846,8 @@ def main():
 
     if rank != 0:
         return
-    dim_list = [int(d) for d in (merger.dims if exact else volume.vol_dim)]
-    dims = "x".join(str(d) for d in dim_list)
-    vol_name = f"{dim_list[0]}^3" if len(set(dim_list)) == 1 else dims  # (the real dims: --voxel changes them)
-    merge_note = ""
-    scaling = "strong" if headline_strong else "weak"  # (N = 1: the weak job's one-rank case -- per-GPU work fixed as N grows)
-    if world > 1:
-        share = (f"the same {args.steps} x {B} frames split in contiguous blocks over the ranks" if headline_strong
-                 else f"{world} x {args.steps} x {B} frames, a contiguous block of {args.steps} steps per rank")
-        merge_note = (f", {share}, frames all-gathered, every rank integrates all frames into its x-slab (bit-identical to 1 GPU), slabs all-gathered"
-                      if exact else f", frame-sharded ({share}), shared volume merged once by reduce-scatter of the 5 accumulator planes + all-gather of the 3 "
-                                    f"volumes (RCCL), inside the timed region")
-    out = {
-        "metric": f"frames/sec (depth+TSDF integrate) @{W}x{H}, {vol_name} vol" + ("" if world == 1 else f", {world} GPUs, {scaling} scaling ({total_frames} frames)"),
-        "value": total_frames / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic",
-        "config": {
-            "workload": f"synthetic {W}x{H}x{T} RGB (seeded room trajectory), host-resident uint8 frames uploaded in the timed region, DPT-Hybrid depth "
-                        f"(seeded random weights: depth 1-7 m, {args.dtype}, {args.engine} engine) + {dims} TSDF integrate, {B} frames/step" + merge_note,
-            "frames_per_step": B, "frames_total": total_frames, "image": [H, W], "volume": dims, "voxel_m": args.voxel,
-            "n_upd_mean": main_roof["n_upd_mean"], "n_upd_fraction": main_roof["n_upd_fraction"], "merge": (args.merge if world > 1 else None),
-            "tsdf_overlap": overlap, "scaling_mode": scaling,
-        },
-        "tsdf_source_stamp": stamp,
-    }
+    out = headline({"n_upd_mean": main_roof["n_upd_mean"], "n_upd_fraction": main_roof["n_upd_fraction"]})
+    out["tsdf_source_stamp"] = stamp
     # key order: a log TAIL shows the end of the line (the driver's tail cut the middle out) -- the side legs first, then the other scaling mode, and
     # the contract's objects last: proof of work, the dominant kernel's roofline, the CPU baseline
     if config4 is not None:

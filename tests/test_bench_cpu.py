@@ -1,4 +1,4 @@
-"""CPU-only checks of bench.py's argument rules and its --dump-outputs writer (the timed job itself needs an MI355X)."""
+"""CPU-only checks of bench.py's argument rules, its synthetic sequence and its --dump-outputs writer (the timed job itself needs an MI355X)."""
 import sys
 
 import numpy as np
@@ -15,6 +15,27 @@ def test_steps_must_be_positive(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "0", "--dump-outputs", "out"])
     args = bench.parse_args()
     assert args.steps == 3 and args.warmup == 0 and args.dump_outputs == "out"
+
+
+def test_full_is_opt_in(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    assert not bench.parse_args().full  # a plain run is the headline job alone
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full"])
+    assert bench.parse_args().full
+
+
+@pytest.mark.parametrize("frames, height, width, seed, yaw", [(5, 48, 64, 1234, 72.0), (9, 30, 40, 7, 2.4)])
+def test_sequence_is_the_librarys(frames, height, width, seed, yaw, monkeypatch):
+    """bench.make_sequence (frames on a thread pool, the seeded draws in order on the caller's thread) gives synthetic.make_sequence's arrays bit for bit,
+    with as many workers as frames in flight and with one."""
+    from hive_amd import synthetic
+    want = synthetic.make_sequence(num_frames=frames, height=height, width=width, seed=seed, yaw_step_deg=yaw)
+    for threads in ("3", "1"):
+        monkeypatch.setenv("HIVE_BENCH_CPU_THREADS", threads)
+        got = bench.make_sequence(frames, height, width, seed=seed, yaw_step_deg=yaw)
+        assert sorted(got) == sorted(want)
+        for key, a in want.items():
+            assert got[key].dtype == a.dtype and np.array_equal(got[key], a), (threads, key)
 
 
 def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path, monkeypatch):

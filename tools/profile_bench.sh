@@ -5,10 +5,11 @@
 #   3. --pmc WRITE_SIZE              -> HBM write bytes
 set -e
 TAG=${1:-r01}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 6 --warmup 2"
+CMD="python3 $REPO/bench.py --full --no-cpu-baseline --steps 6 --warmup 2"
 # first an un-profiled run: MIOpen's find step (cudnn.benchmark) caches its choices in the user db, so the
 # profiled runs below show the steady-state kernels and not the search
 $CMD > $OUT/warm.log 2>&1

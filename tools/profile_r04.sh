@@ -9,6 +9,7 @@
 #   small: kernel trace of tools/probe_small_kernels.py (marching cubes 512^3, unproject, project_bbox, grid_mesh, ...)           -> .../small
 # tools/profile_r04_summary.py condenses them into profiles/r04_*.
 PARTS=${*:-trace pmc valu small}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_r04
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
@@ -17,11 +18,11 @@ ROOM="python3 $GRAFT_REPO_ROOT/tools/probe_integrate.py --reps 1 --frames 32 --y
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has trace; then
   rm -rf $OUT/trace
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $OUT/trace.log 2>&1 || echo "trace failed"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py --full --no-cpu-baseline > $OUT/trace.log 2>&1 || echo "trace failed"
   find $OUT/trace -name "*kernel_trace.csv" -delete
   # the same command with the sweeps on the network's stream: every kernel's duration is its own (what roofline.avg_launch_us is compared with)
   rm -rf $OUT/trace_no_overlap
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_no_overlap -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-overlap > $OUT/trace_no_overlap.log 2>&1 || echo "trace (no overlap) failed"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_no_overlap -- python3 $REPO/bench.py --full --no-cpu-baseline --no-overlap > $OUT/trace_no_overlap.log 2>&1 || echo "trace (no overlap) failed"
   find $OUT/trace_no_overlap -name "*kernel_trace.csv" -delete
 fi
 pmc() {  # name, counters...
@@ -39,7 +40,7 @@ if has small; then
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/small -- python3 $GRAFT_REPO_ROOT/tools/probe_small_kernels.py > $OUT/small.json 2> $OUT/small.err || echo "small failed"
   find $OUT/small -name "*kernel_trace.csv" -delete
 fi
-if has fp16; then timeout -k 10 400 python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --dtype fp16 > $OUT/fp16.log 2>&1 || echo "fp16 failed"; fi
+if has fp16; then timeout -k 10 400 python3 $REPO/bench.py --full --no-cpu-baseline --dtype fp16 > $OUT/fp16.log 2>&1 || echo "fp16 failed"; fi
 if has layers; then timeout -k 10 300 bash $GRAFT_REPO_ROOT/tools/layer_trace.sh 107 bf16 || echo "layers failed"; fi
 for f in $(find $OUT -name "*counter_collection.csv"); do (head -1 $f; grep -E "integrate_kernel|integrate_multi_kernel" $f) > $f.tmp && mv $f.tmp $f; done
 du -sh $OUT; echo profile done

@@ -5,8 +5,8 @@
 cd $GRAFT_REPO_ROOT
 export HIVE_DIST_BACKEND=gloo
 for mode in "--merge sum" "--scaling strong --merge sum" "--merge exact"; do
-  echo "== python bench.py --gpus 2 --steps 2 --warmup 1 --batch 10 --frames 24 --voxel 0.04 --no-cpu-baseline $mode   (no launcher: bench.py starts its own ranks)"
-  timeout -k 10 280 python bench.py --gpus 2 --steps 2 --warmup 1 --batch 10 --frames 24 --voxel 0.04 --no-cpu-baseline $mode 2>&1 | grep '^{"metric"' | tee /tmp/rehearse_line.json
+  echo "== python bench.py --gpus 2 --steps 2 --warmup 1 --batch 10 --frames 24 --voxel 0.04 --full --no-cpu-baseline $mode   (no launcher: bench.py starts its own ranks)"
+  timeout -k 10 280 python bench.py --gpus 2 --steps 2 --warmup 1 --batch 10 --frames 24 --voxel 0.04 --full --no-cpu-baseline $mode 2>&1 | grep '^{"metric"' | tee /tmp/rehearse_line.json
   python3 - >&2 <<'PY'
 import json
 try:
