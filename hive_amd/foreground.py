@@ -8,6 +8,7 @@ face filter, the quadric decimation (opt-in), the connected-component clean-up t
   ``get_mesh_texture_and_uv``    ``Pipeline._get_mesh_texture_and_uv(...)`` (:782-808)
   ``cleanup_with_connected_components``  ``Pipeline._cleanup_with_connected_components(...)`` (:741-779)
   ``decimate_mesh``              ``Pipeline._decimate_mesh(...)`` (:697-738), quadric edge collapse on the GPU
+  ``billboard``                  the ``--billboard`` block of ``process_frame`` (:439-447): an object flattened to its median depth
 
 The triangulation is the implicit one of the pixel grid (csrc/fgmesh.hip): unit squares and triangles of the valid pixels plus the
 (sqrt 2, sqrt 2, 2) triangles with which a lattice Delaunay bridges one-pixel holes -- after the reference's filter (sides <= 2 pixels by
@@ -91,8 +92,9 @@ def filter_faces(points2d, depth, faces, options: MeshFilteringOptions, ctx=None
     return out[:n.value].astype(np.asarray(faces).dtype, copy=False)
 
 
-def get_mesh_texture_and_uv(vertices, image, camera_matrix, rotation=np.eye(3), translation=np.zeros((3, 1)), scale_factor=1.0, ctx=None):
-    """``Pipeline._get_mesh_texture_and_uv``: (cropped texture, UV coordinates relative to the crop's corner)."""
+def get_mesh_texture_and_uv(vertices, image, camera_matrix, rotation=np.eye(3), translation=np.zeros((3, 1)), scale_factor=1.0, ctx=None, return_bbox=False):
+    """``Pipeline._get_mesh_texture_and_uv``: (cropped texture, UV coordinates relative to the crop's corner); with ``return_bbox`` also the crop box
+    (min_u, min_v, max_u, max_v) the texture is ``image[min_v:max_v, min_u:max_u]`` of."""
     validate_shape(vertices, 'vertices', expected_shape=(None, 3))
     validate_shape(image, 'image', expected_shape=(None, None, 3))
     validate_camera_parameter_shapes(camera_matrix, rotation, translation)
@@ -106,7 +108,7 @@ def get_mesh_texture_and_uv(vertices, image, camera_matrix, rotation=np.eye(3), 
     ctx.check(ctx.lib.hive_texture_window(ctx.handle, ptr(pts), len(pts), ptr(K), ptr(R), ptr(t), float(scale_factor), MEM_HOST, ptr(uv), ptr(box)))
     min_u, min_v, max_u, max_v = (int(b) for b in box)
     texture = image[min_v:max_v, min_u:max_u, :].copy()
-    return texture, uv
+    return (texture, uv, (min_u, min_v, max_u, max_v)) if return_bbox else (texture, uv)
 
 
 def cleanup_with_connected_components(vertices, faces, is_object=True, min_components=5, ctx=None):
@@ -141,6 +143,39 @@ def cleanup_with_connected_components(vertices, faces, is_object=True, min_compo
     ctx.check(ctx.lib.hive_mesh_cleanup_cc(ctx.handle, ptr(f), nf, nv, int(bool(is_object)), float(min_components), MEM_HOST, ptr(out_f), ptr(out_vi),
                                            ctypes.byref(n_faces), ctypes.byref(n_verts)))
     return np.asarray(vertices)[out_vi[:n_verts.value]], out_f[:n_faces.value].astype(np.asarray(faces).dtype, copy=False)
+
+
+def billboard(vertices, rotation, translation, ctx=None, return_median=False):
+    """The ``--billboard`` block of ``process_frame`` (hive/pipeline.py:439-447) in one library call (``hive_fg_billboard``): the object flattened to
+    the median camera-space depth of its vertices --
+
+        camera_space_points = rotation @ (vertices.T + translation)
+        camera_space_points[2, :] = np.median(camera_space_points[2, :])
+        vertices = (rotation.T @ (camera_space_points - translation)).T
+
+    restated literally, quirk included: the map is ``R (p + t)`` and back ``R^T (c - t)``, not the ``R p + t`` of ``world2image``, so for ``t != 0`` the two are
+    not inverses of each other (an object does not land on the plane z = median of the camera that ``world2image`` describes).  The operation order is the one in
+    include/hive_mi355x.h; the median is numpy's, bit for bit (an exact radix select on the GPU; -0 sorts before +0).  Finite coordinates only.
+
+    ``vertices`` (V, 3): a float64 device tensor is flattened IN PLACE and returned; a numpy array (or a tensor of another dtype) is copied, and the result is of the
+    input's kind.  V = 0 is a no-op.  With ``return_median`` also the median depth (one extra synchronisation)."""
+    import torch
+    validate_shape(vertices, 'vertices', expected_shape=(None, 3))
+    validate_camera_parameter_shapes(np.eye(3), rotation, translation)
+    R = np.ascontiguousarray(rotation, dtype=np.float64).reshape(3, 3)
+    t = np.ascontiguousarray(translation, dtype=np.float64).reshape(3)
+    if _is_torch(vertices):
+        dev = vertices.device
+        v = vertices if vertices.dtype == torch.float64 and vertices.is_contiguous() else vertices.to(torch.float64).contiguous()
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        v = torch.from_numpy(np.array(vertices, dtype=np.float64, order="C")).to(dev)
+    ctx = ctx or _lib.default_context(dev.index or 0)
+    ctx.follow_torch_stream()
+    median = ctypes.c_double(0.0)
+    ctx.check(ctx.lib.hive_fg_billboard(ctx.handle, ptr(v), int(v.shape[0]), ptr(R), ptr(t), ctypes.byref(median) if return_median else None))
+    out = v if _is_torch(vertices) else v.cpu().numpy()
+    return (out, median.value) if return_median else out
 
 
 def _decimation_budget(is_object, options):
@@ -205,9 +240,10 @@ class FrameMeshBuffers:
 
 
 def frame_mesh(depth, mask, image, camera_matrix, rotation=np.eye(3), translation=np.zeros((3, 1)), options: MeshFilteringOptions = None, ctx=None,
-               buffers: FrameMeshBuffers = None, enable_cc_analysis=False, is_object=True, min_components=5, decimation_options: MeshDecimationOptions = None):
+               buffers: FrameMeshBuffers = None, enable_cc_analysis=False, is_object=True, min_components=5, decimation_options: MeshDecimationOptions = None,
+               billboard=False):
     """One object of one frame, device-resident, in ONE library call (``hive_fg_frame_mesh``): what the loop body of ``process_frame``
-    (/root/reference/hive/pipeline.py:383-461) computes between the binary mask and the texture atlas, minus its CPU-library stages (decimation, billboard) --
+    (/root/reference/hive/pipeline.py:383-461) computes between the binary mask and the texture atlas --
 
         vertices = point_cloud_from_depth(depth, mask, K, R, t)             (:386)
         faces    = _filter_faces(points2d, depth[valid], _triangulate_faces(points2d), options)   (:402-408)
@@ -222,6 +258,10 @@ def frame_mesh(depth, mask, image, camera_matrix, rotation=np.eye(3), translatio
     ``decimate_mesh(vertices, faces, is_object, decimation_options)`` before the clean-up (when enabled) and the texture window, the reference's order
     (:402-453); the dict also carries ``before`` and ``decimated`` = (vertices, faces) after the decimation, and ``decimation_stats``.  When the reference's
     -1 rule skips the decimation the result is the one without ``decimation_options`` (plus those keys).
+
+    With ``billboard`` (off by default) the vertices are then flattened to their median depth (``billboard()``, :439-447: after the clean-up, and after the decimation
+    when that is on) and ``uv``, ``bbox`` and ``texture`` are taken again from the flattened vertices (``hive_texture_window``, :449-453); the faces stay.  Flattened
+    vertices may project outside the frame (the reference's TODO at this spot): the crop is clamped to the image as below.
 
     ``depth`` float32 (H, W), ``mask`` bool / uint8 (H, W) or None, ``image`` uint8 (H, W, 3): device tensors (numpy arrays are uploaded).  Returns a dict of
     device tensors -- ``vertices`` float64 (V, 3), ``faces`` int32 (F, 3), ``uv`` int32 (V, 2), ``texture`` uint8 crop -- and ``bbox`` (min_u, min_v, max_u, max_v);
@@ -270,6 +310,9 @@ def frame_mesh(depth, mask, image, camera_matrix, rotation=np.eye(3), translatio
         ctx.check(ctx.lib.hive_fg_frame_mesh(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
                                              float(options.max_depth_distance), ptr(buffers.vertices), buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0],
                                              ptr(buffers.uv), ctypes.byref(nv), ctypes.byref(nf), ptr(box)))
+    if billboard and nv.value:
+        ctx.check(ctx.lib.hive_fg_billboard(ctx.handle, ptr(buffers.vertices), nv.value, ptr(R), ptr(t), None))
+        ctx.check(ctx.lib.hive_texture_window(ctx.handle, ptr(buffers.vertices), nv.value, ptr(K), ptr(R), ptr(t), 1.0, MEM_DEVICE, ptr(buffers.uv), ptr(box)))
     min_u, min_v, max_u, max_v = (int(b) for b in box)
     texture = None
     if nv.value and img is not None:
@@ -315,7 +358,7 @@ def pack_textures_row(textures, uvs):
 
 def process_frame(rgb, depth, mask_encoded, camera_matrix, pose, dilation_options=None, filtering_options: MeshFilteringOptions = None,
                   disable_coverage_constraint=False, ctx=None, buffers: FrameMeshBuffers = None, enable_cc_analysis=False,
-                  decimation_options: MeshDecimationOptions = None):
+                  decimation_options: MeshDecimationOptions = None, billboard=False):
     """The body of ``process_frame`` in ``Pipeline._create_scene`` (/root/reference/hive/pipeline.py:340-483) for the dynamic objects of ONE frame, device-resident:
     for every object id 1 .. mask_encoded.max(): the binary mask, dilated (``dilate_mask``, :369-370); skipped when it covers less than 1 % of the frame (:374-379); its
     mesh in one library call (``frame_mesh``: point cloud, triangulation + face filter, texture window); skipped with fewer than 9 vertices or no face (:388-391, 410-413);
@@ -324,7 +367,8 @@ def process_frame(rgb, depth, mask_encoded, camera_matrix, pose, dilation_option
     ``filtering_options.min_num_components`` between the face filter and the texture window; an object whose faces all go is still stacked (its vertices and texture,
     no face), as in the reference.  With ``decimation_options`` (None by default: no decimation) every object is decimated after the face filter and before
     the clean-up (:415-429, ``decimate_mesh`` with is_object=True) and the result also carries ``decimation`` = {object id: (vertices, faces) before,
-    (vertices, faces) after}, the reference's ``mesh_decimation`` profiling counts.  Billboard is outside this build's scope and is NOT applied.
+    (vertices, faces) after}, the reference's ``mesh_decimation`` profiling counts.  With ``billboard`` (the reference's ``--billboard``; off by default) every
+    object is flattened to its median depth after those stages and textured from the flattened vertices (:439-453, ``frame_mesh(billboard=True)``).
 
     ``rgb`` uint8 (H, W, 3+), ``depth`` float32 (H, W), ``mask_encoded`` uint8 (H, W) instance ids (0 = background), ``pose`` the frame's 4 x 4 world-to-camera transform
     (``dataset.camera_trajectory.to_homogenous_transforms()[index]``).  Numpy arrays or device tensors.  Returns None for a frame without a surviving object (the reference
@@ -360,7 +404,7 @@ def process_frame(rgb, depth, mask_encoded, camera_matrix, pose, dilation_option
             continue
         mesh = frame_mesh(depth_d, mask, rgb_d, camera_matrix, rotation, translation, filtering_options, ctx=ctx, buffers=buffers,
                           enable_cc_analysis=enable_cc_analysis, is_object=True, min_components=filtering_options.min_num_components,
-                          decimation_options=decimation_options)
+                          decimation_options=decimation_options, billboard=billboard)
         n_points, n_filtered = mesh.get("before", (mesh["vertices"].shape[0], mesh["faces"].shape[0]))
         if n_points < 9 or n_filtered < 1:
             continue

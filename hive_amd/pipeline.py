@@ -1,6 +1,6 @@
 """HIVE's pipeline for the part the dense-compute path serves: dataset -> key frames -> TSDF fusion -> background mesh
 (/root/reference/hive/pipeline.py:258-286, 871-901), then the per-frame foreground meshes (``_create_scene``, :309-497) with the
-connected-component clean-up and decimation disabled.
+connected-component clean-up and, on request, decimation, billboards and trajectory smoothing.
 
 glTF export, draco compression, scene centring and the WebXR viewer of the reference's ``Pipeline`` are outside the scope of this
 build; meshes are written as PLY.
@@ -61,8 +61,8 @@ def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None, *,
 class Pipeline:
     """The reference's ``Pipeline`` (/root/reference/hive/pipeline.py:59-262) for the part this build serves: dataset -> key frames
     -> TSDF fusion -> background mesh -> per-frame foreground meshes.  Constructor, ``from_command_line`` and ``run`` take the reference's
-    arguments; the stages behind the other option groups (decimation, billboard, trajectory smoothing, glTF / draco export, WebXR) are
-    outside this build's scope and ``run`` says so where the reference would run them."""
+    arguments; the foreground path does what the reference's does short of export: the stages behind the remaining option groups (glTF / draco export, WebXR)
+    are outside this build's scope."""
     mesh_folder = "mesh"
     bundle_fusion_folder = "bundle_fusion"
 
@@ -87,10 +87,11 @@ class Pipeline:
 
     @staticmethod
     def from_command_line(argv=None) -> 'Pipeline':
-        """pipeline.py:100-141: every option group registers its flags on one parser; ``argv=None`` reads ``sys.argv``."""
+        """pipeline.py:100-141: every option group registers its flags on one parser; ``argv=None`` reads ``sys.argv``.  (The reference leaves the trajectory
+        smoothing group out of its parser, so its ``--fts_*`` flags can only be set from code; here they are registered like the others.)"""
         parser = argparse.ArgumentParser("HIVE", description="Create 3D mesh videos from a RGB-D sequence with camera trajectory annotations.")
         groups = (PipelineOptions, StorageOptions, MaskDilationOptions, MeshFilteringOptions, MeshDecimationOptions, COLMAPOptions, BackgroundMeshOptions,
-                  WebXROptions)
+                  WebXROptions, ForegroundTrajectorySmoothingOptions)
         for group in groups:
             group.add_args(parser)
         args = parser.parse_args(argv)
@@ -98,7 +99,8 @@ class Pipeline:
         return Pipeline(options=PipelineOptions.from_args(args), storage_options=StorageOptions.from_args(args),
                         decimation_options=MeshDecimationOptions.from_args(args), dilation_options=MaskDilationOptions.from_args(args),
                         filtering_options=MeshFilteringOptions.from_args(args), colmap_options=COLMAPOptions.from_args(args),
-                        static_mesh_options=BackgroundMeshOptions.from_args(args), webxr_options=WebXROptions.from_args(args))
+                        static_mesh_options=BackgroundMeshOptions.from_args(args), webxr_options=WebXROptions.from_args(args),
+                        fts_options=ForegroundTrajectorySmoothingOptions.from_args(args))
 
     @property
     def num_frames(self) -> int:
@@ -131,24 +133,27 @@ class Pipeline:
         return fusion.tsdf_fusion(dataset, options, num_frames=num_frames, frame_set=frame_set)
 
     def create_foreground_meshes(self, dataset: HiveDataset, num_frames: int, folder: str):
-        """``_create_scene`` (pipeline.py:309-497) for the dynamic objects of frames 0 .. num_frames - 1: every frame through ``foreground.process_frame``
-        with the connected-component clean-up on; a frame with a surviving object gives ``<folder>/%06d.ply`` (vertices in the frame of bg.ply, atlas uv)
-        and ``<folder>/%06d.png`` (its texture atlas).  With ``decimation_options.enabled`` (``--enable_decimation``; off by default) every object is
-        decimated before the clean-up and ``mesh_decimation`` profiling counts are recorded; billboard and trajectory smoothing are not applied."""
+        """``_create_foreground_scene`` / ``_create_scene`` (pipeline.py:288-497) for the dynamic objects of frames 0 .. num_frames - 1: every frame through
+        ``foreground.process_frame`` with the connected-component clean-up on; a frame with a surviving object gives ``<folder>/%06d.ply`` (vertices in the frame of
+        bg.ply, atlas uv) and ``<folder>/%06d.png`` (its texture atlas).  With ``decimation_options.enabled`` (``--enable_decimation``; off by default) every object is
+        decimated before the clean-up and ``mesh_decimation`` profiling counts are recorded; with ``options.billboard`` (``--billboard``) every object is flattened to
+        its median depth before texturing; with ``fts_options.num_epochs > 0`` (``--fts_num_epochs``) the meshes are built with the poses ``ForegroundPoseOptimiser``
+        returns (:297-303) -- the dataset's stored trajectory, and with it bg.ply, stay as they are (the reference's ``temporary_trajectory``)."""
         from PIL import Image
         not_applied = []
         decimation = self.decimation_options if self.decimation_options.enabled else None
         if self.decimation_options.num_faces_object > 0 and decimation is None:
             not_applied.append("decimation")
-        if self.options.billboard:
-            not_applied.append("billboard")
-        if self.fts_options.num_epochs > 0:
-            not_applied.append("trajectory_smoothing")
         self.profiling.setdefault("foreground_reconstruction", {})["not_applied"] = not_applied
         if not_applied:
-            logging.info(f"Foreground meshes: {', '.join(not_applied)} outside this build's scope, not applied.")
+            logging.info(f"Foreground meshes: {', '.join(not_applied)} requested without --enable_decimation, not applied.")
         os.makedirs(folder, exist_ok=True)
-        poses = dataset.camera_trajectory.to_homogenous_transforms()
+        trajectory = dataset.camera_trajectory
+        if self.fts_options.num_epochs > 0:
+            from hive_amd.pose_optimisation import ForegroundPoseOptimiser
+            with timed_block("Smoothed the foreground trajectory in", self.profiling, ("timing", "foreground_reconstruction", "trajectory_smoothing")):
+                trajectory = ForegroundPoseOptimiser(dataset, learning_rate=self.fts_options.learning_rate, num_epochs=self.fts_options.num_epochs).run()
+        poses = trajectory.to_homogenous_transforms()
         buffers = None
         for i in range(num_frames):
             depth = dataset.depth_dataset[i]
@@ -156,7 +161,7 @@ class Pipeline:
                 buffers = foreground.FrameMeshBuffers(*depth.shape[:2])
             mesh = foreground.process_frame(dataset.rgb_dataset[i], depth, dataset.mask_dataset[i], dataset.camera_matrix, poses[i], self.dilation_options,
                                             self.filtering_options, disable_coverage_constraint=self.options.disable_coverage_constraint, buffers=buffers,
-                                            enable_cc_analysis=True, decimation_options=decimation)
+                                            enable_cc_analysis=True, decimation_options=decimation, billboard=bool(self.options.billboard))
             if mesh is None:
                 continue
             for object_id, ((v0, f0), (v1, f1)) in mesh.get("decimation", {}).items():  # pipeline.py:418-427

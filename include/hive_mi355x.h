@@ -325,6 +325,32 @@ int hive_filter_faces(hive_ctx *ctx, const int32_t *points2d, const float *depth
  * max_u + 1, max_v + 1} -- the crop `image[min_v:max_v, min_u:max_u]` that becomes the texture; out_uv i32 [n][2] = uv - (min_u, min_v). */
 int hive_texture_window(hive_ctx *ctx, const double *points, int64_t n, const double K[9], const double R[9], const double t[3],
                         double scale_factor, int mem, int32_t *out_uv, int32_t bbox[4]);
+/* Billboard (hive/pipeline.py:439-447): `c = rotation @ (vertices.T + translation); c[2, :] = np.median(c[2, :]); vertices = (rotation.T @ (c - translation)).T`
+ * in place on d_vertices f64 [n][3] (device).  The map is the reference's R (p + t) and back R^T (c - t), NOT hive_project's R p + t: for t != 0 the two are not
+ * inverses of each other, and this is restated as it stands.  Operation order (no fused multiply-add): c_r = (R[r][0] (x + t0) + R[r][1] (y + t1)) + R[r][2] (z + t2);
+ * out_j = (R[0][j] (c_0 - t0) + R[1][j] (c_1 - t1)) + R[2][j] (m - t2).  m is numpy's median EXACTLY (middle order statistic for odd n, (a + b) / 2 of the two
+ * middle ones for even n): a radix select over the order-preserving 64-bit image of the doubles, 8 bits a pass, integer histograms across workgroups -- the same
+ * bits whatever the launch shape; -0 sorts before +0; finite values only.  *median_out (optional, host) = m, at the price of one synchronisation; n = 0: no-op.
+ * Follow with hive_texture_window on the flattened vertices (:449-453). */
+int hive_fg_billboard(hive_ctx *ctx, double *d_vertices, int64_t n, const double R[9], const double t[3], double *median_out);
+/* Centroids of the dynamic objects for ForegroundPoseOptimiser (hive/pose_optimisation.py:1626-1634, 1654-1657): out_centroids[i] = mean, in camera space, of
+ * point_cloud_from_depth(depth_i, mask_i > 0, K) and out_counts[i] = its length, for n_frames <= 65535 device-resident frames d_depth f32 [n][H][W], d_mask u8
+ * [n][H][W] (instance ids, non-zero = object); no point cloud is materialised.  Per point hive_unproject's arithmetic with R = I, t = 0; float64 sums in a fixed tree
+ * that depends on H W alone (tiles of 4096 pixels: 16 per thread in order, lane butterfly, waves in order; then the tiles likewise), so the result is bit-identical
+ * from run to run.  out_centroids f64 [n][3] and out_counts i64 [n] are host arrays; a frame without a valid object pixel has count 0 and centroid 0. */
+int hive_fg_centroids(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_frames, int H, int W, const double Kinv[9], double *out_centroids,
+                      int64_t *out_counts);
+/* The Adam loop of ForegroundPoseOptimiser.run (hive/pose_optimisation.py:1669-1709), all num_epochs epochs in ONE launch of one workgroup.  params f64 [n][7] =
+ * (scalar-last quaternion, translation) in / out (host): the raw parameters, not normalised.  gt_params (NULL = params): the parameters the fixed world-space
+ * centroids gt = conj(q / |q|) (c - t) are taken at -- the reference takes them at the initial parameters.  centroids f64 [n][3] (hive_fg_centroids); chunks: n_chunks
+ * runs [chunk_start[c], chunk_start[c] + chunk_len[c]) of at least 3 frames, ascending and disjoint.  Per epoch and chunk, with w = conj(q / |q|) (c - t):
+ * 0.01 mean_i |gt_i - w_i| + 0.1 |t[:-2] - 2 t[1:-1] + t[2:]|_F + 0.1 |t[:-1] - t[1:]|_F, summed over the chunks; hand-derived gradients (0 where a norm is 0, as
+ * torch.norm's); torch.optim.Adam(lr = learning_rate, weight_decay = 1e-4) semantics on every parameter, frames of no chunk included.  losses f64 [num_epochs + 1]:
+ * the loss before every epoch's step and, last, at the returned parameters.  gradient (optional) f64 [n][7]: dL/dparams at the returned parameters, without the
+ * weight decay (with num_epochs = 0: loss and gradient at `params`).  Float64 throughout -- the reference keeps the parameters in float32 --, fixed summation
+ * order: bit-identical from run to run. */
+int hive_fts_optimise(hive_ctx *ctx, double *params, const double *gt_params, const double *centroids, int n_frames, const int32_t *chunk_start,
+                      const int32_t *chunk_len, int n_chunks, double learning_rate, int num_epochs, double *losses, double *gradient);
 
 /* ---- dilate_mask(mask, MaskDilationOptions(num_iterations)) -- hive/image_processing.py:30-45 */
 /* 3x3 rectangular structuring element applied `iterations` times == one (2*it+1)^2 box max
