@@ -15,13 +15,10 @@
 //             cheapest prefix by key that reaches F <= budget (a bit-by-bit search of the threshold key over the selected set)
 //   apply     faces: v0 -> v1, degenerate faces die; vertices: Q(v1) += Q(v0), v0 removed, lists reset; build: the new lists
 // Integer atomics only (list heads, appends and counts whose final values do not depend on order): results are identical from run to run.
-#include "hive_internal.hpp"
-
-#include <algorithm>
+#include "mesh_compact.hpp"
 
 namespace {
 
-constexpr int TILE = 1024;
 constexpr int DEC_MAX_ROUNDS = 4096;
 constexpr int DEC_BATCH = 16;  // rounds issued between two polls of the device state
 constexpr unsigned long long KEY_NONE = ~0ull;
@@ -57,10 +54,14 @@ struct DecParams {
     int *list;                 // [V] selected vertices
     int *vmap;                 // [V]
     unsigned *sc;
+    // the output compaction (mesh_compact.hpp): the vertices not removed, isolated ones included, and the faces alive
+    __device__ long long nv() const { return min((long long)counts[0], vert_cap); }
+    __device__ long long nf() const { return min((long long)counts[1], face_cap); }
+    __device__ bool keep_vertex(long long i) const { return !(flags[i] & F_REMOVED); }
+    __device__ bool keep_face(long long f) const { return fw[3 * f] >= 0; }
+    __device__ int face_vertex(long long f, int k) const { return vmap[fw[3 * f + k]]; }
 };
 
-__device__ __forceinline__ long long dec_nv(const DecParams &p) { return min((long long)p.counts[0], p.vert_cap); }
-__device__ __forceinline__ long long dec_nf(const DecParams &p) { return min((long long)p.counts[1], p.face_cap); }
 // the round kernels run while nothing has stopped the decimation and the face count is above the budget
 __device__ __forceinline__ bool dec_active(const DecParams &p) {
     const volatile unsigned *sc = p.sc;
@@ -212,7 +213,7 @@ __device__ bool collapse_ok(const DecParams &p, int v1, const Ring &r0, const Ri
 }
 
 __global__ __launch_bounds__(256) void dec_init_kernel(DecParams p) {
-    const long long nv = dec_nv(p), nf = dec_nf(p);
+    const long long nv = p.nv(), nf = p.nf();
     // the scalar block is cleared on the stream before this launch: the error word below is only ever OR-ed into, never reset by a thread of this launch
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         p.sc[0] = (unsigned)nf;
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(256) void dec_init_kernel(DecParams p) {
 
 __global__ __launch_bounds__(256) void dec_build_kernel(DecParams p) {
     if (!dec_active(p)) return;
-    const long long nf = dec_nf(p), nv = dec_nv(p);
+    const long long nf = p.nf(), nv = p.nv();
     for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nf; f += (long long)gridDim.x * 256) {
         if (p.fw[3 * f] < 0) continue;
         for (int k = 0; k < 3; ++k) {
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void dec_build_kernel(DecParams p) {
 // the vertex quadrics (faces in ascending index) and the locked vertices, once
 __global__ __launch_bounds__(256) void dec_quadric_kernel(DecParams p) {
     if (!dec_active(p)) return;
-    const long long nv = dec_nv(p);
+    const long long nv = p.nv();
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
         const int v = (int)i;
         double q[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(256) void dec_quadric_kernel(DecParams p) {
 
 __global__ __launch_bounds__(256) void dec_key_kernel(DecParams p) {
     if (!dec_active(p)) return;
-    const long long nv = dec_nv(p);
+    const long long nv = p.nv();
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
         const int v0 = (int)i;
         unsigned long long best = KEY_NONE;
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(256) void dec_key_kernel(DecParams p) {
 // fk[f] = smallest src over the corners of live face f
 __global__ __launch_bounds__(256) void dec_fmin_kernel(DecParams p, const unsigned long long *__restrict__ src) {
     if (!dec_active(p)) return;
-    const long long nf = dec_nf(p);
+    const long long nf = p.nf();
     for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nf; f += (long long)gridDim.x * 256) {
         if (p.fw[3 * f] < 0) continue;
         p.fk[f] = min(src[p.fw[3 * f]], min(src[p.fw[3 * f + 1]], src[p.fw[3 * f + 2]]));
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(256) void dec_fmin_kernel(DecParams p, const unsign
 // dst[v] = min(src[v], fk over the faces of v)
 __global__ __launch_bounds__(256) void dec_vmin_kernel(DecParams p, const unsigned long long *__restrict__ src, unsigned long long *__restrict__ dst) {
     if (!dec_active(p)) return;
-    const long long nv = dec_nv(p);
+    const long long nv = p.nv();
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
         unsigned long long m = src[i];
         for (int c = p.head[i]; c >= 0; c = p.next[c]) m = min(m, p.fk[c / 3]);
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256) void dec_vmin_kernel(DecParams p, const unsign
 
 __global__ __launch_bounds__(256) void dec_select_kernel(DecParams p) {
     if (!dec_active(p)) return;
-    const long long nv = dec_nv(p);
+    const long long nv = p.nv();
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
         const unsigned long long k = p.key[i];
         const bool s = k != KEY_NONE && k == p.m2[i] && k == p.m2[p.tgt[i]];
@@ -424,7 +425,7 @@ __device__ __forceinline__ bool applied(const DecParams &p, int v, unsigned long
 __global__ __launch_bounds__(256) void dec_apply_faces_kernel(DecParams p) {
     if (!dec_applying(p)) return;
     const unsigned long long thr = *(const unsigned long long *)(p.sc + 8);
-    const long long nf = dec_nf(p);
+    const long long nf = p.nf();
     unsigned killed = 0;
     for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nf; f += (long long)gridDim.x * 256) {
         if (p.fw[3 * f] < 0) continue;
@@ -452,7 +453,7 @@ __global__ __launch_bounds__(256) void dec_apply_faces_kernel(DecParams p) {
 __global__ __launch_bounds__(256) void dec_apply_vertices_kernel(DecParams p) {
     if (!dec_applying(p)) return;
     const unsigned long long thr = *(const unsigned long long *)(p.sc + 8);
-    const long long nv = dec_nv(p);
+    const long long nv = p.nv();
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
         p.head[i] = -1;
         if (applied(p, (int)i, thr)) {
@@ -464,111 +465,35 @@ __global__ __launch_bounds__(256) void dec_apply_vertices_kernel(DecParams p) {
     }
 }
 
-// per block of TILE: surviving vertices -> bv, live faces -> bf
-__global__ __launch_bounds__(256) void dec_count_kernel(DecParams p, unsigned *__restrict__ bv, unsigned *__restrict__ bf) {
-    __shared__ unsigned lds[8];
-    const long long nf = dec_nf(p), nv = dec_nv(p);
-    unsigned cv = 0, cf = 0;
-    for (int j = 0; j < TILE / 256; ++j) {
-        const long long i = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
-        if (i < nf) cf += p.fw[3 * i] >= 0;
-        if (i < nv) cv += !(p.flags[i] & F_REMOVED);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        cv += (unsigned)__shfl_xor((int)cv, off);
-        cf += (unsigned)__shfl_xor((int)cf, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        lds[threadIdx.x >> 6] = cv;
-        lds[4 + (threadIdx.x >> 6)] = cf;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bv[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
-        bf[blockIdx.x] = lds[4] + lds[5] + lds[6] + lds[7];
-    }
-}
-
-__global__ __launch_bounds__(256) void dec_vmap_kernel(DecParams p, const unsigned *__restrict__ bv, int32_t *__restrict__ out_vertex_index) {
-    __shared__ unsigned lds[4];
-    const long long nv = dec_nv(p);
-    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
-    bool ok[TILE / 256];
-    unsigned c = 0;
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j) {
-        ok[j] = base + j < nv && !(p.flags[base + j] & F_REMOVED);
-        c += ok[j];
-    }
-    long long o = (long long)bv[blockIdx.x] + block_exclusive(c, lds);
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j) {
-        if (base + j >= nv) continue;
-        p.vmap[base + j] = ok[j] ? (int)o : -1;
-        if (ok[j]) {
-            if (out_vertex_index) out_vertex_index[o] = (int32_t)(base + j);
-            ++o;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void dec_faces_kernel(DecParams p, const unsigned *__restrict__ bf, int32_t *__restrict__ out, long long out_cap) {
-    __shared__ unsigned lds[4];
-    const long long nf = dec_nf(p);
-    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
-    bool ok[TILE / 256];
-    unsigned c = 0;
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j) {
-        ok[j] = base + j < nf && p.fw[3 * (base + j)] >= 0;
-        c += ok[j];
-    }
-    long long o = (long long)bf[blockIdx.x] + block_exclusive(c, lds);
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j)
-        if (ok[j]) {
-            if (o < out_cap)
-                for (int k = 0; k < 3; ++k) out[3 * o + k] = p.vmap[p.fw[3 * (base + j) + k]];
-            ++o;
-        }
-}
-
 struct DecLayout {
     size_t bytes;
     int nb;
     unsigned *bv, *bf;
 };
 
-DecLayout dec_layout(char *base, long long vert_cap, long long face_cap, DecParams &p) {
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+DecLayout dec_layout(hive_scratch_layout L, long long vert_cap, long long face_cap, DecParams &p) {
     DecLayout l{};
     l.nb = (int)std::max<long long>(1, (std::max(face_cap, vert_cap) + TILE - 1) / TILE);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *at = base ? base + off : nullptr;
-        off += align(bytes);
-        return at;
-    };
     const size_t V = (size_t)vert_cap, F = (size_t)face_cap;
     p.vert_cap = vert_cap;
     p.face_cap = face_cap;
-    p.vmap = (int *)take(V * 4);  // first: hive_decimate_vmap
-    p.fw = (int32_t *)take(F * 12);
-    p.Q = (double *)take(V * 80);
-    p.head = (int *)take(V * 4);
-    p.next = (int *)take(F * 12);
-    p.flags = (uint8_t *)take(V);
-    p.sel = (uint8_t *)take(V);
-    p.rem = (uint8_t *)take(V);
-    p.tgt = (int *)take(V * 4);
-    p.key = (unsigned long long *)take(V * 8);
-    p.m1 = (unsigned long long *)take(V * 8);
-    p.m2 = (unsigned long long *)take(V * 8);
-    p.fk = (unsigned long long *)take(F * 8);
-    p.list = (int *)take(V * 4);
-    l.bv = (unsigned *)take((size_t)l.nb * 4);
-    l.bf = (unsigned *)take((size_t)l.nb * 4);
-    l.bytes = off;
+    p.vmap = L.take<int>(V);  // first: hive_decimate_vmap
+    p.fw = L.take<int32_t>(3 * F);
+    p.Q = L.take<double>(10 * V);
+    p.head = L.take<int>(V);
+    p.next = L.take<int>(3 * F);
+    p.flags = L.take<uint8_t>(V);
+    p.sel = L.take<uint8_t>(V);
+    p.rem = L.take<uint8_t>(V);
+    p.tgt = L.take<int>(V);
+    p.key = L.take<unsigned long long>(V);
+    p.m1 = L.take<unsigned long long>(V);
+    p.m2 = L.take<unsigned long long>(V);
+    p.fk = L.take<unsigned long long>(F);
+    p.list = L.take<int>(V);
+    l.bv = L.take<unsigned>((size_t)l.nb);
+    l.bf = L.take<unsigned>((size_t)l.nb);
+    l.bytes = L.bytes();
     return l;
 }
 
@@ -583,14 +508,14 @@ int dec_error(hive_ctx *ctx, unsigned err) {
 
 size_t hive_decimate_scratch_bytes(long long vert_cap, long long face_cap) {
     DecParams p{};
-    return dec_layout(nullptr, std::max<long long>(vert_cap, 1), std::max<long long>(face_cap, 1), p).bytes;
+    return dec_layout({}, std::max<long long>(vert_cap, 1), std::max<long long>(face_cap, 1), p).bytes;
 }
 
 int32_t *hive_decimate_vmap(void *scratch, long long, long long) { return (int32_t *)scratch; }
 
 int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int64_t stats[3]) {
     DecParams p{};
-    const DecLayout l = dec_layout((char *)scratch, std::max<long long>(job.vert_cap, 1), std::max<long long>(job.face_cap, 1), p);
+    const DecLayout l = dec_layout({(char *)scratch}, std::max<long long>(job.vert_cap, 1), std::max<long long>(job.face_cap, 1), p);
     p.counts = job.counts;
     p.pos = job.pos;
     p.faces_in = job.faces;
@@ -635,10 +560,7 @@ int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int
     }
     int rc = dec_error(ctx, err);
     if (rc) return rc;
-    hipLaunchKernelGGL(dec_count_kernel, dim3(l.nb), blk, 0, s, p, l.bv, l.bf);
-    hive_launch_scan_blocks2(ctx, l.bv, l.bf, l.nb, job.out_counts, (int *)(p.sc + 12));
-    hipLaunchKernelGGL(dec_vmap_kernel, dim3(l.nb), blk, 0, s, p, (const unsigned *)l.bv, job.out_vertex_index);
-    hipLaunchKernelGGL(dec_faces_kernel, dim3(l.nb), blk, 0, s, p, (const unsigned *)l.bf, job.out_faces, job.out_face_cap);
+    launch_compaction(ctx, p, l.bv, l.bf, l.nb, job.out_counts, (int *)(p.sc + 12), job.out_faces, job.out_face_cap, job.out_vertex_index);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
 }
@@ -662,27 +584,37 @@ int hive_mesh_decimate(hive_ctx *ctx, const double *vertices, int64_t n_vertices
         HIVE_REQUIRE(ctx, n_faces == 0, "mesh_decimate: a face references a vertex id outside [0, n_vertices)");
         return HIVE_OK;
     }
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const long long fcap = std::max<long long>(n_faces, 1);
     // device scratch: [vertices | faces | out faces | out vertex ids] (host memory) | the decimation's state
-    const size_t off_faces = align((size_t)n_vertices * 24), off_out_faces = off_faces + align((size_t)fcap * 12);
-    const size_t off_out_vi = off_out_faces + align((size_t)fcap * 12);
-    const size_t off_dec = mem == HIVE_MEM_HOST ? off_out_vi + align((size_t)n_vertices * 4) : 0;
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_dec + hive_decimate_scratch_bytes(n_vertices, fcap));
+    double *s_pos = nullptr;
+    int32_t *s_faces = nullptr, *s_out_faces = nullptr, *s_out_vi = nullptr;
+    char *s_dec;
+    auto lay = [&](char *base) {
+        hive_scratch_layout L{base};
+        if (mem == HIVE_MEM_HOST) {
+            s_pos = L.take<double>(3 * (size_t)n_vertices);
+            s_faces = L.take<int32_t>(3 * (size_t)fcap);
+            s_out_faces = L.take<int32_t>(3 * (size_t)fcap);
+            s_out_vi = L.take<int32_t>((size_t)n_vertices);
+        }
+        s_dec = L.take<char>(hive_decimate_scratch_bytes(n_vertices, fcap));
+        return L.bytes();
+    };
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, lay(nullptr));
     if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
+    lay((char *)ctx->d_scratch);
     hive_dec_job job;
     job.pos = vertices;
     job.faces = faces;
     job.out_faces = out_faces;
     job.out_vertex_index = out_vertex_index;
     if (mem == HIVE_MEM_HOST) {
-        if ((rc = hive_upload(ctx, base, vertices, (size_t)n_vertices * 24))) return rc;
-        if (n_faces && (rc = hive_upload(ctx, base + off_faces, faces, (size_t)n_faces * 12))) return rc;
-        job.pos = (const double *)base;
-        job.faces = (const int32_t *)(base + off_faces);
-        job.out_faces = (int32_t *)(base + off_out_faces);
-        job.out_vertex_index = (int32_t *)(base + off_out_vi);
+        if ((rc = hive_upload(ctx, s_pos, vertices, (size_t)n_vertices * 24))) return rc;
+        if (n_faces && (rc = hive_upload(ctx, s_faces, faces, (size_t)n_faces * 12))) return rc;
+        job.pos = s_pos;
+        job.faces = s_faces;
+        job.out_faces = s_out_faces;
+        job.out_vertex_index = s_out_vi;
     }
     unsigned *sc = ctx->d_scalars + DEC_SCALARS + 16;  // [16] = V, [17] = F in, [18] / [19] = vertices / faces out
     const unsigned counts[2] = {(unsigned)n_vertices, (unsigned)n_faces};
@@ -694,7 +626,7 @@ int hive_mesh_decimate(hive_ctx *ctx, const double *vertices, int64_t n_vertices
     job.max_error = max_error;
     job.out_face_cap = fcap;
     job.out_counts = sc + 2;
-    if ((rc = hive_decimate_run(ctx, job, base + off_dec, stats))) return rc;
+    if ((rc = hive_decimate_run(ctx, job, s_dec, stats))) return rc;
     unsigned out[2];
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(out, sc + 2, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
     HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -20,13 +20,11 @@
 //
 // All integer work (vertex ids, face lists, the crop window) is exact; the filter compares in the reference's types
 // (float32 depth differences, float64 pixel distances).
-#include "hive_internal.hpp"
-
-#include <algorithm>
+#include "mesh_compact.hpp"
 
 namespace {
 
-constexpr int TILE = 1024;  // pixels (and 2 x 2 blocks, by their top-left pixel) per workgroup
+// a workgroup takes TILE (mesh_compact.hpp) pixels, and the 2 x 2 blocks by their top-left pixel
 
 __device__ __forceinline__ bool px_valid(const float *depth, const uint8_t *mask, int i) { return (!mask || mask[i]) && depth[i] > 0.0f; }
 
@@ -113,18 +111,10 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const float *__restrict
             cf += (unsigned)pixel_faces(p, depth, mask, i, tri);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        cv += (unsigned)__shfl_xor((int)cv, off);
-        cf += (unsigned)__shfl_xor((int)cf, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        lds[threadIdx.x >> 6] = cv;
-        lds[4 + (threadIdx.x >> 6)] = cf;
-    }
-    __syncthreads();
+    block_sum2(cv, cf, lds);
     if (threadIdx.x == 0) {
-        blk_valid[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
-        blk_faces[blockIdx.x] = lds[4] + lds[5] + lds[6] + lds[7];
+        blk_valid[blockIdx.x] = cv;
+        blk_faces[blockIdx.x] = cf;
     }
 }
 
@@ -152,41 +142,6 @@ __global__ __launch_bounds__(1024) void scan_blocks_kernel(unsigned *__restrict_
     for (int i = lo; i < hi; ++i) {
         const unsigned v = a[i];
         a[i] = r;
-        r += v;
-    }
-}
-
-
-// hive_fg_frame_mesh: both block-count arrays scanned by ONE workgroup (threads 0..511: valid pixels, 512..1023: faces), totals[0..1] = sums, and the texture
-// window's bounding box initialised for the atomics of window_project_kernel (no host-to-device copy in the call)
-__global__ __launch_bounds__(1024) void scan_blocks2_kernel(unsigned *__restrict__ a, unsigned *__restrict__ b, int nb, unsigned *totals, int *bbox) {
-    __shared__ unsigned part[1024];
-    const int half = threadIdx.x >> 9, t = threadIdx.x & 511;
-    unsigned *arr = half ? b : a;
-    const int per = (nb + 511) / 512;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    unsigned s = 0;
-    for (int i = lo; i < hi; ++i) s += arr[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (t == 0) {
-        unsigned r = 0;
-        for (int i = 0; i < 512; ++i) {
-            const unsigned v = part[half * 512 + i];
-            part[half * 512 + i] = r;
-            r += v;
-        }
-        totals[half] = r;
-    }
-    if (threadIdx.x == 1) {
-        bbox[0] = bbox[1] = 0x7fffffff;
-        bbox[2] = bbox[3] = (int)0x80000000;
-    }
-    __syncthreads();
-    unsigned r = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) {
-        const unsigned v = arr[i];
-        arr[i] = r;
         r += v;
     }
 }
@@ -313,9 +268,11 @@ struct WindowParams {
 };
 
 // uv = world2image(points) in its default int32 form (np.round, half to even -- geometric.py:175-178); bbox = {min, max} per axis
-// (int atomics); out[0..3] = INT_MAX, INT_MAX, INT_MIN, INT_MIN
-__global__ __launch_bounds__(256) void window_project_kernel(const double *__restrict__ pts, long long n, WindowParams p, int32_t *__restrict__ uv,
-                                                             int *__restrict__ out) {
+// (int atomics) over an initial INT_MAX, INT_MAX, INT_MIN, INT_MIN.  The point count is the host's (n_ptr null, n_or_capacity = n) or lives in device
+// memory (the frame path: the vertex count is known to the device only), bounded by n_or_capacity.
+__global__ __launch_bounds__(256) void window_project_kernel(const double *__restrict__ pts, const unsigned *__restrict__ n_ptr, long long n_or_capacity, WindowParams p,
+                                                             int32_t *__restrict__ uv, int *__restrict__ out) {
+    const long long n = n_ptr ? min((long long)*n_ptr, n_or_capacity) : n_or_capacity;
     int mn_u = 0x7fffffff, mn_v = 0x7fffffff, mx_u = (int)0x80000000, mx_v = (int)0x80000000;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
@@ -337,7 +294,7 @@ __global__ __launch_bounds__(256) void window_project_kernel(const double *__res
         mn_v = min(mn_v, __shfl_xor(mn_v, off));
         mx_v = max(mx_v, __shfl_xor(mx_v, off));
     }
-    if ((threadIdx.x & 63) == 0) {
+    if ((threadIdx.x & 63) == 0 && mn_u != 0x7fffffff) {  // (a wave without points: its atomics would change nothing)
         atomicMin(out + 0, mn_u);
         atomicMin(out + 1, mn_v);
         atomicMax(out + 2, mx_u);
@@ -345,48 +302,8 @@ __global__ __launch_bounds__(256) void window_project_kernel(const double *__res
     }
 }
 
-__global__ __launch_bounds__(256) void window_shift_kernel(int32_t *__restrict__ uv, long long n, const int *__restrict__ bbox) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    uv[2 * i + 0] -= bbox[0];
-    uv[2 * i + 1] -= bbox[1];
-}
-
-// the same two steps with the point count in device memory (hive_fg_frame_mesh: the vertex count is known to the device only)
-__global__ __launch_bounds__(256) void window_project_dev_kernel(const double *__restrict__ pts, const unsigned *__restrict__ n_ptr, long long capacity, WindowParams p,
-                                                                 int32_t *__restrict__ uv, int *__restrict__ out) {
-    const long long n = min((long long)*n_ptr, capacity);
-    int mn_u = 0x7fffffff, mn_v = 0x7fffffff, mx_u = (int)0x80000000, mx_v = (int)0x80000000;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-        double cam[3], c[3];
-        for (int r = 0; r < 3; ++r) cam[r] = p.R[3 * r + 0] * X[0] + p.R[3 * r + 1] * X[1] + p.R[3 * r + 2] * X[2] + p.t[r];
-        for (int r = 0; r < 3; ++r) c[r] = p.K[3 * r + 0] * cam[0] + p.K[3 * r + 1] * cam[1] + p.K[3 * r + 2] * cam[2];
-        const double u = c[0] / c[2] / p.scale, v = c[1] / c[2] / p.scale;
-        const int ru = (int)rint(u), rv = (int)rint(v);  // np.round: half to even
-        uv[2 * i + 0] = ru;
-        uv[2 * i + 1] = rv;
-        mn_u = min(mn_u, ru);
-        mx_u = max(mx_u, ru);
-        mn_v = min(mn_v, rv);
-        mx_v = max(mx_v, rv);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        mn_u = min(mn_u, __shfl_xor(mn_u, off));
-        mx_u = max(mx_u, __shfl_xor(mx_u, off));
-        mn_v = min(mn_v, __shfl_xor(mn_v, off));
-        mx_v = max(mx_v, __shfl_xor(mx_v, off));
-    }
-    if ((threadIdx.x & 63) == 0 && mn_u != 0x7fffffff) {
-        atomicMin(out + 0, mn_u);
-        atomicMin(out + 1, mn_v);
-        atomicMax(out + 2, mx_u);
-        atomicMax(out + 3, mx_v);
-    }
-}
-
-__global__ __launch_bounds__(256) void window_shift_dev_kernel(int32_t *__restrict__ uv, const unsigned *__restrict__ n_ptr, long long capacity, const int *__restrict__ bbox) {
-    const long long n = min((long long)*n_ptr, capacity);
+__global__ __launch_bounds__(256) void window_shift_kernel(int32_t *__restrict__ uv, const unsigned *__restrict__ n_ptr, long long n_or_capacity, const int *__restrict__ bbox) {
+    const long long n = n_ptr ? min((long long)*n_ptr, n_or_capacity) : n_or_capacity;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         uv[2 * i + 0] -= bbox[0];
         uv[2 * i + 1] -= bbox[1];
@@ -404,7 +321,7 @@ __global__ __launch_bounds__(256) void window_shift_dev_kernel(int32_t *__restri
 //                with agent-scope CAS, parents are read through agent-scope atomics (workgroups on other XCDs see the hooks, not their stale L2 lines)
 //   labels       every face's root = the smallest face of its component; per root the faces that have a neighbour (wave-aggregated atomics)
 //   selection    one 64-bit atomicMax of (size << 32) | ~root over the roots whose size passes min_len (the largest; on a tie the smallest root)
-//   compaction   the surviving faces in order, the vertices an input face references in order (trimesh's process=True), faces remapped: the block scans above
+//   compaction   the surviving faces in order, the vertices an input face references in order (trimesh's process=True), faces remapped: mesh_compact.hpp
 // Every bounded loop that runs out (table full, a CAS that keeps losing) and every out-of-range vertex id sets a bit of the error word instead of spinning.
 constexpr unsigned long long CC_EMPTY = ~0ull;
 constexpr int CC_ERR_TABLE = 1, CC_ERR_VERTEX = 2, CC_ERR_UNION = 4;
@@ -433,14 +350,29 @@ struct CCParams {
     int *vmap;                     // [V] compacted index or -1
     double min_len;
     int is_object;
-};
 
-__device__ __forceinline__ long long cc_nf(const CCParams &p) { return min((long long)p.counts[1], p.face_cap); }
-__device__ __forceinline__ long long cc_nv(const CCParams &p) { return min((long long)p.counts[0], p.vert_cap); }
+    __device__ long long nf() const { return min((long long)counts[1], face_cap); }
+    __device__ long long nv() const { return min((long long)counts[0], vert_cap); }
+    __device__ bool passes(unsigned component_size) const { return component_size > 0 && (double)component_size >= min_len; }
+    // the compaction (mesh_compact.hpp): the vertices an input face references, the faces of the surviving components
+    __device__ bool keep_vertex(long long i) const { return referenced[i]; }
+    __device__ bool keep_face(long long f) const {
+        if (!has_nbr[f]) return false;
+        const int r = label[f];
+        if (!passes(size[r])) return false;
+        if (!is_object) return true;
+        const unsigned long long b = *best;  // cc_select_kernel: (size << 32) | ~root of the largest component
+        return b && (unsigned)~(unsigned)r == (unsigned)b;
+    }
+    __device__ int face_vertex(long long f, int k) const {  // (an id out of range has set the error word already: the call fails, the read stays in bounds)
+        const int v = faces[3 * f + k];
+        return v >= 0 && v < nv() ? vmap[v] : -1;
+    }
+};
 // slots in use for F faces: the power of two >= 4 F (at most 3 F distinct edges: load <= 3 / 4), at least 64, within what was allocated
 __device__ __forceinline__ unsigned long long cc_table(const CCParams &p) {
     unsigned long long c = 64;
-    while (c < 4ull * (unsigned long long)cc_nf(p) && (long long)c < p.table_cap) c <<= 1;
+    while (c < 4ull * (unsigned long long)p.nf() && (long long)c < p.table_cap) c <<= 1;
     return c;
 }
 __device__ __forceinline__ unsigned long long cc_hash(unsigned long long k) {  // splitmix64 finaliser
@@ -467,7 +399,7 @@ __device__ __forceinline__ int cc_find(int *parent, int x) {
 
 __global__ __launch_bounds__(256) void cc_init_kernel(CCParams p) {
     const unsigned long long table = cc_table(p);
-    const long long nf = cc_nf(p), nv = cc_nv(p);
+    const long long nf = p.nf(), nv = p.nv();
     const long long n = max((long long)table, max(nf, nv));
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *p.err = 0;
@@ -490,7 +422,7 @@ __global__ __launch_bounds__(256) void cc_init_kernel(CCParams p) {
 
 __global__ __launch_bounds__(256) void cc_insert_kernel(CCParams p) {
     const unsigned long long mask = cc_table(p) - 1;
-    const long long nf = cc_nf(p), nv = cc_nv(p);
+    const long long nf = p.nf(), nv = p.nv();
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < 3 * nf; e += (long long)gridDim.x * 256) {
         const long long f = e / 3;
         const int k = (int)(e - 3 * f);
@@ -517,7 +449,7 @@ __global__ __launch_bounds__(256) void cc_insert_kernel(CCParams p) {
 }
 
 __global__ __launch_bounds__(256) void cc_users_kernel(CCParams p) {
-    const long long nf = cc_nf(p);
+    const long long nf = p.nf();
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < 3 * nf; e += (long long)gridDim.x * 256) {
         const int s = p.slot[e];
         if (s < 0) continue;
@@ -527,7 +459,7 @@ __global__ __launch_bounds__(256) void cc_users_kernel(CCParams p) {
 }
 
 __global__ __launch_bounds__(256) void cc_union_kernel(CCParams p) {
-    const long long nf = cc_nf(p);
+    const long long nf = p.nf();
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < 3 * nf; e += (long long)gridDim.x * 256) {
         const int s = p.slot[e];
         if (s < 0 || p.users[s] != 2) continue;
@@ -550,7 +482,7 @@ __global__ __launch_bounds__(256) void cc_union_kernel(CCParams p) {
 
 // labels and per-root sizes of the faces with a neighbour: one atomic per distinct root in a wave
 __global__ __launch_bounds__(256) void cc_label_kernel(CCParams p) {
-    const long long nf = cc_nf(p);
+    const long long nf = p.nf();
     const int lane = threadIdx.x & 63;
     for (long long base = (long long)blockIdx.x * 256; base < nf; base += (long long)gridDim.x * 256) {
         const long long f = base + threadIdx.x;
@@ -571,135 +503,44 @@ __global__ __launch_bounds__(256) void cc_label_kernel(CCParams p) {
     }
 }
 
-__device__ __forceinline__ bool cc_passes(const CCParams &p, unsigned size) { return size > 0 && (double)size >= p.min_len; }
-
 __global__ __launch_bounds__(256) void cc_select_kernel(CCParams p) {
-    const long long nf = cc_nf(p);
+    const long long nf = p.nf();
     unsigned long long best = 0;
     for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nf; f += (long long)gridDim.x * 256)
-        if (p.label[f] == (int)f && cc_passes(p, p.size[f])) best = max(best, ((unsigned long long)p.size[f] << 32) | (unsigned)~(unsigned)f);
+        if (p.label[f] == (int)f && p.passes(p.size[f])) best = max(best, ((unsigned long long)p.size[f] << 32) | (unsigned)~(unsigned)f);
     for (int off = 32; off > 0; off >>= 1) best = max(best, __shfl_xor(best, off));
     if ((threadIdx.x & 63) == 0 && best) atomicMax(p.best, best);
 }
 
-__device__ __forceinline__ bool cc_keep(const CCParams &p, long long f, unsigned long long best) {
-    if (!p.has_nbr[f]) return false;
-    const int r = p.label[f];
-    if (!cc_passes(p, p.size[r])) return false;
-    return !p.is_object || (best && (unsigned)~(unsigned)r == (unsigned)best);
-}
-
-// per block of TILE: kept faces -> bf, referenced vertices -> bv (both arrays cover max(face blocks, vertex blocks))
-__global__ __launch_bounds__(256) void cc_count_kernel(CCParams p, unsigned *__restrict__ bv, unsigned *__restrict__ bf) {
-    __shared__ unsigned lds[8];
-    const long long nf = cc_nf(p), nv = cc_nv(p);
-    const unsigned long long best = *p.best;
-    unsigned cv = 0, cf = 0;
-    for (int j = 0; j < TILE / 256; ++j) {
-        const long long i = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
-        if (i < nf) cf += cc_keep(p, i, best);
-        if (i < nv) cv += p.referenced[i];
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        cv += (unsigned)__shfl_xor((int)cv, off);
-        cf += (unsigned)__shfl_xor((int)cf, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        lds[threadIdx.x >> 6] = cv;
-        lds[4 + (threadIdx.x >> 6)] = cf;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bv[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
-        bf[blockIdx.x] = lds[4] + lds[5] + lds[6] + lds[7];
-    }
-}
-
-// vmap[v] = compacted index of a referenced vertex (else -1); out_vertex_index (optional) = the kept input ids in order
-__global__ __launch_bounds__(256) void cc_vmap_kernel(CCParams p, const unsigned *__restrict__ bv, int32_t *__restrict__ out_vertex_index) {
-    __shared__ unsigned lds[4];
-    const long long nv = cc_nv(p);
-    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
-    bool ok[TILE / 256];
-    unsigned c = 0;
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j) {
-        ok[j] = base + j < nv && p.referenced[base + j];
-        c += ok[j];
-    }
-    long long o = (long long)bv[blockIdx.x] + block_exclusive(c, lds);
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j) {
-        if (base + j >= nv) continue;
-        p.vmap[base + j] = ok[j] ? (int)o : -1;
-        if (ok[j]) {
-            if (out_vertex_index) out_vertex_index[o] = (int32_t)(base + j);
-            ++o;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void cc_faces_kernel(CCParams p, const unsigned *__restrict__ bf, int32_t *__restrict__ out, long long out_cap) {
-    __shared__ unsigned lds[4];
-    const long long nf = cc_nf(p), nv = cc_nv(p);
-    const unsigned long long best = *p.best;
-    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
-    bool ok[TILE / 256];
-    unsigned c = 0;
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j) {
-        ok[j] = base + j < nf && cc_keep(p, base + j, best);
-        c += ok[j];
-    }
-    long long o = (long long)bf[blockIdx.x] + block_exclusive(c, lds);
-#pragma unroll
-    for (int j = 0; j < TILE / 256; ++j)
-        if (ok[j]) {  // (an id out of range has set the error word already: the call fails, the read stays in bounds)
-            if (o < out_cap)
-                for (int k = 0; k < 3; ++k) {
-                    const int v = p.faces[3 * (base + j) + k];
-                    out[3 * o + k] = v >= 0 && v < nv ? p.vmap[v] : -1;
-                }
-            ++o;
-        }
-}
-
-// hive_fg_frame_mesh_cc: the pixels' vertex rows through the clean-up's vertex map (vid[i] = vmap[vid[i]], -1 = not written)
-__global__ __launch_bounds__(256) void cc_remap_vid_kernel(int *__restrict__ vid, int n, const int *__restrict__ vmap, const unsigned *__restrict__ n_verts, long long vert_cap) {
+// frame_mesh_run: the pixels' vertex rows through a stage's vertex map (vid[i] = vmap[vid[i]], -1 = not written)
+__global__ __launch_bounds__(256) void remap_vid_kernel(int *__restrict__ vid, int n, const int *__restrict__ vmap, const unsigned *__restrict__ n_verts, long long vert_cap) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int v = vid[i];
     vid[i] = v >= 0 && v < min((long long)*n_verts, vert_cap) ? vmap[v] : -1;
 }
 
-// scratch of a clean-up of at most face_cap faces over at most vert_cap vertices, from `base`; returns the bytes it needs
-size_t cc_layout(char *base, long long face_cap, long long vert_cap, CCParams &p, unsigned **bv, unsigned **bf, int *nb) {
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+// scratch of a clean-up of at most face_cap faces over at most vert_cap vertices, taken from L
+void cc_layout(hive_scratch_layout &L, long long face_cap, long long vert_cap, CCParams &p, unsigned **bv, unsigned **bf, int *nb) {
     long long table = 64;
     while (table < 4 * face_cap) table <<= 1;
     *nb = (int)std::max<long long>(1, (std::max(face_cap, vert_cap) + TILE - 1) / TILE);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *at = base + off;
-        off += align(bytes);
-        return at;
-    };
+    const size_t T = (size_t)table, F = (size_t)face_cap, V = (size_t)vert_cap;
     p.face_cap = face_cap;
     p.vert_cap = vert_cap;
     p.table_cap = table;
-    p.keys = (unsigned long long *)take((size_t)table * 8);
-    p.users = (unsigned *)take((size_t)table * 4);
-    p.first = (int *)take((size_t)table * 4);
-    p.slot = (int *)take((size_t)face_cap * 12);
-    p.parent = (int *)take((size_t)face_cap * 4);
-    p.label = (int *)take((size_t)face_cap * 4);
-    p.size = (unsigned *)take((size_t)face_cap * 4);
-    p.has_nbr = (uint8_t *)take((size_t)face_cap);
-    p.vmap = (int *)take((size_t)vert_cap * 4);
-    p.referenced = (uint8_t *)take((size_t)vert_cap);
-    *bv = (unsigned *)take((size_t)*nb * 4);
-    *bf = (unsigned *)take((size_t)*nb * 4);
-    return off;
+    p.keys = L.take<unsigned long long>(T);
+    p.users = L.take<unsigned>(T);
+    p.first = L.take<int>(T);
+    p.slot = L.take<int>(3 * F);
+    p.parent = L.take<int>(F);
+    p.label = L.take<int>(F);
+    p.size = L.take<unsigned>(F);
+    p.has_nbr = L.take<uint8_t>(F);
+    p.vmap = L.take<int>(V);
+    p.referenced = L.take<uint8_t>(V);
+    *bv = L.take<unsigned>((size_t)*nb);
+    *bf = L.take<unsigned>((size_t)*nb);
 }
 
 // the clean-up's launches on faces already in device memory (counts in p.counts): scans into scalars[6] (vertices) / [7] (faces), box init at scalars + 8
@@ -713,10 +554,7 @@ void cc_launch(hive_ctx *ctx, const CCParams &p, unsigned *bv, unsigned *bf, int
     hipLaunchKernelGGL(cc_union_kernel, grid, dim3(256), 0, ctx->stream, p);
     hipLaunchKernelGGL(cc_label_kernel, grid, dim3(256), 0, ctx->stream, p);
     if (p.is_object) hipLaunchKernelGGL(cc_select_kernel, grid, dim3(256), 0, ctx->stream, p);
-    hipLaunchKernelGGL(cc_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, bv, bf);
-    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, bf, nb, scalars + 6, (int *)(scalars + 8));
-    hipLaunchKernelGGL(cc_vmap_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)bv, out_vertex_index);
-    hipLaunchKernelGGL(cc_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)bf, out_faces, out_face_cap);
+    launch_compaction(ctx, p, bv, bf, nb, scalars + 6, (int *)(scalars + 8), out_faces, out_face_cap, out_vertex_index);
 }
 
 int cc_error(hive_ctx *ctx, unsigned err) {
@@ -726,11 +564,167 @@ int cc_error(hive_ctx *ctx, unsigned err) {
     return HIVE_OK;
 }
 
-}  // namespace
+// ---- the frame path: one object of one frame from the mask to the texture window, behind hive_fg_frame_mesh / _cc / _dec -----------------------------
+struct FrameMeshJob {
+    const char *name;      // the entry point, for messages
+    long long max_pixels;  // H W stays below it
+    const float *depth;    // the inputs
+    const uint8_t *mask;
+    int H, W;
+    const double *Kinv, *K, *R, *t;
+    double max_px, max_depth;
+    double *vertices;  // the caller's buffers and their capacities
+    int64_t vertex_capacity;
+    int32_t *faces;
+    int64_t face_capacity;
+    int32_t *uv;
+    int64_t *n_vertices, *n_faces;  // the results
+    int32_t *bbox;
+    // the optional stages, in the order they run, and what only they report
+    bool decimate = false;
+    int64_t budget = 0;
+    double max_error = 0.0;
+    bool cleanup = false;
+    int is_object = 0;
+    double min_len = 0.0;
+    int64_t *before = nullptr, *decimated = nullptr, *stats = nullptr;  // counts after the grid / after the decimation; the decimation's statistics
+};
 
-void hive_launch_scan_blocks2(hive_ctx *ctx, unsigned *a, unsigned *b, int nb, unsigned *totals, int *bbox) {
-    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, a, b, nb, totals, bbox);
+struct FrameMeshScratch {
+    unsigned *bv, *bf;  // the grid's block counts
+    int *vid;
+    int32_t *grid_faces, *dec_faces;  // with a later stage: every pixel's faces fit
+    double *pos;                      // the grid's vertices, for the decimation
+    char *dec;
+    CCParams cc;
+    unsigned *cbv, *cbf;
+    int cnb;
+};
+
+// device scratch: grid block counts x 2 | vid | the grid's faces | [the grid's vertices | the decimated faces | the decimation's state] | the clean-up's tables
+size_t frame_mesh_layout(char *base, const FrameMeshJob &j, FrameMeshScratch &s) {
+    const size_t n = (size_t)j.H * j.W, nb = (n + TILE - 1) / TILE, fcap = MAX_PIXEL_FACES * n;
+    hive_scratch_layout L{base};
+    s.bv = L.take<unsigned>(nb);
+    s.bf = L.take<unsigned>(nb);
+    s.vid = L.take<int>(n);
+    if (!j.decimate && !j.cleanup) return L.bytes();  // the plain path: its faces go straight to the caller
+    s.grid_faces = L.take<int32_t>(3 * fcap);
+    if (j.decimate) {
+        s.pos = L.take<double>(3 * n);
+        s.dec_faces = L.take<int32_t>(3 * fcap);
+        s.dec = L.take<char>(hive_decimate_scratch_bytes((long long)n, (long long)fcap));
+    }
+    cc_layout(L, (long long)fcap, (long long)n, s.cc, &s.cbv, &s.cbf, &s.cnb);  // (also reserved by a decimation without the clean-up)
+    return L.bytes();
 }
+
+// Scalar block (hive_ctx::d_scalars + CC_SCALARS, the clean-up's): [0] / [1] vertices / faces of the grid, [2] the clean-up's error word, [4..5] its
+// selection, [6] / [7] vertices / faces of the result, [8..11] the texture window's box, [12] / [13] vertices / faces after the decimation.
+int frame_mesh_run(hive_ctx *ctx, const FrameMeshJob &j) {
+    HIVE_REQUIRE(ctx, j.depth && j.Kinv && j.K && j.R && j.t && j.vertices && j.faces && j.uv && j.n_vertices && j.n_faces && j.bbox, "%s: NULL argument", j.name);
+    HIVE_REQUIRE(ctx, j.H > 0 && j.W > 0 && (long long)j.H * j.W < j.max_pixels, "%s: bad image size %dx%d", j.name, j.H, j.W);
+    HIVE_REQUIRE(ctx, j.vertex_capacity > 0 && j.face_capacity > 0, "%s: empty output buffers", j.name);
+    HIVE_REQUIRE(ctx, !j.decimate || j.budget >= 0, "%s: budget %lld < 0", j.name, (long long)j.budget);
+    const int n = j.H * j.W, nb = (n + TILE - 1) / TILE;
+    const long long fcap = (long long)MAX_PIXEL_FACES * n;
+    FrameMeshScratch s{};
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, frame_mesh_layout(nullptr, j, s));
+    if (rc) return rc;
+    frame_mesh_layout((char *)ctx->d_scratch, j, s);
+    const bool staged = j.decimate || j.cleanup;
+    unsigned *sc = ctx->d_scalars + CC_SCALARS, *final_counts = sc + 6;
+    int *d_box = (int *)(sc + 8);
+    // where the grid's faces go: the caller's buffer when no later stage follows, scratch otherwise
+    int32_t *grid_faces = staged ? s.grid_faces : j.faces;
+    const long long grid_face_cap = staged ? fcap : (long long)j.face_capacity;
+    // which stage writes the final counts: the last one that runs; the earlier ones write the words their successor reads
+    unsigned *grid_counts = staged ? sc : final_counts;
+    unsigned *dec_counts = j.cleanup ? sc + 12 : final_counts;
+    const GridParams gp{j.H, j.W, j.max_px, (float)j.max_depth};
+    FrameMeshCam cam;
+    memcpy(cam.Kinv, j.Kinv, sizeof(cam.Kinv));
+    memcpy(cam.R, j.R, sizeof(cam.R));
+    memcpy(cam.t, j.t, sizeof(cam.t));
+    WindowParams wp;
+    memcpy(wp.K, j.K, sizeof(wp.K));
+    memcpy(wp.R, j.R, sizeof(wp.R));
+    memcpy(wp.t, j.t, sizeof(wp.t));
+    wp.scale = 1.0;
+    const dim3 tiles(nb), pixels((n + 255) / 256), blk(256);
+    hipStream_t st = ctx->stream;
+    // 1. the triangulation + face filter of the valid pixels (hive_grid_mesh's kernels; the scan also empties the texture window's box)
+    hipLaunchKernelGGL(grid_count_kernel, tiles, blk, 0, st, j.depth, j.mask, gp, s.bv, s.bf);
+    scan_blocks2(ctx, s.bv, s.bf, nb, grid_counts, d_box);
+    hipLaunchKernelGGL(grid_vid_kernel, tiles, blk, 0, st, j.depth, j.mask, n, (const unsigned *)s.bv, s.vid);
+    hipLaunchKernelGGL(grid_faces_kernel, tiles, blk, 0, st, j.depth, j.mask, gp, (const unsigned *)s.bf, (const int *)s.vid, grid_faces, grid_face_cap);
+    // 2. the decimation (hive_mesh_decimate) of the grid's mesh in scratch; without the clean-up its faces are the result
+    if (j.decimate) {
+        HIVE_CHECK_HIP(ctx, hipMemsetAsync(sc + 2, 0, sizeof(unsigned), st));
+        hipLaunchKernelGGL(grid_vertices_kernel, pixels, blk, 0, st, j.depth, (const int *)s.vid, n, j.W, cam, s.pos, (long long)n);
+        HIVE_CHECK_HIP(ctx, hipGetLastError());
+        hive_dec_job dj;
+        dj.pos = s.pos;
+        dj.faces = grid_faces;
+        dj.counts = grid_counts;
+        dj.vert_cap = n;
+        dj.face_cap = fcap;
+        dj.budget = j.budget;
+        dj.max_error = j.max_error;
+        dj.out_faces = j.cleanup ? s.dec_faces : j.faces;
+        dj.out_face_cap = j.cleanup ? fcap : (long long)j.face_capacity;
+        dj.out_counts = dec_counts;
+        if ((rc = hive_decimate_run(ctx, dj, s.dec, j.stats))) return rc;
+        hipLaunchKernelGGL(remap_vid_kernel, pixels, blk, 0, st, s.vid, n, (const int *)hive_decimate_vmap(s.dec, n, fcap), (const unsigned *)grid_counts, (long long)n);
+    }
+    // 3. the clean-up (hive_mesh_cleanup_cc) of the mesh so far: survivors into the caller's faces, remapped to the vertices they reference
+    if (j.cleanup) {
+        CCParams &p = s.cc;
+        p.counts = j.decimate ? dec_counts : grid_counts;
+        p.err = sc + 2;
+        p.best = (unsigned long long *)(sc + 4);
+        p.faces = j.decimate ? s.dec_faces : grid_faces;
+        p.min_len = j.min_len;
+        p.is_object = j.is_object ? 1 : 0;
+        cc_launch(ctx, p, s.cbv, s.cbf, s.cnb, sc, j.faces, (long long)j.face_capacity, nullptr);
+        hipLaunchKernelGGL(remap_vid_kernel, pixels, blk, 0, st, s.vid, n, (const int *)p.vmap, p.counts, (long long)n);
+    }
+    // 4. the vertices of the pixels that are left, 5. their texture window
+    hipLaunchKernelGGL(grid_vertices_kernel, pixels, blk, 0, st, j.depth, (const int *)s.vid, n, j.W, cam, j.vertices, (long long)j.vertex_capacity);
+    const dim3 wgrid((unsigned)std::min<long long>((std::min<long long>(n, j.vertex_capacity) + 255) / 256, (long long)ctx->num_cus * 4));
+    hipLaunchKernelGGL(window_project_kernel, wgrid, blk, 0, st, (const double *)j.vertices, (const unsigned *)final_counts, (long long)j.vertex_capacity, wp, j.uv, d_box);
+    hipLaunchKernelGGL(window_shift_kernel, wgrid, blk, 0, st, j.uv, (const unsigned *)final_counts, (long long)j.vertex_capacity, (const int *)d_box);
+    HIVE_CHECK_HIP(ctx, hipGetLastError());
+    // 6. ONE read-back through pinned memory, of the words in use: [6..11] on the plain path, [0..11] with the clean-up, [0..13] with the decimation
+    const int first = staged ? 0 : 6, last = j.decimate ? 14 : 12;
+    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
+    unsigned *back = (unsigned *)ctx->h_pinned_small;
+    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(back + first, sc + first, (size_t)(last - first) * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    // when the clean-up's error word is checked: whenever the clean-up ran, before any result is handed out
+    if (j.cleanup && (rc = cc_error(ctx, back[2]))) return rc;
+    const unsigned nv = back[6], nf = back[7];
+    const int *box = (const int *)(back + 8);
+    *j.n_vertices = nv;
+    *j.n_faces = nf;
+    j.bbox[0] = box[0];
+    j.bbox[1] = box[1];
+    j.bbox[2] = nv ? box[2] + 1 : box[2];
+    j.bbox[3] = nv ? box[3] + 1 : box[3];
+    if (staged && j.before) {
+        j.before[0] = back[0];
+        j.before[1] = back[1];
+    }
+    if (j.decimate && j.decimated) {
+        j.decimated[0] = back[dec_counts - sc];
+        j.decimated[1] = back[dec_counts - sc + 1];
+    }
+    HIVE_REQUIRE(ctx, (int64_t)nv <= j.vertex_capacity && (int64_t)nf <= j.face_capacity, "%s: %u vertices / %u faces do not fit the buffers (%lld / %lld)", j.name, nv, nf,
+                 (long long)j.vertex_capacity, (long long)j.face_capacity);
+    return HIVE_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -743,28 +737,37 @@ int hive_grid_mesh(hive_ctx *ctx, const float *depth, const uint8_t *mask, int H
     HIVE_REQUIRE(ctx, capacity >= 0 && (capacity == 0 || out_faces), "grid_mesh: bad output buffer");
     HIVE_REQUIRE(ctx, mem == HIVE_MEM_HOST || mem == HIVE_MEM_DEVICE, "grid_mesh: bad mem kind %d", mem);
     const int n = H * W, nb = (n + TILE - 1) / TILE;
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // device scratch: [depth | mask] (host inputs) | block counts x 2 | vid | faces (host outputs)
-    const size_t off_mask = align((size_t)n * 4), off_bv = off_mask + align((size_t)n), off_bf = off_bv + align((size_t)nb * 4);
-    const size_t off_vid = off_bf + align((size_t)nb * 4), off_faces = off_vid + align((size_t)n * 4);
-    const size_t total = off_faces + (mem == HIVE_MEM_HOST ? align((size_t)capacity * 12) : 0);
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, total);
+    float *s_depth;
+    uint8_t *s_mask;
+    unsigned *bv, *bf;
+    int *vid;
+    int32_t *s_faces = nullptr;
+    auto lay = [&](char *base) {
+        hive_scratch_layout L{base};
+        s_depth = L.take<float>((size_t)n);
+        s_mask = L.take<uint8_t>((size_t)n);
+        bv = L.take<unsigned>((size_t)nb);
+        bf = L.take<unsigned>((size_t)nb);
+        vid = L.take<int>((size_t)n);
+        if (mem == HIVE_MEM_HOST) s_faces = L.take<int32_t>(3 * (size_t)capacity);
+        return L.bytes();
+    };
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, lay(nullptr));
     if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
+    lay((char *)ctx->d_scratch);
     const float *d_depth = depth;
     const uint8_t *d_mask = mask;
     int32_t *d_faces = out_faces;
     if (mem == HIVE_MEM_HOST) {
-        if ((rc = hive_upload(ctx, base, depth, (size_t)n * 4))) return rc;
-        d_depth = (const float *)base;
+        if ((rc = hive_upload(ctx, s_depth, depth, (size_t)n * 4))) return rc;
+        d_depth = s_depth;
         if (mask) {
-            if ((rc = hive_upload(ctx, base + off_mask, mask, (size_t)n))) return rc;
-            d_mask = (const uint8_t *)(base + off_mask);
+            if ((rc = hive_upload(ctx, s_mask, mask, (size_t)n))) return rc;
+            d_mask = s_mask;
         }
-        d_faces = (int32_t *)(base + off_faces);
+        d_faces = s_faces;
     }
-    unsigned *bv = (unsigned *)(base + off_bv), *bf = (unsigned *)(base + off_bf);
-    int *vid = (int *)(base + off_vid);
     unsigned *d_tot = ctx->d_scalars + 32;  // [32] = vertices, [33] = faces
     GridParams p{H, W, max_pixel_distance, (float)max_depth_distance};
     hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, p, bv, bf);
@@ -792,55 +795,9 @@ int hive_fg_frame_mesh(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mas
                        int64_t face_capacity, int32_t *d_uv, int64_t *n_vertices, int64_t *n_faces, int32_t bbox[4]) {
     HIVE_ENTER(ctx);
     if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, d_depth && Kinv && K && R && t && d_vertices && d_faces && d_uv && n_vertices && n_faces && bbox, "fg_frame_mesh: NULL argument");
-    HIVE_REQUIRE(ctx, H > 0 && W > 0 && (long long)H * W < (1ll << 30), "fg_frame_mesh: bad image size %dx%d", H, W);
-    HIVE_REQUIRE(ctx, vertex_capacity > 0 && face_capacity > 0, "fg_frame_mesh: empty output buffers");
-    const int n = H * W, nb = (n + TILE - 1) / TILE;
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t off_bf = align((size_t)nb * 4), off_vid = off_bf + align((size_t)nb * 4);
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_vid + align((size_t)n * 4));
-    if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
-    unsigned *bv = (unsigned *)base, *bf = (unsigned *)(base + off_bf);
-    int *vid = (int *)(base + off_vid);
-    unsigned *d_tot = ctx->d_scalars + 32;  // [32] = vertices, [33] = faces, [34..37] = the texture window's box
-    int *d_box = (int *)(ctx->d_scalars + 34);
-    GridParams p{H, W, max_pixel_distance, (float)max_depth_distance};
-    FrameMeshCam cam;
-    memcpy(cam.Kinv, Kinv, sizeof(cam.Kinv));
-    memcpy(cam.R, R, sizeof(cam.R));
-    memcpy(cam.t, t, sizeof(cam.t));
-    WindowParams wp;
-    memcpy(wp.K, K, sizeof(wp.K));
-    memcpy(wp.R, R, sizeof(wp.R));
-    memcpy(wp.t, t, sizeof(wp.t));
-    wp.scale = 1.0;
-    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, p, bv, bf);
-    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, bf, nb, d_tot, d_box);
-    hipLaunchKernelGGL(grid_vid_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, n, (const unsigned *)bv, vid);
-    hipLaunchKernelGGL(grid_vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_depth, (const int *)vid, n, W, cam, d_vertices, (long long)vertex_capacity);
-    hipLaunchKernelGGL(grid_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, p, (const unsigned *)bf, (const int *)vid, d_faces,
-                       (long long)face_capacity);
-    const dim3 wgrid((unsigned)std::min<long long>((std::min<long long>(n, vertex_capacity) + 255) / 256, (long long)ctx->num_cus * 4));
-    hipLaunchKernelGGL(window_project_dev_kernel, wgrid, dim3(256), 0, ctx->stream, (const double *)d_vertices, (const unsigned *)d_tot, (long long)vertex_capacity, wp, d_uv,
-                       d_box);
-    hipLaunchKernelGGL(window_shift_dev_kernel, wgrid, dim3(256), 0, ctx->stream, d_uv, (const unsigned *)d_tot, (long long)vertex_capacity, (const int *)d_box);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    // ONE read-back for the whole frame mesh: {vertices, faces, box[4]} through pinned memory
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
-    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_pinned_small, d_tot, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned *tot = (const unsigned *)ctx->h_pinned_small;
-    const int *box = (const int *)(tot + 2);
-    *n_vertices = tot[0];
-    *n_faces = tot[1];
-    bbox[0] = box[0];
-    bbox[1] = box[1];
-    bbox[2] = tot[0] ? box[2] + 1 : box[2];
-    bbox[3] = tot[0] ? box[3] + 1 : box[3];
-    HIVE_REQUIRE(ctx, (int64_t)tot[0] <= vertex_capacity && (int64_t)tot[1] <= face_capacity, "fg_frame_mesh: %u vertices / %u faces do not fit the buffers (%lld / %lld)",
-                 tot[0], tot[1], (long long)vertex_capacity, (long long)face_capacity);
-    return HIVE_OK;
+    FrameMeshJob j{"fg_frame_mesh", 1ll << 30, d_depth, d_mask, H, W, Kinv, K, R, t, max_pixel_distance, max_depth_distance,
+                   d_vertices, vertex_capacity, d_faces, face_capacity, d_uv, n_vertices, n_faces, bbox};
+    return frame_mesh_run(ctx, j);
 }
 
 int hive_mesh_cleanup_cc(hive_ctx *ctx, const int32_t *faces, int64_t n_faces, int64_t n_vertices, int is_object, double min_len, int mem, int32_t *out_faces,
@@ -858,25 +815,32 @@ int hive_mesh_cleanup_cc(hive_ctx *ctx, const int32_t *faces, int64_t n_faces, i
         HIVE_REQUIRE(ctx, n_faces == 0, "mesh_cleanup_cc: a face references a vertex id outside [0, n_vertices)");
         return HIVE_OK;
     }
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const long long fcap = std::max<long long>(n_faces, 1);
-    const size_t off_out_faces = align((size_t)fcap * 12), off_out_vi = off_out_faces + align((size_t)fcap * 12);
-    const size_t off_cc = mem == HIVE_MEM_HOST ? off_out_vi + align((size_t)n_vertices * 4) : 0;
+    // device scratch: [faces | out faces | out vertex ids] (host memory) | the clean-up's tables
     CCParams p{};
     unsigned *bv, *bf;
     int nb;
-    const size_t cc_bytes = cc_layout(nullptr, fcap, n_vertices, p, &bv, &bf, &nb);
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_cc + cc_bytes);
+    int32_t *s_faces = nullptr, *s_out_faces = nullptr, *s_out_vi = nullptr;
+    auto lay = [&](char *base) {
+        hive_scratch_layout L{base};
+        if (mem == HIVE_MEM_HOST) {
+            s_faces = L.take<int32_t>(3 * (size_t)fcap);
+            s_out_faces = L.take<int32_t>(3 * (size_t)fcap);
+            s_out_vi = L.take<int32_t>((size_t)n_vertices);
+        }
+        cc_layout(L, fcap, n_vertices, p, &bv, &bf, &nb);
+        return L.bytes();
+    };
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, lay(nullptr));
     if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
-    cc_layout(base + off_cc, fcap, n_vertices, p, &bv, &bf, &nb);
+    lay((char *)ctx->d_scratch);
     const int32_t *d_faces = faces;
     int32_t *d_out_faces = out_faces, *d_out_vi = out_vertex_index;
     if (mem == HIVE_MEM_HOST) {
-        if (n_faces && (rc = hive_upload(ctx, base, faces, (size_t)n_faces * 12))) return rc;
-        d_faces = (const int32_t *)base;
-        d_out_faces = (int32_t *)(base + off_out_faces);
-        d_out_vi = (int32_t *)(base + off_out_vi);
+        if (n_faces && (rc = hive_upload(ctx, s_faces, faces, (size_t)n_faces * 12))) return rc;
+        d_faces = s_faces;
+        d_out_faces = s_out_faces;
+        d_out_vi = s_out_vi;
     }
     unsigned *sc = ctx->d_scalars + CC_SCALARS;
     const unsigned counts[2] = {(unsigned)n_vertices, (unsigned)n_faces};
@@ -907,78 +871,13 @@ int hive_fg_frame_mesh_cc(hive_ctx *ctx, const float *d_depth, const uint8_t *d_
                           int64_t vertex_capacity, int32_t *d_faces, int64_t face_capacity, int32_t *d_uv, int64_t *n_vertices, int64_t *n_faces, int32_t bbox[4], int64_t before[2]) {
     HIVE_ENTER(ctx);
     if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, d_depth && Kinv && K && R && t && d_vertices && d_faces && d_uv && n_vertices && n_faces && bbox, "fg_frame_mesh_cc: NULL argument");
-    HIVE_REQUIRE(ctx, H > 0 && W > 0 && (long long)H * W < (1ll << 27), "fg_frame_mesh_cc: bad image size %dx%d", H, W);
-    HIVE_REQUIRE(ctx, vertex_capacity > 0 && face_capacity > 0, "fg_frame_mesh_cc: empty output buffers");
-    const int n = H * W, nb = (n + TILE - 1) / TILE;
-    const long long fcap = (long long)MAX_PIXEL_FACES * n;  // every pixel's faces fit: the grid's faces land in scratch, the survivors in d_faces
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // device scratch: grid block counts x 2 | vid | the grid's faces | the clean-up's tables
-    const size_t off_bf = align((size_t)nb * 4), off_vid = off_bf + align((size_t)nb * 4), off_faces = off_vid + align((size_t)n * 4);
-    const size_t off_cc = off_faces + align((size_t)fcap * 12);
-    CCParams p{};
-    unsigned *cbv, *cbf;
-    int cnb;
-    const size_t cc_bytes = cc_layout(nullptr, fcap, n, p, &cbv, &cbf, &cnb);
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_cc + cc_bytes);
-    if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
-    cc_layout(base + off_cc, fcap, n, p, &cbv, &cbf, &cnb);
-    unsigned *bv = (unsigned *)base, *bf = (unsigned *)(base + off_bf);
-    int *vid = (int *)(base + off_vid);
-    int32_t *grid_faces = (int32_t *)(base + off_faces);
-    unsigned *sc = ctx->d_scalars + CC_SCALARS;  // [0] = grid vertices, [1] = grid faces, ..., [6] / [7] = vertices / faces kept, [8..11] = the texture window's box
-    GridParams gp{H, W, max_pixel_distance, (float)max_depth_distance};
-    FrameMeshCam cam;
-    memcpy(cam.Kinv, Kinv, sizeof(cam.Kinv));
-    memcpy(cam.R, R, sizeof(cam.R));
-    memcpy(cam.t, t, sizeof(cam.t));
-    WindowParams wp;
-    memcpy(wp.K, K, sizeof(wp.K));
-    memcpy(wp.R, R, sizeof(wp.R));
-    memcpy(wp.t, t, sizeof(wp.t));
-    wp.scale = 1.0;
-    p.counts = sc;
-    p.err = sc + 2;
-    p.best = (unsigned long long *)(sc + 4);
-    p.faces = grid_faces;
-    p.min_len = min_len;
-    p.is_object = is_object ? 1 : 0;
-    // hive_fg_frame_mesh's triangulation + face filter, into scratch
-    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, gp, bv, bf);
-    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, bf, nb, sc, (int *)(sc + 8));
-    hipLaunchKernelGGL(grid_vid_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, n, (const unsigned *)bv, vid);
-    hipLaunchKernelGGL(grid_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, gp, (const unsigned *)bf, (const int *)vid, grid_faces, fcap);
-    // the clean-up: survivors into d_faces, remapped to the referenced vertices; the pixels' vertex rows follow the vertex map
-    cc_launch(ctx, p, cbv, cbf, cnb, sc, d_faces, (long long)face_capacity, nullptr);
-    hipLaunchKernelGGL(cc_remap_vid_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, vid, n, (const int *)p.vmap, (const unsigned *)sc, (long long)n);
-    hipLaunchKernelGGL(grid_vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_depth, (const int *)vid, n, W, cam, d_vertices, (long long)vertex_capacity);
-    // the texture window over the vertices that are left
-    const dim3 wgrid((unsigned)std::min<long long>((std::min<long long>(n, vertex_capacity) + 255) / 256, (long long)ctx->num_cus * 4));
-    hipLaunchKernelGGL(window_project_dev_kernel, wgrid, dim3(256), 0, ctx->stream, (const double *)d_vertices, (const unsigned *)(sc + 6), (long long)vertex_capacity, wp,
-                       d_uv, (int *)(sc + 8));
-    hipLaunchKernelGGL(window_shift_dev_kernel, wgrid, dim3(256), 0, ctx->stream, d_uv, (const unsigned *)(sc + 6), (long long)vertex_capacity, (const int *)(sc + 8));
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    // ONE read-back: {grid counts, error word, selection, kept counts, box[4]} through pinned memory
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
-    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_pinned_small, sc, 12 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned *back = (const unsigned *)ctx->h_pinned_small;
-    if ((rc = cc_error(ctx, back[2]))) return rc;
-    const int *box = (const int *)(back + 8);
-    *n_vertices = back[6];
-    *n_faces = back[7];
-    bbox[0] = box[0];
-    bbox[1] = box[1];
-    bbox[2] = back[6] ? box[2] + 1 : box[2];
-    bbox[3] = back[6] ? box[3] + 1 : box[3];
-    if (before) {
-        before[0] = back[0];
-        before[1] = back[1];
-    }
-    HIVE_REQUIRE(ctx, (int64_t)back[6] <= vertex_capacity && (int64_t)back[7] <= face_capacity,
-                 "fg_frame_mesh_cc: %u vertices / %u faces do not fit the buffers (%lld / %lld)", back[6], back[7], (long long)vertex_capacity, (long long)face_capacity);
-    return HIVE_OK;
+    FrameMeshJob j{"fg_frame_mesh_cc", 1ll << 27, d_depth, d_mask, H, W, Kinv, K, R, t, max_pixel_distance, max_depth_distance,
+                   d_vertices, vertex_capacity, d_faces, face_capacity, d_uv, n_vertices, n_faces, bbox};
+    j.cleanup = true;
+    j.is_object = is_object;
+    j.min_len = min_len;
+    j.before = before;
+    return frame_mesh_run(ctx, j);
 }
 
 int hive_fg_frame_mesh_dec(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int H, int W, const double Kinv[9], const double K[9], const double R[9],
@@ -987,107 +886,18 @@ int hive_fg_frame_mesh_dec(hive_ctx *ctx, const float *d_depth, const uint8_t *d
                            int64_t *n_vertices, int64_t *n_faces, int32_t bbox[4], int64_t before[2], int64_t decimated[2], int64_t stats[3]) {
     HIVE_ENTER(ctx);
     if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, d_depth && Kinv && K && R && t && d_vertices && d_faces && d_uv && n_vertices && n_faces && bbox, "fg_frame_mesh_dec: NULL argument");
-    HIVE_REQUIRE(ctx, H > 0 && W > 0 && (long long)H * W < (1ll << 27), "fg_frame_mesh_dec: bad image size %dx%d", H, W);
-    HIVE_REQUIRE(ctx, vertex_capacity > 0 && face_capacity > 0, "fg_frame_mesh_dec: empty output buffers");
-    HIVE_REQUIRE(ctx, budget >= 0, "fg_frame_mesh_dec: budget %lld < 0", (long long)budget);
-    const int n = H * W, nb = (n + TILE - 1) / TILE;
-    const long long fcap = (long long)MAX_PIXEL_FACES * n;
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // device scratch: grid block counts x 2 | vid | the grid's faces | the grid's vertices | the decimated faces | the decimation's state | the clean-up's tables
-    const size_t off_bf = align((size_t)nb * 4), off_vid = off_bf + align((size_t)nb * 4), off_faces = off_vid + align((size_t)n * 4);
-    const size_t off_pos = off_faces + align((size_t)fcap * 12), off_dfaces = off_pos + align((size_t)n * 24);
-    const size_t off_dec = off_dfaces + align((size_t)fcap * 12), off_cc = off_dec + align(hive_decimate_scratch_bytes(n, fcap));
-    CCParams p{};
-    unsigned *cbv, *cbf;
-    int cnb;
-    const size_t cc_bytes = cc_layout(nullptr, fcap, n, p, &cbv, &cbf, &cnb);
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_cc + cc_bytes);
-    if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
-    cc_layout(base + off_cc, fcap, n, p, &cbv, &cbf, &cnb);
-    unsigned *bv = (unsigned *)base, *bf = (unsigned *)(base + off_bf);
-    int *vid = (int *)(base + off_vid);
-    int32_t *grid_faces = (int32_t *)(base + off_faces), *dec_faces = (int32_t *)(base + off_dfaces);
-    double *pos = (double *)(base + off_pos);
-    // [0] = grid vertices, [1] = grid faces, [2] error word of the clean-up, [6] / [7] = vertices / faces kept, [8..11] = the texture window's box,
-    // [12] / [13] = vertices / faces after the decimation
-    unsigned *sc = ctx->d_scalars + CC_SCALARS;
-    GridParams gp{H, W, max_pixel_distance, (float)max_depth_distance};
-    FrameMeshCam cam;
-    memcpy(cam.Kinv, Kinv, sizeof(cam.Kinv));
-    memcpy(cam.R, R, sizeof(cam.R));
-    memcpy(cam.t, t, sizeof(cam.t));
-    WindowParams wp;
-    memcpy(wp.K, K, sizeof(wp.K));
-    memcpy(wp.R, R, sizeof(wp.R));
-    memcpy(wp.t, t, sizeof(wp.t));
-    wp.scale = 1.0;
-    // hive_fg_frame_mesh's triangulation + face filter and point cloud, into scratch
-    HIVE_CHECK_HIP(ctx, hipMemsetAsync(sc + 2, 0, sizeof(unsigned), ctx->stream));
-    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, gp, bv, bf);
-    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, bf, nb, sc, (int *)(sc + 8));
-    hipLaunchKernelGGL(grid_vid_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, n, (const unsigned *)bv, vid);
-    hipLaunchKernelGGL(grid_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, gp, (const unsigned *)bf, (const int *)vid, grid_faces, fcap);
-    hipLaunchKernelGGL(grid_vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_depth, (const int *)vid, n, W, cam, pos, (long long)n);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    // the decimation (hive_mesh_decimate); without the clean-up its faces are the result
-    hive_dec_job job;
-    job.pos = pos;
-    job.faces = grid_faces;
-    job.counts = sc;
-    job.vert_cap = n;
-    job.face_cap = fcap;
-    job.budget = budget;
-    job.max_error = max_error;
-    job.out_faces = enable_cc ? dec_faces : d_faces;
-    job.out_face_cap = enable_cc ? fcap : (long long)face_capacity;
-    job.out_counts = enable_cc ? sc + 12 : sc + 6;
-    void *dec_scratch = base + off_dec;
-    if ((rc = hive_decimate_run(ctx, job, dec_scratch, stats))) return rc;
-    const int32_t *dvmap = hive_decimate_vmap(dec_scratch, n, fcap);
-    hipLaunchKernelGGL(cc_remap_vid_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, vid, n, (const int *)dvmap, (const unsigned *)sc, (long long)n);
-    if (enable_cc) {
-        p.counts = sc + 12;
-        p.err = sc + 2;
-        p.best = (unsigned long long *)(sc + 4);
-        p.faces = dec_faces;
-        p.min_len = min_len;
-        p.is_object = is_object ? 1 : 0;
-        cc_launch(ctx, p, cbv, cbf, cnb, sc, d_faces, (long long)face_capacity, nullptr);
-        hipLaunchKernelGGL(cc_remap_vid_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, vid, n, (const int *)p.vmap, (const unsigned *)(sc + 12), (long long)n);
-    }
-    hipLaunchKernelGGL(grid_vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_depth, (const int *)vid, n, W, cam, d_vertices, (long long)vertex_capacity);
-    // the texture window over the vertices that are left
-    const dim3 wgrid((unsigned)std::min<long long>((std::min<long long>(n, vertex_capacity) + 255) / 256, (long long)ctx->num_cus * 4));
-    hipLaunchKernelGGL(window_project_dev_kernel, wgrid, dim3(256), 0, ctx->stream, (const double *)d_vertices, (const unsigned *)(sc + 6), (long long)vertex_capacity, wp,
-                       d_uv, (int *)(sc + 8));
-    hipLaunchKernelGGL(window_shift_dev_kernel, wgrid, dim3(256), 0, ctx->stream, d_uv, (const unsigned *)(sc + 6), (long long)vertex_capacity, (const int *)(sc + 8));
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    // the final read-back: {grid counts, error word, selection, kept counts, box[4], decimated counts} through pinned memory
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
-    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_pinned_small, sc, 14 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned *back = (const unsigned *)ctx->h_pinned_small;
-    if (enable_cc && (rc = cc_error(ctx, back[2]))) return rc;
-    const int *box = (const int *)(back + 8);
-    *n_vertices = back[6];
-    *n_faces = back[7];
-    bbox[0] = box[0];
-    bbox[1] = box[1];
-    bbox[2] = back[6] ? box[2] + 1 : box[2];
-    bbox[3] = back[6] ? box[3] + 1 : box[3];
-    if (before) {
-        before[0] = back[0];
-        before[1] = back[1];
-    }
-    if (decimated) {
-        decimated[0] = enable_cc ? back[12] : back[6];
-        decimated[1] = enable_cc ? back[13] : back[7];
-    }
-    HIVE_REQUIRE(ctx, (int64_t)back[6] <= vertex_capacity && (int64_t)back[7] <= face_capacity,
-                 "fg_frame_mesh_dec: %u vertices / %u faces do not fit the buffers (%lld / %lld)", back[6], back[7], (long long)vertex_capacity, (long long)face_capacity);
-    return HIVE_OK;
+    FrameMeshJob j{"fg_frame_mesh_dec", 1ll << 27, d_depth, d_mask, H, W, Kinv, K, R, t, max_pixel_distance, max_depth_distance,
+                   d_vertices, vertex_capacity, d_faces, face_capacity, d_uv, n_vertices, n_faces, bbox};
+    j.decimate = true;
+    j.budget = budget;
+    j.max_error = max_error;
+    j.cleanup = enable_cc != 0;
+    j.is_object = is_object;
+    j.min_len = min_len;
+    j.before = before;
+    j.decimated = decimated;
+    j.stats = stats;
+    return frame_mesh_run(ctx, j);
 }
 
 int hive_filter_faces(hive_ctx *ctx, const int32_t *points2d, const float *depth, int64_t n_points, const int32_t *faces, int64_t n_faces_in,
@@ -1099,25 +909,35 @@ int hive_filter_faces(hive_ctx *ctx, const int32_t *points2d, const float *depth
     if (n_faces_in == 0) return HIVE_OK;
     HIVE_REQUIRE(ctx, points2d && depth && faces && out_faces && n_points > 0, "filter_faces: NULL argument");
     HIVE_REQUIRE(ctx, mem == HIVE_MEM_HOST || mem == HIVE_MEM_DEVICE, "filter_faces: bad mem kind %d", mem);
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const int nb = (int)((n_faces_in + TILE - 1) / TILE);
-    const size_t off_depth = align((size_t)n_points * 8), off_faces = off_depth + align((size_t)n_points * 4);
-    const size_t off_out = off_faces + align((size_t)n_faces_in * 12), off_blk = off_out + align((size_t)n_faces_in * 12);
-    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, off_blk + (size_t)nb * 4);
+    // device scratch: [points | depth | faces | out faces] (host memory) | block counts
+    int32_t *s_points2d, *s_faces, *s_out;
+    float *s_depth;
+    unsigned *blk;
+    auto lay = [&](char *base) {
+        hive_scratch_layout L{base};
+        s_points2d = L.take<int32_t>(2 * (size_t)n_points);
+        s_depth = L.take<float>((size_t)n_points);
+        s_faces = L.take<int32_t>(3 * (size_t)n_faces_in);
+        s_out = L.take<int32_t>(3 * (size_t)n_faces_in);
+        blk = L.take<unsigned>((size_t)nb);
+        return L.bytes();
+    };
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, lay(nullptr));
     if (rc) return rc;
-    char *base = (char *)ctx->d_scratch;
+    lay((char *)ctx->d_scratch);
     FilterParams p{points2d, depth, faces, (long long)n_faces_in, max_pixel_distance, (float)max_depth_distance};
     int32_t *d_out = out_faces;
     if (mem == HIVE_MEM_HOST) {
-        if ((rc = hive_upload(ctx, base, points2d, (size_t)n_points * 8))) return rc;
-        if ((rc = hive_upload(ctx, base + off_depth, depth, (size_t)n_points * 4))) return rc;
-        if ((rc = hive_upload(ctx, base + off_faces, faces, (size_t)n_faces_in * 12))) return rc;
-        p.points2d = (const int32_t *)base;
-        p.depth = (const float *)(base + off_depth);
-        p.faces = (const int32_t *)(base + off_faces);
-        d_out = (int32_t *)(base + off_out);
+        if ((rc = hive_upload(ctx, s_points2d, points2d, (size_t)n_points * 8))) return rc;
+        if ((rc = hive_upload(ctx, s_depth, depth, (size_t)n_points * 4))) return rc;
+        if ((rc = hive_upload(ctx, s_faces, faces, (size_t)n_faces_in * 12))) return rc;
+        p.points2d = s_points2d;
+        p.depth = s_depth;
+        p.faces = s_faces;
+        d_out = s_out;
     }
-    unsigned *blk = (unsigned *)(base + off_blk), *d_tot = ctx->d_scalars + 34;
+    unsigned *d_tot = ctx->d_scalars + 34;
     hipLaunchKernelGGL(filter_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, blk);
     hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, d_tot);
     hipLaunchKernelGGL(filter_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)blk, d_out);
@@ -1155,8 +975,8 @@ int hive_texture_window(hive_ctx *ctx, const double *points, int64_t n, const do
     memcpy(p.t, t, sizeof(p.t));
     p.scale = scale_factor;
     const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, (long long)ctx->num_cus * 4));
-    hipLaunchKernelGGL(window_project_kernel, grid, dim3(256), 0, ctx->stream, d_pts, (long long)n, p, d_uv, d_box);
-    hipLaunchKernelGGL(window_shift_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_uv, (long long)n, (const int *)d_box);
+    hipLaunchKernelGGL(window_project_kernel, grid, dim3(256), 0, ctx->stream, d_pts, (const unsigned *)nullptr, (long long)n, p, d_uv, d_box);
+    hipLaunchKernelGGL(window_shift_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_uv, (const unsigned *)nullptr, (long long)n, (const int *)d_box);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     int32_t box[4];
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, ctx->stream));

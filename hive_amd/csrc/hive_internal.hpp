@@ -130,9 +130,19 @@ __device__ __forceinline__ unsigned block_exclusive(unsigned c, unsigned *lds) {
     __syncthreads();
     return before + inc - c;
 }
-// fgmesh.hip: exclusive scans of two block-count arrays of nb entries by one workgroup, totals[0..1] = their sums; bbox[0..3] = the texture window's
-// empty box (INT_MAX, INT_MAX, INT_MIN, INT_MIN)
-void hive_launch_scan_blocks2(hive_ctx *ctx, unsigned *a, unsigned *b, int nb, unsigned *totals, int *bbox);
+// regions of one block of device scratch, 256-byte aligned, in the order they are taken.  With a null base the layout only sizes: take() returns
+// null, bytes() is what to reserve; the same takes over the reserved block then give the pointers.
+struct hive_scratch_layout {
+    char *base = nullptr;
+    size_t off = 0;
+    template <class T>
+    T *take(size_t count) {
+        T *at = base ? (T *)(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return at;
+    }
+    size_t bytes() const { return off; }
+};
 // decimate.hip: quadric edge collapse of a device-resident mesh (hive_mesh_decimate), for the entry points of any translation unit
 struct hive_dec_job {
     const double *pos;                   // [V][3]

@@ -111,6 +111,37 @@ def get_mesh_texture_and_uv(vertices, image, camera_matrix, rotation=np.eye(3), 
     return (texture, uv, (min_u, min_v, max_u, max_v)) if return_bbox else (texture, uv)
 
 
+def _compact_mesh(vertices, faces, ctx, call):
+    """The marshalling of the calls that keep a subset of a mesh (``hive_mesh_cleanup_cc``, ``hive_mesh_decimate``): device form when either input is a tensor,
+    host form otherwise.  Prepares the int32 faces ``f`` and the outputs ``out_f`` (F, 3) and ``out_vi`` (V), runs
+    ``call(ctx, as_input, f, nf, nv, mem, out_f, out_vi, n_faces, n_verts)`` (``as_input(a, "float64")``: ``a`` contiguous in that dtype where ``f`` lives; the
+    last two are ``byref`` counts) and returns ``(vertices[kept], faces[:n])`` in the inputs' kind and dtype."""
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    n_faces, n_verts = ctypes.c_int64(0), ctypes.c_int64(0)
+    on_device = _is_torch(faces) or _is_torch(vertices)
+    if on_device:
+        import torch
+        dev = faces.device if _is_torch(faces) else vertices.device
+        ctx = ctx or _lib.default_context(dev.index or 0)
+        ctx.follow_torch_stream()
+        as_input = lambda a, dt: (a if _is_torch(a) else torch.from_numpy(np.asarray(a))).to(device=dev, dtype=getattr(torch, dt)).contiguous()
+        out_f = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        out_vi = torch.empty(nv, dtype=torch.int32, device=dev)
+    else:
+        ctx = ctx or _lib.default_context()
+        as_input = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
+        out_f = np.empty((nf, 3), np.int32)
+        out_vi = np.empty(nv, np.int32)
+    f = as_input(faces, "int32")
+    ctx.check(call(ctx, as_input, f, nf, nv, MEM_DEVICE if on_device else MEM_HOST, out_f, out_vi, ctypes.byref(n_faces), ctypes.byref(n_verts)))
+    if on_device:
+        keep = out_vi[:n_verts.value].long()
+        v = vertices if _is_torch(vertices) else torch.from_numpy(np.asarray(vertices)).to(dev)
+        out_dtype = faces.dtype if _is_torch(faces) else torch.int32
+        return v.index_select(0, keep.to(v.device)), out_f[:n_faces.value].to(out_dtype)
+    return np.asarray(vertices)[out_vi[:n_verts.value]], out_f[:n_faces.value].astype(np.asarray(faces).dtype, copy=False)
+
+
 def cleanup_with_connected_components(vertices, faces, is_object=True, min_components=5, ctx=None):
     """``Pipeline._cleanup_with_connected_components`` (/root/reference/hive/pipeline.py:741-779) in one library call (``hive_mesh_cleanup_cc``): the
     components of trimesh's face adjacency (faces sharing an edge that exactly two faces use; a face without such a neighbour is in no component and
@@ -120,29 +151,9 @@ def cleanup_with_connected_components(vertices, faces, is_object=True, min_compo
     to vertex order), and the surviving faces in order, indexing them.  Without faces every vertex is kept."""
     validate_shape(vertices, 'vertices', expected_shape=(None, 3))
     validate_shape(faces, 'faces', expected_shape=(None, 3))
-    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
-    n_faces, n_verts = ctypes.c_int64(0), ctypes.c_int64(0)
-    if _is_torch(faces) or _is_torch(vertices):
-        import torch
-        dev = faces.device if _is_torch(faces) else vertices.device
-        ctx = ctx or _lib.default_context(dev.index or 0)
-        ctx.follow_torch_stream()
-        f = (faces if _is_torch(faces) else torch.from_numpy(np.asarray(faces))).to(device=dev, dtype=torch.int32).contiguous()
-        out_f = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        out_vi = torch.empty(nv, dtype=torch.int32, device=dev)
-        ctx.check(ctx.lib.hive_mesh_cleanup_cc(ctx.handle, ptr(f), nf, nv, int(bool(is_object)), float(min_components), MEM_DEVICE, ptr(out_f), ptr(out_vi),
-                                               ctypes.byref(n_faces), ctypes.byref(n_verts)))
-        keep = out_vi[:n_verts.value].long()
-        v = vertices if _is_torch(vertices) else torch.from_numpy(np.asarray(vertices)).to(dev)
-        out_dtype = faces.dtype if _is_torch(faces) else torch.int32
-        return v.index_select(0, keep.to(v.device)), out_f[:n_faces.value].to(out_dtype)
-    ctx = ctx or _lib.default_context()
-    f = np.ascontiguousarray(faces, dtype=np.int32)
-    out_f = np.empty((nf, 3), np.int32)
-    out_vi = np.empty(nv, np.int32)
-    ctx.check(ctx.lib.hive_mesh_cleanup_cc(ctx.handle, ptr(f), nf, nv, int(bool(is_object)), float(min_components), MEM_HOST, ptr(out_f), ptr(out_vi),
-                                           ctypes.byref(n_faces), ctypes.byref(n_verts)))
-    return np.asarray(vertices)[out_vi[:n_verts.value]], out_f[:n_faces.value].astype(np.asarray(faces).dtype, copy=False)
+    def call(ctx, as_input, f, nf, nv, mem, out_f, out_vi, n_faces, n_verts):
+        return ctx.lib.hive_mesh_cleanup_cc(ctx.handle, ptr(f), nf, nv, int(bool(is_object)), float(min_components), mem, ptr(out_f), ptr(out_vi), n_faces, n_verts)
+    return _compact_mesh(vertices, faces, ctx, call)
 
 
 def billboard(vertices, rotation, translation, ctx=None, return_median=False):
@@ -197,33 +208,12 @@ def decimate_mesh(vertices, faces, is_object, options: MeshDecimationOptions, ct
     budget = _decimation_budget(is_object, options)
     if budget is None:
         return (vertices, faces, (0, 0, 0)) if return_stats else (vertices, faces)
-    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
-    n_faces, n_verts = ctypes.c_int64(0), ctypes.c_int64(0)
     stats = np.zeros(3, np.int64)
-    if _is_torch(faces) or _is_torch(vertices):
-        import torch
-        dev = faces.device if _is_torch(faces) else vertices.device
-        ctx = ctx or _lib.default_context(dev.index or 0)
-        ctx.follow_torch_stream()
-        f = (faces if _is_torch(faces) else torch.from_numpy(np.asarray(faces))).to(device=dev, dtype=torch.int32).contiguous()
-        v = (vertices if _is_torch(vertices) else torch.from_numpy(np.asarray(vertices))).to(device=dev, dtype=torch.float64).contiguous()
-        out_f = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        out_vi = torch.empty(nv, dtype=torch.int32, device=dev)
-        ctx.check(ctx.lib.hive_mesh_decimate(ctx.handle, ptr(v), nv, ptr(f), nf, budget, float(options.max_error), MEM_DEVICE, ptr(out_f), ptr(out_vi),
-                                             ctypes.byref(n_faces), ctypes.byref(n_verts), ptr(stats)))
-        keep = out_vi[:n_verts.value].long()
-        src = vertices if _is_torch(vertices) else torch.from_numpy(np.asarray(vertices)).to(dev)
-        out_dtype = faces.dtype if _is_torch(faces) else torch.int32
-        out = (src.index_select(0, keep.to(src.device)), out_f[:n_faces.value].to(out_dtype))
-    else:
-        ctx = ctx or _lib.default_context()
-        v = np.ascontiguousarray(vertices, dtype=np.float64)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
-        out_f = np.empty((nf, 3), np.int32)
-        out_vi = np.empty(nv, np.int32)
-        ctx.check(ctx.lib.hive_mesh_decimate(ctx.handle, ptr(v), nv, ptr(f), nf, budget, float(options.max_error), MEM_HOST, ptr(out_f), ptr(out_vi),
-                                             ctypes.byref(n_faces), ctypes.byref(n_verts), ptr(stats)))
-        out = (np.asarray(vertices)[out_vi[:n_verts.value]], out_f[:n_faces.value].astype(np.asarray(faces).dtype, copy=False))
+
+    def call(ctx, as_input, f, nf, nv, mem, out_f, out_vi, n_faces, n_verts):
+        v = as_input(vertices, "float64")
+        return ctx.lib.hive_mesh_decimate(ctx.handle, ptr(v), nv, ptr(f), nf, budget, float(options.max_error), mem, ptr(out_f), ptr(out_vi), n_faces, n_verts, ptr(stats))
+    out = _compact_mesh(vertices, faces, ctx, call)
     return (*out, tuple(int(x) for x in stats)) if return_stats else out
 
 
@@ -291,25 +281,20 @@ def frame_mesh(depth, mask, image, camera_matrix, rotation=np.eye(3), translatio
     before = None
     budget = None if decimation_options is None else _decimation_budget(is_object, decimation_options)
     decimated, stats = None, np.zeros(3, np.int64)
+    # what the three entry points share: the inputs through max_depth_distance in front, the buffers and results behind the stages' own arguments
+    inputs = (ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance), float(options.max_depth_distance))
+    outputs = (ptr(buffers.vertices), buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0], ptr(buffers.uv), ctypes.byref(nv), ctypes.byref(nf), ptr(box))
+    cleanup = (int(bool(is_object)), float(min_components))
+    counts, after = np.zeros(2, np.int64), np.zeros(2, np.int64)
     if budget is not None:
-        counts, after = np.zeros(2, np.int64), np.zeros(2, np.int64)
-        ctx.check(ctx.lib.hive_fg_frame_mesh_dec(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
-                                                 float(options.max_depth_distance), budget, float(decimation_options.max_error), int(bool(enable_cc_analysis)),
-                                                 int(bool(is_object)), float(min_components), ptr(buffers.vertices), buffers.vertices.shape[0], ptr(buffers.faces),
-                                                 buffers.faces.shape[0], ptr(buffers.uv), ctypes.byref(nv), ctypes.byref(nf), ptr(box), ptr(counts), ptr(after),
-                                                 ptr(stats)))
+        ctx.check(ctx.lib.hive_fg_frame_mesh_dec(*inputs, budget, float(decimation_options.max_error), int(bool(enable_cc_analysis)), *cleanup, *outputs, ptr(counts),
+                                                 ptr(after), ptr(stats)))
         before, decimated = (int(counts[0]), int(counts[1])), (int(after[0]), int(after[1]))
     elif enable_cc_analysis:
-        counts = np.zeros(2, np.int64)
-        ctx.check(ctx.lib.hive_fg_frame_mesh_cc(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
-                                                float(options.max_depth_distance), int(bool(is_object)), float(min_components), ptr(buffers.vertices),
-                                                buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0], ptr(buffers.uv), ctypes.byref(nv),
-                                                ctypes.byref(nf), ptr(box), ptr(counts)))
+        ctx.check(ctx.lib.hive_fg_frame_mesh_cc(*inputs, *cleanup, *outputs, ptr(counts)))
         before = (int(counts[0]), int(counts[1]))
     else:
-        ctx.check(ctx.lib.hive_fg_frame_mesh(ctx.handle, ptr(d), ptr(m), h, w, ptr(Kinv), ptr(K), ptr(R), ptr(t), float(options.max_pixel_distance),
-                                             float(options.max_depth_distance), ptr(buffers.vertices), buffers.vertices.shape[0], ptr(buffers.faces), buffers.faces.shape[0],
-                                             ptr(buffers.uv), ctypes.byref(nv), ctypes.byref(nf), ptr(box)))
+        ctx.check(ctx.lib.hive_fg_frame_mesh(*inputs, *outputs))
     if billboard and nv.value:
         ctx.check(ctx.lib.hive_fg_billboard(ctx.handle, ptr(buffers.vertices), nv.value, ptr(R), ptr(t), None))
         ctx.check(ctx.lib.hive_texture_window(ctx.handle, ptr(buffers.vertices), nv.value, ptr(K), ptr(R), ptr(t), 1.0, MEM_DEVICE, ptr(buffers.uv), ptr(box)))

@@ -331,3 +331,90 @@ def test_process_frame_stacks_the_objects_like_the_reference_loop(gpu_ctx):
         assert 0.0 <= float(got["uv"].min()) and float(got["uv"].max()) <= 1.0
     empty = foreground.process_frame(rgb, depth, np.zeros_like(ids), K, pose, dil, flt, ctx=gpu_ctx)
     assert empty is None
+
+
+# ---- the three entry points share one runner, one scalar block and one scratch layout: what that can newly get wrong ----
+_VARIANTS = {"plain": (False, False), "cc": (True, False), "dec": (False, True), "dec+cc": (True, True)}  # (clean-up, decimation)
+
+
+def _room_object(h, w):
+    """One frame of the synthetic room with one ellipse object: (depth, mask, rgb) on the device, K, R, t."""
+    import torch
+    from hive_amd import synthetic
+    seq = synthetic.make_sequence(num_frames=1, height=h, width=w)
+    mask = synthetic.ellipse_masks(1, h, w, num_objects=1, seed=7)[0] == 1
+    w2c = np.linalg.inv(seq["poses"][0])
+    dev = [torch.from_numpy(a).cuda() for a in (seq["depth"][0], mask, seq["color"][0])]
+    return dev, seq["K"], w2c[:3, :3], w2c[:3, 3:4]
+
+
+def _run_variant(ctx, buffers, frame, variant, mask=None):
+    from hive_amd import foreground
+    from hive_amd.options import MeshDecimationOptions
+    (depth, obj_mask, rgb), K, R, t = frame
+    cc, dec = _VARIANTS[variant]
+    return foreground.frame_mesh(depth, obj_mask if mask is None else mask, rgb, K, R, t, ctx=ctx, buffers=buffers, enable_cc_analysis=cc,
+                                 decimation_options=MeshDecimationOptions(num_faces_object=40) if dec else None)
+
+
+def _snapshot(out):
+    return {k: out[k].cpu().numpy().copy() for k in ("vertices", "faces", "uv")} | {k: out.get(k) for k in ("bbox", "before", "decimated")}
+
+
+def _same(a, b):
+    return all(np.array_equal(a[k], b[k]) and a[k].dtype == b[k].dtype for k in ("vertices", "faces", "uv")) and all(a[k] == b[k] for k in ("bbox", "before", "decimated"))
+
+
+def test_frame_mesh_variants_do_not_disturb_each_other_through_scratch(gpu_ctx):
+    """One context and one set of buffers per size, the variants in turn at alternating sizes (45 x 67: a ragged last tile of 1024 pixels; the scratch regrows
+    at 60 x 80): every result equals, bit for bit, the same variant's result from a fresh context -- nothing one variant leaves in the shared scalar block or
+    in the scratch reaches the next."""
+    from hive_amd import _lib, foreground
+    sizes = [(45, 67), (60, 80)]
+    frames = {s: _room_object(*s) for s in sizes}
+    buffers = {s: foreground.FrameMeshBuffers(*s) for s in sizes}
+    for i, variant in enumerate(["plain", "dec+cc", "plain", "cc", "dec", "plain"]):
+        size = sizes[i % 2]
+        got = _snapshot(_run_variant(gpu_ctx, buffers[size], frames[size], variant))
+        fresh = _lib.Context(0)
+        want = _snapshot(_run_variant(fresh, foreground.FrameMeshBuffers(*size), frames[size], variant))
+        fresh.close()
+        assert len(want["faces"]) > 20, (variant, size)
+        assert _same(got, want), (i, variant, size)
+
+
+@pytest.mark.parametrize("variant", list(_VARIANTS))
+def test_frame_mesh_of_an_object_without_a_valid_pixel(gpu_ctx, variant):
+    """No pixel of the mask is set: V = F = 0, no texture and no error through every variant; the box is the empty one the scan leaves (INT_MAX, INT_MAX,
+    INT_MIN, INT_MIN), the counts before the clean-up and after the decimation are zero."""
+    import torch
+    from hive_amd import foreground
+    frame = _room_object(45, 67)
+    out = _run_variant(gpu_ctx, foreground.FrameMeshBuffers(45, 67), frame, variant, mask=torch.zeros_like(frame[0][1]))
+    cc, dec = _VARIANTS[variant]
+    print(variant, out["vertices"].shape, out["faces"].shape, out["bbox"], out.get("before"), out.get("decimated"), out.get("decimation_stats"))
+    assert out["vertices"].shape == (0, 3) and out["faces"].shape == (0, 3) and out["uv"].shape == (0, 2) and out["texture"] is None
+    assert out["bbox"] == (2**31 - 1, 2**31 - 1, -2**31, -2**31)
+    assert out.get("before") == ((0, 0) if cc or dec else None)
+    assert out.get("decimated") == ((0, 0) if dec else None)
+
+
+@pytest.mark.parametrize("variant", list(_VARIANTS))
+def test_frame_mesh_buffers_too_small(gpu_ctx, variant):
+    """The result does not fit the declared capacity: ERR_INVALID naming the sizes, and nothing is written past the capacity (the buffers are leading views
+    of larger tensors whose tails hold a sentinel)."""
+    import torch
+    from hive_amd import _lib, foreground
+    h, w, cap = 45, 67, 8
+    frame = _room_object(h, w)
+    full = _run_variant(gpu_ctx, foreground.FrameMeshBuffers(h, w), frame, variant)
+    assert full["vertices"].shape[0] > cap and full["faces"].shape[0] > cap
+    big = foreground.FrameMeshBuffers(h, w)
+    big.vertices.fill_(-7.0), big.faces.fill_(-7), big.uv.fill_(-7)
+    small = foreground.FrameMeshBuffers.__new__(foreground.FrameMeshBuffers)
+    small.shape, small.vertices, small.faces, small.uv = (h, w), big.vertices[:cap], big.faces[:cap], big.uv[:cap]
+    with pytest.raises(_lib.HiveError) as err:
+        _run_variant(gpu_ctx, small, frame, variant)
+    assert err.value.code == _lib.ERR_INVALID and "do not fit" in str(err.value), str(err.value)
+    torch.cuda.synchronize()
+    assert bool((big.vertices[cap:] == -7.0).all()) and bool((big.faces[cap:] == -7).all()) and bool((big.uv[cap:] == -7).all())
