@@ -250,6 +250,16 @@ __global__ __launch_bounds__(256) void dilate_rows_batch_kernel(const uint8_t *_
     out[base + i] = m;
 }
 
+__global__ __launch_bounds__(256) void dilate_cols_batch_kernel(const uint8_t *__restrict__ rows, int H, int W, int r, uint8_t *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= H * W) return;
+    const size_t base = (size_t)blockIdx.y * H * W;
+    const int v = i / W, u = i % W;
+    uint8_t m = 0;
+    for (int vv = max(0, v - r); vv <= min(H - 1, v + r); ++vv) m |= rows[base + (size_t)vv * W + u];
+    out[base + i] = m;
+}
+
 __global__ __launch_bounds__(256) void dilate_cols_apply_kernel(const uint8_t *__restrict__ rows, int H, int W, int r,
                                                                 const float *__restrict__ depth, float *__restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -493,6 +503,28 @@ static int dilate_se_iterate(hive_ctx *ctx, const uint8_t *d_in, int n, int H, i
     *d_result = src;
     return HIVE_OK;
 }
+
+}  // extern "C"
+
+// hive_dilate_mask_se's two paths over a frame set on the device (hive_internal.hpp; inpaint.hip dilates a batch's masks with it)
+int hive_dilate_frames(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, uint8_t *a, uint8_t *b,
+                       const uint8_t **d_result) {
+    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && iterations >= 0, "dilate: bad arguments n=%d %dx%d, %d iterations", n, H, W, iterations);
+    StructuringElement el;
+    int rc = check_se(ctx, se, kh, kw, &el);
+    if (rc) return rc;
+    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), n);
+    if (se_is_full_odd_rect(se, kh, kw) || iterations == 0) {  // (0 iterations: the box of radius 0 = `mask != 0`)
+        hipLaunchKernelGGL(dilate_rows_batch_kernel, grid, dim3(256), 0, ctx->stream, d_mask, H, W, iterations * (kw / 2), 0, a);
+        hipLaunchKernelGGL(dilate_cols_batch_kernel, grid, dim3(256), 0, ctx->stream, (const uint8_t *)a, H, W, iterations * (kh / 2), b);
+        HIVE_CHECK_HIP(ctx, hipGetLastError());
+        *d_result = b;
+        return HIVE_OK;
+    }
+    return dilate_se_iterate(ctx, d_mask, n, H, W, el, iterations, 0, a, b, d_result);
+}
+
+extern "C" {
 
 int hive_dilate_mask_se(hive_ctx *ctx, const uint8_t *mask, int H, int W, const uint8_t *se, int kh, int kw, int iterations, int mem, uint8_t *out) {
     HIVE_ENTER(ctx);

@@ -161,6 +161,10 @@ size_t hive_decimate_scratch_bytes(long long vert_cap, long long face_cap);
 int32_t *hive_decimate_vmap(void *scratch, long long vert_cap, long long face_cap);
 // runs every round (polling the device between batches of rounds) and the output compaction on ctx->stream; stats = {rounds, collapses, locked vertices}
 int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int64_t stats[3]);
+// geometry.hip: hive_dilate_mask_se over n frames on the device (se in host memory).  a, b: two planes of n * H * W bytes; the dilated masks
+// (0 / 1) are left in *d_result, which is one of them
+int hive_dilate_frames(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, uint8_t *a, uint8_t *b,
+                       const uint8_t **d_result);
 // event helpers for kernel timing
 int hive_time_begin(hive_ctx *ctx);
 int hive_time_end(hive_ctx *ctx);

@@ -20,6 +20,7 @@ from hive_amd.depth import estimate_depth_dpt  # noqa: F401  (reference location
 from hive_amd.geometric import Trajectory
 from hive_amd.io import DatasetMetadata, HiveDataset, ImageFolderDataset
 from hive_amd.options import BackgroundMeshOptions, COLMAPOptions, InpaintingMode, PipelineOptions, StorageOptions
+from hive_amd.utils import timed_block
 
 
 class DatasetAdaptor:
@@ -42,6 +43,10 @@ class DatasetAdaptor:
         raise NotImplementedError(f"{type(self).__name__}.convert: this capture format needs stages outside the dense-compute path of "
                                   f"this build (COLMAP / ffmpeg / capture-specific decoding, SURVEY.md section 2 row 11); convert the "
                                   f"sequence with the reference and open the resulting HIVE folder, or use a TUM-layout folder")
+
+    def _inpaint_frame_data(self, mode: InpaintingMode):
+        """Inpaints the RGB frames, depth maps and masks of the converted folder and writes them to disk (dataset_adaptors.py:473-571)."""
+        inpaint_frame_data(self.output_path, mode)
 
 
 class TUMAdaptor(DatasetAdaptor):
@@ -126,8 +131,9 @@ class TUMAdaptor(DatasetAdaptor):
         ``estimate_depth=True`` replaces the sensor depth by DPT-Hybrid estimates (needs the weights file)."""
         if estimate_pose:
             raise NotImplementedError("pose estimation runs COLMAP, which is outside the dense-compute scope")
-        if inpainting_mode != InpaintingMode.Off or static_camera:
-            raise NotImplementedError("inpainting (LaMa / cv2) and the static-camera override are outside the dense-compute scope")
+        if static_camera:
+            raise NotImplementedError("the static-camera override is outside the dense-compute scope")
+        _check_inpainting_mode(inpainting_mode)
         out = self.output_path
         if no_cache and os.path.isdir(out):
             shutil.rmtree(out)
@@ -148,6 +154,8 @@ class TUMAdaptor(DatasetAdaptor):
             estimate_depth_dpt(ImageFolderDataset(pjoin(out, "rgb")), pjoin(out, "depth"))
         np.savetxt(pjoin(out, HiveDataset.camera_matrix_filename), self.intrinsic_matrix)
         Trajectory(self.camera_trajectory.values[:self.num_frames]).save(pjoin(out, HiveDataset.camera_trajectory_filename))
+        with timed_block("Inpainted the frame data in", profiling, ('timing', 'load_dataset', 'inpainting')):  # (dataset_adaptors.py:261-262)
+            self._inpaint_frame_data(mode=inpainting_mode)
         return HiveDataset(out)
 
 
@@ -203,6 +211,93 @@ class StrayScannerAdaptor(VideoAdaptorBase):
         self.depth_confidence_filter_level, self.fix_orientation = depth_confidence_filter_level, fix_orientation
 
 
+INPAINTING_MASK_DILATION = (5, 5, 5)  # `cv2.dilate(mask, np.ones((5, 5)), iterations=5)` (dataset_adaptors.py:501-503)
+INPAINTING_RADIUS = 30                # `cv2.inpaint(image, mask, 30, cv2.INPAINT_TELEA)` (:510)
+
+
+def _check_inpainting_mode(mode: InpaintingMode):
+    if mode & (InpaintingMode.Lama_Image | InpaintingMode.Lama_Depth):
+        raise NotImplementedError(f"inpainting mode {mode.name}: LaMa is a third-party network outside this build; use CV2_Image_Depth "
+                                  f"(--inpainting_mode 1), or inpaint the frames with the reference and open the resulting HIVE folder")
+    if mode != InpaintingMode.Off and mode != InpaintingMode.CV2_Image_Depth:
+        raise RuntimeError(f"The inpainting mode must either be {InpaintingMode.Off} or specify an image and a depth inpainting method, got {mode}.")
+
+
+def _write_png(path, array):
+    Image.fromarray(array).save(path)  # uint8 [H][W] / [H][W][3] -> 8-bit PNG, uint16 [H][W] -> 16-bit PNG
+
+
+def inpaint_frame_data(dataset_path, mode: InpaintingMode, ctx=None, batch_size=32):
+    """``DatasetAdaptor._inpaint_frame_data`` (dataset_adaptors.py:473-571) on a HIVE-format folder: the instance masks are dilated with a 5 x 5
+    element five times, colour and depth are filled under them (radius 30) and written to ``rgb_inpainted/`` and ``depth_inpainted/`` under the
+    file names and bit depths of ``rgb/`` and ``depth/``; ``mask_inpainted/`` gets an all-zero mask per frame (the background then has no
+    dynamic object left to mask, :536-539, :570-571).
+
+    ``Off`` does nothing; ``CV2_Image_Depth`` runs Telea's method on the GPU, ``batch_size`` frames per call, in the level order that
+    ``hive_inpaint_telea`` states (not cv2's heap order: INTEGRATION.md); the three modes with LaMa raise ``NotImplementedError``.  The PNG
+    files of a batch are written by a thread pool while the GPU fills the next one."""
+    mode = InpaintingMode(mode)
+    if mode == InpaintingMode.Off:
+        return
+    _check_inpainting_mode(mode)
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from hive_amd.image_processing import inpaint_frames
+    from hive_amd.utils import usable_cores
+    logging.info("Creating inpainted frame data.")
+    dataset_path = str(dataset_path)
+    folders = {}
+    for name in (HiveDataset.rgb_folder, HiveDataset.depth_folder, HiveDataset.mask_folder):
+        folders[name] = ImageFolderDataset(pjoin(dataset_path, name))
+    rgb_set, depth_set, mask_set = (folders[name] for name in (HiveDataset.rgb_folder, HiveDataset.depth_folder, HiveDataset.mask_folder))
+    if not len(rgb_set) == len(depth_set) == len(mask_set):
+        raise RuntimeError(f"{dataset_path}: {len(rgb_set)} colour frames, {len(depth_set)} depth maps and {len(mask_set)} masks")
+    out_rgb, out_depth, out_mask = (pjoin(dataset_path, name) for name in (HiveDataset.inpainted_rgb_folder, HiveDataset.inpainted_depth_folder,
+                                                                           HiveDataset.inpainted_mask_folder))
+    for folder in (out_rgb, out_depth, out_mask):
+        os.makedirs(folder, exist_ok=True)
+    n = len(rgb_set)
+    device = torch.device("cuda", ctx.device if ctx is not None else torch.cuda.current_device())
+    writers = ThreadPoolExecutor(max_workers=max(1, min(32, usable_cores() - 1)))
+    pending = []
+    try:
+        for start in range(0, n, batch_size):
+            index = range(start, min(n, start + batch_size))
+            rgb = np.stack([np.asarray(rgb_set[i]) for i in index])
+            depth = np.stack([np.asarray(depth_set[i]) for i in index])
+            mask = np.stack([np.asarray(mask_set[i]) for i in index])
+            if mask.ndim == 4:  # a mask stored as a colour image: any channel marks the object
+                mask = mask.max(axis=3)
+            if depth.dtype != np.uint16 or rgb.dtype != np.uint8 or rgb.ndim != 4:
+                raise RuntimeError(f"{dataset_path}: expected 8-bit colour frames and 16-bit depth maps, got {rgb.dtype} {rgb.shape} and {depth.dtype}")
+            filled_rgb, filled_depth = inpaint_frames(torch.from_numpy(rgb).to(device), torch.from_numpy(depth).to(device),
+                                                      torch.from_numpy(np.ascontiguousarray(mask != 0, dtype=np.uint8)).to(device),
+                                                      dilation=INPAINTING_MASK_DILATION, radius=INPAINTING_RADIUS, ctx=ctx)
+            filled_rgb, filled_depth = filled_rgb.cpu().numpy(), filled_depth.cpu().numpy()
+            for done in pending:  # at most two batches of files in flight
+                done.result()
+            pending = []
+            black = np.zeros(mask.shape[1:], np.uint8)
+            for j, i in enumerate(index):
+                pending.append(writers.submit(_write_png, pjoin(out_rgb, rgb_set.image_filenames[i]), filled_rgb[j]))
+                pending.append(writers.submit(_write_png, pjoin(out_depth, depth_set.image_filenames[i]), filled_depth[j]))
+                pending.append(writers.submit(_write_png, pjoin(out_mask, mask_set.image_filenames[i]), black))
+        for done in pending:
+            done.result()
+    finally:
+        writers.shutdown(wait=True)
+
+
+def _open_hive_folder(path, inpainting_mode, profiling=None) -> HiveDataset:
+    """A HIVE folder as it is; with an inpainting mode and no inpainted frames yet, those are made first (the masks come with the folder)."""
+    dataset = HiveDataset(path)
+    if inpainting_mode != InpaintingMode.Off and not dataset.has_inpainted_frame_data:
+        with timed_block("Inpainted the frame data in", profiling, ('timing', 'load_dataset', 'inpainting')):
+            inpaint_frame_data(path, inpainting_mode)
+        dataset = HiveDataset(path)
+    return dataset
+
+
 def get_dataset(storage_options, colmap_options=None, pipeline_options=None, resize_to=640, depth_confidence_filter_level=0, profiling=None,
                 **legacy) -> HiveDataset:
     """Open a HIVE dataset, converting it first if it is in another format (dataset_adaptors.py:1438-1498).
@@ -223,11 +318,11 @@ def get_dataset(storage_options, colmap_options=None, pipeline_options=None, res
     pipeline_options = pipeline_options or PipelineOptions()
     dataset_path, output_path = str(storage_options.dataset_path), str(storage_options.output_path)
     if not storage_options.no_cache and HiveDataset.is_valid_folder_structure(output_path):
-        return HiveDataset(output_path)
+        return _open_hive_folder(output_path, pipeline_options.inpainting_mode, profiling)
     base = dict(base_path=dataset_path, output_path=output_path, num_frames=pipeline_options.num_frames, frame_step=pipeline_options.frame_step,
                 colmap_options=colmap_options)
     if HiveDataset.is_valid_folder_structure(dataset_path):
-        return HiveDataset(dataset_path)
+        return _open_hive_folder(dataset_path, pipeline_options.inpainting_mode, profiling)
     if TUMAdaptor.is_valid_folder_structure(dataset_path):
         converter = TUMAdaptor(**base)
     elif UnrealAdaptor.is_valid_folder_structure(dataset_path):

@@ -379,7 +379,11 @@ class WebXROptions(Options):
 
 class InpaintingMode(enum.Flag):
     """Which inpainter fills the background behind the dynamic objects, for colour and for depth (options.py:530-582).  The five
-    combinations the CLI exposes map to the integers 0..4."""
+    combinations the CLI exposes map to the integers 0..4.
+
+    This build runs ``Off`` and ``CV2_Image_Depth`` (``--inpainting_mode 1``): Telea's method on the GPU for colour and depth
+    (``dataset_adaptors.inpaint_frame_data``, ``hive_inpaint_frames``) -- bit-exact against its stated operation order, not pinned against
+    cv2's heap-ordered implementation.  The three modes with LaMa raise ``NotImplementedError``: LaMa is a third-party network."""
     Off = 0
     CV2_Image = enum.auto()
     CV2_Depth = enum.auto()

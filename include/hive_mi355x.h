@@ -378,6 +378,51 @@ int hive_depth_apply_mask(hive_ctx *ctx, const float *d_depth, const uint8_t *d_
  * (`depth_scale * mm`), `> max_depth -> 0`. */
 int hive_depth_mm_to_m(hive_ctx *ctx, const uint16_t *d_mm, int64_t n, float depth_scale, float max_depth, float *d_out);
 
+/* ---- inpainting behind the dynamic objects -- DatasetAdaptor._inpaint_frame_data, hive/dataset_adaptors.py:473-571, InpaintingMode.CV2_Image_Depth:
+ *      `cv2.inpaint(image, mask, 30, cv2.INPAINT_TELEA)` --------------------------------------------------------------------------------------------
+ * cv2's Telea is a sequential, heap-ordered fast-marching pass; its output is not pinned here.  The specification of record is Telea's
+ * published method (A. Telea, "An Image Inpainting Technique Based on the Fast Marching Method", 2004, eq. 2-3 and the weight of section 2.3), reordered so that
+ * the result does not depend on scheduling, and stated to the bit:
+ *
+ * Inputs.  image u8 [H][W][C], C = 1 or 3, or u16 [H][W]; mask u8 [H][W], non-zero = hole; integer radius eps, 2 <= eps <= 64; H, W <= 4096.  A frame
+ *   without a hole is copied unchanged; a frame without a known pixel is HIVE_ERR_INVALID, and so is eps < 2 (the guarantee below needs the diagonal
+ *   neighbours) or eps > 64.
+ * Distances.  d_in2(p): the exact squared Euclidean distance (an integer) from hole pixel p to the nearest known pixel; d_out2(q): the same from known
+ *   pixel q to the nearest hole pixel.
+ * Level set.  T = sqrt(d_in2) on the hole, T = 1 - sqrt(d_out2) outside, float64.
+ * Levels.  level(p) = the smallest integer L with L * L >= d_in2(p), in integers; known pixels have level 0.  The hole is filled level by level, L = 1, 2, ...
+ *   At level L the USABLE pixels are those of level < L, with their stored values (already rounded to the integer type); pixels of one level never read
+ *   each other.  Every hole pixel has an 8-neighbour of lower level (a unit step towards the nearest known pixel shortens the distance by at least 1), which
+ *   eps >= 2 puts inside the window: the weight sum is never zero, and the number of fill launches is the largest level.
+ * A pixel p = (x, y) of level L.  gT = ((T(x + 1, y) - T(x - 1, y)) / 2, (T(x, y + 1) - T(x, y - 1)) / 2), coordinates clamped to the image.  The window
+ *   offsets are indexed k = (dy + eps) (2 eps + 1) + (dx + eps), q = p + (dx, dy); a term exists for 0 < dx^2 + dy^2 <= eps^2, q inside the image, q usable.
+ *   With r = p - q = (-dx, -dy) as float64 and r2 = dx^2 + dy^2:
+ *     dst = 1 / (r2 * sqrt(r2))
+ *     lev = 1 / (1 + |T(q) - T(p)|)
+ *     dir = |r.x * gT.x + r.y * gT.y|;  dir <= 0.01 -> dir = 1e-6
+ *     w   = (dst * lev) * dir
+ *   per channel, gI(q) along x: (I(qx + 1, qy) - I(qx - 1, qy)) / 2 when both neighbours are inside the image and usable, I(qx + 1, qy) - I(q) or
+ *   I(q) - I(qx - 1, qy) when one is, 0 when none is; along y likewise;
+ *     term = w * (I(q) + (gI.x * r.x + gI.y * r.y))
+ * Sums.  64 partial sums: partial j starts at 0.0 and adds the terms (for s: the weights w) of the offsets k = j, j + 64, j + 128, ... in ascending k.
+ *   Then v[j] = v[j] + v[j + off] for j < off, off = 32, 16, 8, 4, 2, 1; the sum is v[0].  Ia (per channel) and s are summed alike.
+ * Output.  clamp(floor(Ia / s + 0.5), 0, 255 or 65535).  Known pixels are never written.
+ * Arithmetic.  float64 IEEE add, subtract, multiply, divide, sqrt; no fused multiply-add.
+ * Three things differ from cv2: level order instead of heap order, exact distances instead of the eikonal solve, the paper's gradient term
+ * instead of cv2's normalised variant.
+ *
+ * hive_inpaint_telea: one image, `mem` = HIVE_MEM_HOST or HIVE_MEM_DEVICE for image, mask and out alike; bytes_per_sample 1 (channels 1 or 3) or 2 (channels 1).
+ * out may be the image itself (device).  Host calls write nothing to `out` when the frame is refused. */
+int hive_inpaint_telea(hive_ctx *ctx, const void *image, int H, int W, int channels, int bytes_per_sample, const uint8_t *mask, int radius, int mem, void *out);
+/* The frames of a batch at once, device memory: d_rgb u8 [n][H][W][3], d_depth u16 [n][H][W] (either may be NULL, with its output), d_mask u8 [n][H][W].
+ * `d_mask != 0` is first dilated as hive_dilate_mask_se does with a full dilate_kh x dilate_kw element, dilate_iterations times (0 = not at all; the
+ * reference: 5 x 5, 5 times).  Colour and depth share the mask, the levels and the weights; the hole pixels of all frames are sorted by (level, frame, y, x)
+ * and one launch fills a level of every frame, so a batch costs its largest level count in fill launches.  Bit for bit the frames run one by one, and two
+ * hive_inpaint_telea calls per frame.  Outputs may be the inputs.  levels_out (host, optional) i32 [n]: each frame's level count (0 = no hole).
+ * n * H * W < 2^31. */
+int hive_inpaint_frames(hive_ctx *ctx, const uint8_t *d_rgb, const uint16_t *d_depth, const uint8_t *d_mask, int n, int H, int W, int dilate_kh, int dilate_kw,
+                        int dilate_iterations, int radius, uint8_t *d_rgb_out, uint16_t *d_depth_out, int32_t *levels_out);
+
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
  * (x 1/1000 as float32, > max_depth -> 0), optional mask (non-zero -> depth 0, fusion.py:121).
