@@ -59,15 +59,7 @@ __device__ __forceinline__ int bn_swz(int q, int c) { return q * 128 + ((c ^ (q 
 
 __device__ __forceinline__ float bn_dot2(vec<__bf16, 2> a, vec<__bf16, 2> b, float c) { return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false); }
 __device__ __forceinline__ float bn_dot2(vec<_Float16, 2> a, vec<_Float16, 2> b, float c) { return __builtin_amdgcn_fdot2(a, b, c, false); }
-__device__ __forceinline__ float bn_row_total(float v) {  // sum over the 16 lanes of a DPP row, left in every lane
-#define HIVE_ROR_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
-    HIVE_ROR_ADD(0x128);
-    HIVE_ROR_ADD(0x124);
-    HIVE_ROR_ADD(0x122);
-    HIVE_ROR_ADD(0x121);
-#undef HIVE_ROR_ADD
-    return v;
-}
+using hive_mfma::dpp_row_total;  // sum over the 16 lanes of a DPP row, left in every lane
 
 template <typename T>
 __global__ __launch_bounds__(512, 2) void bneck_conv3x3_kernel(BneckParams<T> p) {
@@ -151,10 +143,7 @@ __global__ __launch_bounds__(512, 2) void bneck_conv3x3_kernel(BneckParams<T> p)
         if (tile + (int)gridDim.x < p.n_tiles) fetch(tile + gridDim.x);  // in flight during the MFMAs and the stores below
         // wave w: output rows 2 w, 2 w + 1 of the tile; m fragment mt: row 2 w + (mt >> 1), columns 16 (mt & 1) .. + 15
         f32x4 acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        hive_mfma::zero_acc(acc);
 #pragma unroll 1
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - ky * 3;
@@ -209,8 +198,8 @@ __global__ __launch_bounds__(512, 2) void bneck_conv3x3_kernel(BneckParams<T> p)
                     }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    sv[e] = bn_row_total(sv[e]);
-                    qv[e] = bn_row_total(qv[e]);
+                    sv[e] = dpp_row_total(sv[e]);
+                    qv[e] = dpp_row_total(qv[e]);
                 }
                 if (fr == 0) {
                     const int ch = (nt >> 1) * 32 + fq * 8 + (nt & 1) * 4;
@@ -234,10 +223,10 @@ __global__ __launch_bounds__(512, 2) void bneck_conv3x3_kernel(BneckParams<T> p)
 template <typename T>
 int launch_bneck(hive_ctx *ctx, const void *d_x, int N, int H, int W, const float *stats, const void *gamma, const void *beta, const void *d_w, void *d_out,
                  float *d_gn_partial, long long gn_partial_floats, int *gn_tile_rows) {
-    static bool attr_set[64] = {};
-    if (!(ctx->device < 64 && attr_set[ctx->device])) {
+    static hive_device_latch latch;
+    if (!latch.done(ctx)) {
         HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)bneck_conv3x3_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, BN_LDS));
-        if (ctx->device < 64) attr_set[ctx->device] = true;
+        latch.mark(ctx);
     }
     BneckParams<T> p{};
     p.x = (const T *)d_x;

@@ -23,7 +23,7 @@
 // out again: a deep LDS ring (K-step 32, 3 / 4 / 5 stages of 32 KiB in flight, counted vmcnt) -- 725-780 TFLOP/s whatever the
 // depth, i.e. the fill latency is NOT what bounds the K-step, and the second barrier per 64 k costs 13 %.  What does bound it: a CU's
 // vector-memory path moves one 64-byte line per ~2.3 cycles (tools/ubench/gather.hip, ldsdma.hip), so the 64 KiB of a 256 x 256 x 64
-// stage take 2550+ cycles to arrive against 2048 cycles of MFMA -- per-workgroup clocks (tools/probe_gemm_stamps.py) show 2100 busy +
+// stage take 2550+ cycles to arrive against 2048 cycles of MFMA -- per-workgroup phase clocks (round 5: DESIGN_LOG.md) show 2100 busy +
 // 800 waiting cycles per K-step.  Also tried and taken out: start delays that de-phase the persistent workgroups (so that their
 // epilogues' stores do not hit HBM together): no change where the delay is free (workgroups with one tile fewer), slower elsewhere.
 // And a timing experiment that settles what a smarter A path could buy (an LDS-resident pixel window re-used by the 9 taps): with
@@ -34,17 +34,8 @@
 
 #include <algorithm>
 
-// tuning builds only (make ablate_conv; tools/probe_resnet.py): phases of conv_kernel left out -- 1: the epilogue's turn through LDS and its
-// stores, 2: the MFMAs (the stage pieces are still issued), 4: the LDS-DMA, 8: the GroupNorm sums' reduction and their store
-#ifndef HIVE_CONV_AHEAD_GN2
-#define HIVE_CONV_AHEAD_GN2 4  // the same for the second pass of the two-pass GroupNorm convolutions (fewer live registers there)
-#endif
-#ifndef HIVE_CONV_ABLATE
-#define HIVE_CONV_ABLATE 0
-#endif
-#ifndef HIVE_CONV_AHEAD
-#define HIVE_CONV_AHEAD 4  // fragment rows the shortcut loads of the epilogue run ahead (ONE shortcut; with two: half as many)
-#endif
+constexpr int HIVE_CONV_AHEAD = 4;      // fragment rows the shortcut loads of the epilogue run ahead (ONE shortcut; with two: half as many)
+constexpr int HIVE_CONV_AHEAD_GN2 = 4;  // the same for the second pass of the two-pass GroupNorm convolutions (fewer live registers there)
 
 using hive_mfma::f32x4;
 using hive_mfma::vec;  // vec<T, 8>: 8 elements of the 16-bit type T (__bf16 or _Float16), one 16-byte register quad
@@ -198,15 +189,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams<T> &p, f32x4 (&ac
 // below `boundary`) and second image -- written AFTER the epilogue's stores (the accumulators are still there; the wave's 4 KiB of LDS is free).
 __device__ __forceinline__ float dot2acc(vec<__bf16, 2> a, vec<__bf16, 2> b, float c) { return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false); }
 __device__ __forceinline__ float dot2acc(vec<_Float16, 2> a, vec<_Float16, 2> b, float c) { return __builtin_amdgcn_fdot2(a, b, c, false); }
-__device__ __forceinline__ float dpp_row_total(float v) {
-#define HIVE_ROR_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
-    HIVE_ROR_ADD(0x128);  // row_ror:8
-    HIVE_ROR_ADD(0x124);
-    HIVE_ROR_ADD(0x122);
-    HIVE_ROR_ADD(0x121);
-#undef HIVE_ROR_ADD
-    return v;
-}
+using hive_mfma::dpp_row_total;
 template <typename T, int MT>
 __device__ __forceinline__ void gn_sums_from_acc(const ConvParams<T> &p, const f32x4 (&acc)[4][MT], int m_base, int n_base, int lane, int boundary,
                                                  float *wsum) {
@@ -306,8 +289,8 @@ __global__ __launch_bounds__(512, 1) void conv_kernel(ConvParams<T> p) {
     // K-step of the current one and lands while its epilogue runs -- what the 1 x 1 convolutions of the ResNet stages need
     // (K = 64 .. 1024: one to sixteen K-steps per tile, then 64-128 KiB of output to store).
     const int tiles_n = p.Cout / TN, n_tiles = ((p.M + TM - 1) / TM) * tiles_n;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3, tq = n_tiles >> 3, tr = n_tiles & 7;
-    const int run0 = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq, run_n = tq + (xcd < tr ? 1 : 0);
+    int run0, run_n, per_xcd;
+    hive_mfma::xcd_run(n_tiles, run0, run_n, per_xcd);
     int tl = blockIdx.x >> 3;  // position in the XCD's run
     if (tl >= run_n) return;   // (whole workgroup)
     const int K = p.taps * p.Cin, CPT = p.Cin / BK;  // CPT: K-steps (channel blocks) per tap
@@ -345,7 +328,6 @@ __global__ __launch_bounds__(512, 1) void conv_kernel(ConvParams<T> p) {
     // one LDS-DMA wave-instruction of a stage: j < A_PW an A group (8 output pixels x 128 B of one tap), else a W group
     auto issue_piece = [&](const Tile &tile, int stage, int tap, int cc, int j) {
         unsigned char *st = lds + stage * STAGE_BYTES;
-        if (HIVE_CONV_ABLATE & 4) return;
         if (j < A_PW) {
             const int dy = tap / p.S, dx = tap - dy * p.S;
             const long long shift = ((long long)dy * p.W + dx) * p.Cin + cc * BK;
@@ -402,22 +384,18 @@ __global__ __launch_bounds__(512, 1) void conv_kernel(ConvParams<T> p) {
             }
             if (++nx_tap == p.taps) nx_tap = 0, ++nx_cc;
             const unsigned char *a_t = lds + buf * STAGE_BYTES, *w_t = a_t + A_GROUPS * 1024;
-            if (HIVE_CONV_ABLATE & 2) {
-                for (int j = 0; j < PER_WAVE; ++j) issue_piece(tile, buf ^ 1, is_tap, is_cc, j);
-            } else {
-                hive_mfma::kstep64<T, MT, false>(a_t, w_t, wr * RW, wc * 64, fr, fq, acc, PER_WAVE, [&](int j) { issue_piece(tile, buf ^ 1, is_tap, is_cc, j); });
-            }
+            hive_mfma::kstep64<T, MT, false>(a_t, w_t, wr * RW, wc * 64, fr, fq, acc, PER_WAVE, [&](int j) { issue_piece(tile, buf ^ 1, is_tap, is_cc, j); });
             buf ^= 1;
         }
         unsigned char *stage = lds + 2 * STAGE_BYTES + wave * 4096;
         const int hw = p.Ho * p.Wo, boundary = (em0 / hw + 1) * hw;  // first row of the tile's second image
-        if (!(HIVE_CONV_ABLATE & 1) && !(GN == 1 && p.stats_only)) {
+        if (!(GN == 1 && p.stats_only)) {
             if (GN == 0 && p.res2)  // (kernel-uniform) both skip connections
                 conv_epilogue<T, MT, GN, 2>(p, acc, em0 + wr * RW, en0 + wc * 64, stage, lane, boundary);
             else
                 conv_epilogue<T, MT, GN, 1>(p, acc, em0 + wr * RW, en0 + wc * 64, stage, lane, boundary);
         }
-        if (GN == 1 && !(HIVE_CONV_ABLATE & 8)) {
+        if (GN == 1) {
             __builtin_amdgcn_wave_barrier();  // behind the epilogue's last reads of this LDS
             gn_sums_from_acc<T, MT>(p, acc, em0 + wr * RW, en0 + wc * 64, lane, boundary, reinterpret_cast<float *>(stage));
             __syncthreads();
@@ -459,8 +437,8 @@ __global__ __launch_bounds__(512, 1) void conv_deep_kernel(ConvParams<T> p) {
     const int wr = wave / WN, wc = wave % WN;
     const int S = p.split_k, KT = p.taps * (p.Cin / BK);
     const int tiles_n = p.Cout / TN, n_items = ((p.M + TM - 1) / TM) * tiles_n * S;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3, tq = n_items >> 3, tr = n_items & 7;
-    const int run0 = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq, run_n = tq + (xcd < tr ? 1 : 0);
+    int run0, run_n, per_xcd;
+    hive_mfma::xcd_run(n_items, run0, run_n, per_xcd);
     int tl = blockIdx.x >> 3;  // position in the XCD's run of items
     if (tl >= run_n) return;   // (whole workgroup)
 
@@ -597,8 +575,8 @@ constexpr int CONV_DEEP_NST = 4;  // 4 x 32 KiB of stages + 32 KiB for the epilo
 
 template <typename T>
 int ensure_conv_attrs(hive_ctx *ctx) {
-    static bool set[64] = {};
-    if (ctx->device < 64 && set[ctx->device]) return HIVE_OK;
+    static hive_device_latch latch;
+    if (latch.done(ctx)) return HIVE_OK;
 #define HIVE_CONV_ATTR(TM_, TN_, GN_) \
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)conv_kernel<T, TM_, TN_, GN_>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_lds(TM_, TN_)))
     HIVE_CONV_ATTR(256, 256, 0);
@@ -616,7 +594,7 @@ int ensure_conv_attrs(hive_ctx *ctx) {
 #undef HIVE_CONV_ATTR
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)conv_deep_kernel<T, 128, 0, CONV_DEEP_NST>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_lds(128, 128, CONV_DEEP_NST)));
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)conv_deep_kernel<T, 128, 1, CONV_DEEP_NST>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_lds(128, 128, CONV_DEEP_NST)));
-    if (ctx->device < 64) set[ctx->device] = true;
+    latch.mark(ctx);
     return HIVE_OK;
 }
 

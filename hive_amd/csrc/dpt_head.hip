@@ -39,12 +39,6 @@
 using hive_mfma::f32x16;
 using hive_mfma::vec;  // T = __bf16 or _Float16 (the reference's model.half()): v_mfma_f32_32x32x16_{bf16,f16}
 
-// tuning builds only (make -C hive_amd/csrc ablate): bit mask of phases left out of head_conv_kernel, to read what each costs from
-// tools/probe_head.py (1 = low-resolution patch load, 2 = upsampled patch, 4 = MFMA loop, 8 = partial-sum exchange).  0 in the library.
-#ifndef HIVE_HEAD_ABLATE
-#define HIVE_HEAD_ABLATE 0
-#endif
-
 namespace {
 
 constexpr int TH = 8, TW = 16;                 // output tile
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void head_conv_kernel(HeadParams<T> p) {
         }
     };
     static_assert(LO_DMA % 4 == 0, "pieces per wave");
-    if (!(HIVE_HEAD_ABLATE & 1) && (int)blockIdx.x < n_tiles) issue_lo(blockIdx.x);
+    if ((int)blockIdx.x < n_tiles) issue_lo(blockIdx.x);
 
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int tx = tile % tiles_x;
@@ -156,10 +150,10 @@ __global__ __launch_bounds__(256, 2) void head_conv_kernel(HeadParams<T> p) {
         // horizontal terms t(r) = w0 * v(r, x0) + w1 * v(r, x1) of a low-resolution row r are computed once and kept in registers for the
         // two or three output rows that use them (same values, 43 % fewer flops and LDS reads than per pixel).
         // Pass 2, the two halo columns 16, 17: 32 (column, vector) items -- walked like pass 1 they kept half a wave busy for as long as all
-        // of pass 1 (this phase was HALF of the kernel's time: ablation builds, tools/probe_head.py); as 320 independent (item, row) units they
+        // of pass 1 (this phase was HALF of the kernel's time: timing builds with one phase left out, tools/probe_head.py); as 320 independent (item, row) units they
         // take 1 - 2 short steps per thread.
         const uint4 zero = make_uint4(0u, 0u, 0u, 0u);  // zero padding of the convolution
-        if (!(HIVE_HEAD_ABLATE & 2)) {
+        {
             const int v = tid & 15, ux = tid >> 4, ox = C0 + ux;
             const bool col_ok = ox >= 0 && ox < OW;
             const float fx = sw * (float)ox;
@@ -225,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void head_conv_kernel(HeadParams<T> p) {
         }
         __syncthreads();
         // nobody reads `lo` any more: the next tile's patch streams in under phases (c), (d) and the epilogue
-        if (!(HIVE_HEAD_ABLATE & 1) && tile + (int)gridDim.x < n_tiles) issue_lo(tile + gridDim.x);
+        if (tile + (int)gridDim.x < n_tiles) issue_lo(tile + gridDim.x);
         // (c) 9 taps x 2 k-steps x 4 pixel tiles of 32 (tile m = output rows 2m, 2m+1 of the 8 x 16 patch)
         f32x16 acc[4];
 #pragma unroll
@@ -234,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void head_conv_kernel(HeadParams<T> p) {
             for (int v = 0; v < 16; ++v) acc[m][v] = 0.f;
         const int pix_base = (nn >> 4) * UP_PITCH + (nn & 15) * PIX + (32 * wave + 8 * hh) * 2;
 #pragma unroll
-        for (int t = 0; t < ((HIVE_HEAD_ABLATE & 4) ? 0 : 9); ++t) {
+        for (int t = 0; t < 9; ++t) {
             const int tap_off = (t / 3) * UP_PITCH + (t % 3) * PIX;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void head_conv_kernel(HeadParams<T> p) {
         typedef hive_mfma::f32x4 f32x4;
         f32x4 *part = reinterpret_cast<f32x4 *>(up);
 #pragma unroll
-        for (int m = 0; m < ((HIVE_HEAD_ABLATE & 8) ? 0 : 4); ++m)
+        for (int m = 0; m < 4; ++m)
             if (wave != m) {
                 const int slot = wave < m ? wave : wave - 1;
 #pragma unroll
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void head_conv_kernel(HeadParams<T> p) {
         for (int g = 0; g < 4; ++g) {  // registers 4g .. 4g+3 = output channels 8g + 4hh .. + 3 of pixel nn
             f32x4 sum = f32x4{mine[4 * g], mine[4 * g + 1], mine[4 * g + 2], mine[4 * g + 3]};
 #pragma unroll
-            for (int slot = 0; slot < ((HIVE_HEAD_ABLATE & 8) ? 0 : 3); ++slot) sum += part[((wave * 3 + slot) * 4 + g) * 64 + lane];
+            for (int slot = 0; slot < 3; ++slot) sum += part[((wave * 3 + slot) * 4 + g) * 64 + lane];
             const f32x4 b3q = *reinterpret_cast<const f32x4 *>(tab + 8 * g + 4 * hh);
             const f32x4 w1q = *reinterpret_cast<const f32x4 *>(tab + COUT + 8 * g + 4 * hh);
 #pragma unroll
@@ -314,11 +308,11 @@ int launch_head(hive_ctx *ctx, const void *d_x, const float *d_b0, int N, int H,
     p.out_depth = d_depth;
     p.out_mm = d_out_mm;
     p.out_m = d_out_m;
-    static bool attr_set[64] = {};
+    static hive_device_latch latch;
     const int lds = UP_BYTES + LO_BYTES + 2 * COUT * (int)sizeof(float);
-    if (ctx->device >= 64 || !attr_set[ctx->device]) {
+    if (!latch.done(ctx)) {
         HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)head_conv_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        if (ctx->device < 64) attr_set[ctx->device] = true;
+        latch.mark(ctx);
     }
     const long long tiles = (long long)N * ((2 * H + TH - 1) / TH) * ((2 * W + TW - 1) / TW);
     const dim3 grid((unsigned)std::min<long long>(tiles, (long long)ctx->num_cus * 2));

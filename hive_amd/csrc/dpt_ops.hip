@@ -647,11 +647,15 @@ int hive_nhwc_upsample2x(hive_ctx *ctx, const void *d_in, const void *d_bias, in
     const size_t lds = (size_t)(UP_TY + 2) * (UP_TX + 2) * C * 2;
     if (C <= 512 && !gather_only && (H + UP_TY - 1) / UP_TY <= 65535) {  // through an LDS tile
         const dim3 tiles((unsigned)((W + UP_TX - 1) / UP_TX), (unsigned)((H + UP_TY - 1) / UP_TY), (unsigned)N);
-        if (dtype == HIVE_BF16) {
+        static hive_device_latch latch;
+        if (!latch.done(ctx)) {
             HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)upsample2x_lds_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+            HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)upsample2x_lds_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+            latch.mark(ctx);
+        }
+        if (dtype == HIVE_BF16) {
             hipLaunchKernelGGL(upsample2x_lds_kernel<bf16>, tiles, dim3(256), lds, ctx->stream, (const bf16 *)d_in, (const bf16 *)d_bias, (bf16 *)d_out, N, H, W, C);
         } else if (dtype == HIVE_F16) {
-            HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)upsample2x_lds_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
             hipLaunchKernelGGL(upsample2x_lds_kernel<_Float16>, tiles, dim3(256), lds, ctx->stream, (const _Float16 *)d_in, (const _Float16 *)d_bias, (_Float16 *)d_out,
                                N, H, W, C);
         } else {

@@ -279,10 +279,10 @@ __global__ __launch_bounds__(256) void gram_finalize_kernel(const float *__restr
 template <typename T, int CIN, int NW>
 int launch_gram(hive_ctx *ctx, const GramParams<T> &p, int chunks, int N) {
     constexpr int lds = CIN == 64 ? 4 * (2048 + 64) * 4 : 2 * (CIN / 64) * 128 * 128;  // two tiles; C_in = 64: also half of the four waves' partial sums (33 792 bytes)
-    static bool set[64] = {};
-    if (!(ctx->device < 64 && set[ctx->device])) {
+    static hive_device_latch latch;
+    if (!latch.done(ctx)) {
         HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gram_kernel<T, CIN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        if (ctx->device < 64) set[ctx->device] = true;
+        latch.mark(ctx);
     }
     hipLaunchKernelGGL((gram_kernel<T, CIN, NW>), dim3(chunks, N), dim3(NW * 64), lds, ctx->stream, p);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
@@ -328,10 +328,10 @@ int gram_stats_t(hive_ctx *ctx, const void *d_x, int N, int H, int W, int C_in, 
         HIVE_CHECK_HIP(ctx, hipMemcpyAsync(d_s_out, p.s, (size_t)N * parts * C_in * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
     const size_t quad_lds = ((size_t)G * QUAD_KL + QUAD_NS * (QUAD_KL + 1)) * sizeof(float);
-    static bool qset[64] = {};
-    if (!(ctx->device < 64 && qset[ctx->device])) {
+    static hive_device_latch quad_latch;
+    if (!quad_latch.done(ctx)) {
         HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gram_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)64 * QUAD_KL + QUAD_NS * (QUAD_KL + 1)) * sizeof(float))));
-        if (ctx->device < 64) qset[ctx->device] = true;
+        quad_latch.mark(ctx);
     }
     hipLaunchKernelGGL(gram_quad_kernel, dim3(KC, (N + QUAD_NS - 1) / QUAD_NS), dim3(256), quad_lds, ctx->stream, p.S, d_tables, N, parts, CC, G, KC, Q);
     hipLaunchKernelGGL(gram_finalize_kernel, dim3(N), dim3(256), 0, ctx->stream, Q, p.s, d_tables + (size_t)G * CC, G, C_in, parts, KC, (double)HW * cpg, eps, d_stats);

@@ -55,7 +55,8 @@ struct hive_ctx {
     void *d_gram = nullptr;  // partial Gram matrices / sums / quadratic forms of gram.hip (GroupNorm statistics of 1 x 1 convolutions)
     size_t gram_bytes = 0;
 
-    // hive_ctx_set_deterministic: no split-K, no Gram-matrix GroupNorm statistics (the two paths whose use depends on the batch size and the CU count)
+    // hive_ctx_set_deterministic: no split-K, no key split inside the attention workgroup, no Gram-matrix GroupNorm statistics (the three paths whose use
+    // depends on the batch size and the CU count)
     bool deterministic = false;
     // launches of the small-launch paths since creation / the last reset (hive_ctx_launch_stats): split-K items, four-stage-ring kernels
     int64_t n_splitk_launches = 0, n_deep_ring_launches = 0;
@@ -101,6 +102,16 @@ void hive_set_global_error(const char *msg);
     do {                                                               \
         if (!(cond)) return hive_fail((ctx), HIVE_ERR_INVALID, __VA_ARGS__); \
     } while (0)
+
+// Once per device: the latch of a launcher's hipFuncSetAttribute block (a function-local static: hipFuncAttributeMaxDynamicSharedMemorySize is a property of
+// the kernel ON a device).  `if (!latch.done(ctx)) { ... set the attributes ...; latch.mark(ctx); }`; devices past 63 set them every time.
+struct hive_device_latch {
+    bool set[64] = {};
+    bool done(const hive_ctx *ctx) const { return ctx->device < 64 && set[ctx->device]; }
+    void mark(const hive_ctx *ctx) {
+        if (ctx->device < 64) set[ctx->device] = true;
+    }
+};
 
 // grows *ptr to at least `bytes` of device memory
 int hive_reserve_device(hive_ctx *ctx, void **ptr, size_t *cur, size_t bytes);

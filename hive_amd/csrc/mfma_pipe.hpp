@@ -35,14 +35,10 @@ __device__ __forceinline__ f32x16 mfma32(vec<_Float16, 8> a, vec<_Float16, 8> b,
 // One LDS-DMA wave instruction (64 lanes x 16 B, lane-linear, to the wave-uniform LDS address lds_dst) outside the compiler's wait-count bookkeeping.  The rings
 // deeper than two stages count vmcnt BY HAND (s_waitcnt vmcnt(pieces of the younger stages)): any wait hipcc adds inside the K loop on its own account
 // drains the ring every step, silently (it shows only in the ISA).  The one such wait found here came from ordinary loads (see the builtin s_waitcnt behind the
-// deep kernels' epilogues); hipcc 7.2 did not add one for the builtin LDS-DMA itself in these kernels (-DHIVE_LDSDMA_TRACKED builds them that way: same ISA
-// waits), but it can (the CDNA4 guide reports an s_waitcnt vmcnt(0) in front of the first ds_read of every K-step once a second LDS object exists), so the
-// deep rings keep their pieces out of its books altogether.  M0 holds the LDS base and is compiler-reserved: saved, set, put back (the guide's recipe).
+// deep kernels' epilogues); hipcc 7.2 did not add one for the builtin LDS-DMA itself in these kernels (a round-5 build that issued these pieces with
+// __builtin_amdgcn_global_load_lds instead had the same ISA waits), but it can (the CDNA4 guide reports an s_waitcnt vmcnt(0) in front of the first ds_read of
+// every K-step once a second LDS object exists), so the deep rings keep their pieces out of its books altogether.  M0 holds the LDS base and is compiler-reserved: saved, set, put back (the guide's recipe).
 __device__ __forceinline__ void lds_dma16_untracked(const void *gsrc, unsigned lds_dst) {
-#ifdef HIVE_LDSDMA_TRACKED  // (tuning build: the compiler's own LDS-DMA)
-    __builtin_amdgcn_global_load_lds(gsrc, (__attribute__((address_space(3))) void *)(size_t)lds_dst, 16, 0, 0);
-    return;
-#endif
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
@@ -52,6 +48,36 @@ __device__ __forceinline__ unsigned lds_address(const void *p) { return (unsigne
 // byte offset of 16-byte chunk `c` (0..7) of row `r` in a tile with 128-byte rows: the chunk is XORed with (r >> 1) & 7 so that
 // any 16 consecutive rows at one chunk index land on 16 distinct 16-byte slots
 __device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+
+// v += the value DPP control CTRL selects from another lane of the 16-lane row (quad_perm, row_ror, row_half_mirror ...): on the VALU, where the
+// ds_bpermute behind __shfl_xor goes through the LDS pipe
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// sum over the 16 lanes of a DPP row, left in all of them: row_ror 8, 4, 2, 1
+__device__ __forceinline__ float dpp_row_total(float v) { return dpp_add<0x121>(dpp_add<0x122>(dpp_add<0x124>(dpp_add<0x128>(v)))); }
+
+// acc[i][j] = 0 for the R x C accumulators of a wave.  (stem.hip, bneck.hip and splitk_combine below; the persistent GEMM and convolution kernels keep
+// their own loops: with this call in them, inlined though it is, hipcc 7.2 emits other machine code for them.)
+template <int R, int C>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[R][C]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < C; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// The run of items (tiles, or tiles x split-K ways) of a PERSISTENT workgroup, XCD-aware: the grid is a multiple of 8, workgroups are dealt round-robin over
+// the 8 XCDs, each XCD owns a contiguous run [run0, run0 + run_n) of the n items (neighbours share operands in that XCD's L2) and its per_xcd workgroups
+// walk it from blockIdx.x >> 3 with a stride of per_xcd.  (Three plain ints, not a struct returned by value: with that form hipcc 7.2 emits other machine
+// code for the kernels.)
+__device__ __forceinline__ void xcd_run(int n, int &run0, int &run_n, int &per_xcd) {
+    const int xcd = blockIdx.x & 7, tq = n >> 3, tr = n & 7;
+    per_xcd = gridDim.x >> 3;
+    run0 = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+    run_n = tq + (xcd < tr ? 1 : 0);
+}
 
 // SWAP = false: acc[nt][mt] += W_frag[nt] . A_frag[mt]^T (rows = W rows: a lane owns 4 consecutive W rows of one A row)
 // SWAP = true : acc[mt][nt] += A_frag[mt] . W_frag[nt]^T (MT == 4 only: the transposed v^T store of the QKV GEMM)
@@ -95,10 +121,8 @@ __device__ __forceinline__ void kstep64(const unsigned char *a_t, const unsigned
 // fragments are in registers), and the next step, after the barrier, first issues its fragment reads (`begin`), then runs the
 // held-back MFMAs under that latency (`flush`), then its own slots (`body`).  Per tile: begin/body for the first step, barrier +
 // begin/flush/body for the others, one flush before the epilogue.
-#ifndef HIVE_PIPE_ABLATE_READS
-#define HIVE_PIPE_ABLATE_READS 0  // tuning build (make ablate_reads; WRONG results): 1 = a third of KPipe's fragment reads left out -- what a 128 x 128-per-wave register
-                                  // blocking would save of the LDS port's 192 KiB per K-step -- to see whether the K loop is LDS-port-bound before building that kernel
-#endif
+// (Round 5, a timing build with WRONG results: a third of KPipe's fragment reads left out -- what a 128 x 128-per-wave register blocking would save of the LDS
+// port's 192 KiB per K-step -- to see whether the K loop is LDS-port-bound before building that kernel.  It is not: within 2 %.)
 template <typename T, int MT, bool SWAP>
 struct KPipe {
     typedef vec<T, 8> frag;
@@ -110,11 +134,9 @@ struct KPipe {
     int a_row0, w_row0, fr, fq;
 
     __device__ __forceinline__ frag rd_a(int sl) const {
-        if (HIVE_PIPE_ABLATE_READS && sl >= MT + MT / 2) return wfr[0][sl & 3];  // (timing experiment: no LDS read for the second half of sub-step 1's A fragments)
         return *reinterpret_cast<const frag *>(a_t + swz(a_row0 + (sl % MT) * 16 + fr, (sl / MT) * 4 + fq));
     }
     __device__ __forceinline__ frag rd_w(int sub, int t) const {
-        if (HIVE_PIPE_ABLATE_READS && sub == 1) return wfr[0][t];  // (timing experiment: sub-step 1 reuses sub-step 0's W fragments)
         return *reinterpret_cast<const frag *>(w_t + swz(w_row0 + t * 16 + fr, sub * 4 + fq));
     }
     template <typename Acc>
@@ -162,7 +184,7 @@ struct KPipe {
 
 // Epilogue of the SWAP = false accumulators through LDS.  In the MFMA layout a lane owns 4 consecutive W rows (output columns) of
 // one A row, so a direct store writes 16 rows x 32 bytes per wave-instruction, 8 bytes per lane.  A CU's vector-memory path takes a
-// wave-instruction every 40-47 cycles whatever its width (per-workgroup clocks, tools/probe_gemm_stamps.py: 23 000 cycles for the
+// wave-instruction every 40-47 cycles whatever its width (per-workgroup phase clocks, round 5 -- DESIGN_LOG.md: 23 000 cycles for the
 // 8 x 32 such stores of a 256 x 256 tile -- as long as 8 of the tile's 12 K-steps at K = 768), so the epilogue wants FEW, WIDE
 // instructions on whole lines.  Each wave turns one 16-row fragment row (16 x 64 f32 = 4 KiB) around in a PRIVATE 4 KiB of LDS:
 // ds_write_b128 in the MFMA layout, two ds_read_b128 with 8 lanes along a row; `finish(row, col, lo, hi)` then gets 8 consecutive
@@ -254,10 +276,7 @@ __device__ __forceinline__ bool splitk_combine(int S, f32x4 *ws, unsigned *count
     const bool last = *flag == S - 1;
     __syncthreads();  // (the caller's epilogue reuses flag's LDS)
     if (!last) return false;
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-#pragma unroll
-        for (int j = 0; j < C; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     const f32x4 *src = ws + (size_t)tile * S * (R * C * NT) + tid;
     for (int s = 0; s < S; ++s, src += R * C * NT) {
 #pragma unroll

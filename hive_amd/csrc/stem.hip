@@ -21,9 +21,6 @@ using hive_mfma::vec;  // T = __bf16 or _Float16 (the reference's model.half())
 
 namespace {
 
-#ifndef HIVE_STEM_ABLATE
-#define HIVE_STEM_ABLATE 0  // tuning builds: 1 no output stores, 2 no patch loads, 4 no MFMAs
-#endif
 constexpr int ST_TH = 8, ST_TW = 32;                      // output tile
 constexpr int ST_PH = 2 * ST_TH + 5, ST_PW = 2 * ST_TW + 5;  // input patch 21 x 69 pixels
 constexpr int ST_ROW = 240;                               // patch row pitch in elements (69 x 3 = 207, + slack for the 32-wide k-steps; 480 B)
@@ -48,15 +45,7 @@ struct StemParams {
 
 __device__ __forceinline__ float stem_dot2(vec<__bf16, 2> a, vec<__bf16, 2> b, float c) { return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false); }
 __device__ __forceinline__ float stem_dot2(vec<_Float16, 2> a, vec<_Float16, 2> b, float c) { return __builtin_amdgcn_fdot2(a, b, c, false); }
-__device__ __forceinline__ float stem_row_total(float v) {  // sum over the 16 lanes of a DPP row, left in every lane
-#define HIVE_ROR_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
-    HIVE_ROR_ADD(0x128);
-    HIVE_ROR_ADD(0x124);
-    HIVE_ROR_ADD(0x122);
-    HIVE_ROR_ADD(0x121);
-#undef HIVE_ROR_ADD
-    return v;
-}
+using hive_mfma::dpp_row_total;  // sum over the 16 lanes of a DPP row, left in every lane
 
 // PERSISTENT workgroups (as many as fit: 3 per CU by LDS): the weights go to LDS once; per tile the patch of the NEXT tile is loaded into
 // registers (dwords: a patch row is 414 contiguous bytes of the frame, 4-byte aligned when W and the left padding are even -- `fast`;
@@ -98,10 +87,7 @@ __global__ __launch_bounds__(256, 3) void stem_conv_kernel(StemParams<T> p) {  /
         const int iy0 = 2 * oy0 - p.pad_t, ix0 = 2 * ox0 - p.pad_l;
         const T *xin = p.x + (size_t)img * p.H * p.W * 3;
         const bool inside = iy0 >= 0 && iy0 + ST_PH <= p.H && ix0 >= 0 && ix0 + (2 * ST_RD + 2) / 3 <= p.W;  // (workgroup-uniform)
-        if (HIVE_STEM_ABLATE & 2) {
-#pragma unroll
-            for (int k = 0; k < ST_LOADS; ++k) regs[k] = u4{0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};
-        } else if (even && inside) {
+        if (even && inside) {
             const uint32_t *base = reinterpret_cast<const uint32_t *>(xin + ((size_t)iy0 * p.W + ix0) * 3);
             const int row_dwords = p.W * 3 / 2;
 #pragma unroll
@@ -164,10 +150,7 @@ __global__ __launch_bounds__(256, 3) void stem_conv_kernel(StemParams<T> p) {  /
         const int oy0 = (t / p.tiles_x) * ST_TH, ox0 = (t % p.tiles_x) * ST_TW;
         // wave w: output rows 2 w, 2 w + 1 of the tile; m fragment mt: row 2 w + (mt >> 1), columns 16 (mt & 1) .. + 15
         f32x4 acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        hive_mfma::zero_acc(acc);
 #pragma unroll 1  // (unrolled, the compiler reads all seven kernel rows' fragments ahead: 247 registers, or 82 spilled at three waves per SIMD)
         for (int ky = 0; ky < 7; ++ky) {
             vec<T, 8> wf[4], af[4];
@@ -185,19 +168,14 @@ __global__ __launch_bounds__(256, 3) void stem_conv_kernel(StemParams<T> p) {  /
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    if (HIVE_STEM_ABLATE & 4)
-                        acc[nt][mt][0] += (float)wf[nt][0] + (float)af[mt][0];
-                    else
-                        acc[nt][mt] = hive_mfma::mfma16(wf[nt], af[mt], acc[nt][mt]);
-                }
+                for (int nt = 0; nt < 4; ++nt) acc[nt][mt] = hive_mfma::mfma16(wf[nt], af[mt], acc[nt][mt]);
         }
         // a lane owns channels 32 a + 8 fq .. + 7 (a = 0, 1: accumulators nt = 2 a, 2 a + 1) of pixel (2 w + (mt >> 1), 16 (mt & 1) + fr)
         T *out = p.out + (size_t)img * p.Ho * p.Wo * 64;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             const int oy = oy0 + 2 * wave + (mt >> 1), ox = ox0 + 16 * (mt & 1) + fr;
-            if (oy < p.Ho && ox < p.Wo && (!(HIVE_STEM_ABLATE & 1) || acc[0][mt][0] == 12345.678f)) {
+            if (oy < p.Ho && ox < p.Wo) {
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     vec<T, 8> ov;
@@ -229,8 +207,8 @@ __global__ __launch_bounds__(256, 3) void stem_conv_kernel(StemParams<T> p) {  /
                     f32x4 sv, qv;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        sv[e] = stem_row_total(rs[nt][e]);
-                        qv[e] = stem_row_total(rq[nt][e]);
+                        sv[e] = dpp_row_total(rs[nt][e]);
+                        qv[e] = dpp_row_total(rq[nt][e]);
                     }
                     if (fr == 0) {
                         const int ch = (nt >> 1) * 32 + fq * 8 + (nt & 1) * 4;

@@ -35,9 +35,7 @@ using hive_mfma::f32x16;
 using hive_mfma::vec;  // vec<T, 8>: 8 elements of the 16-bit element type T = __bf16 (north_star's contract) or _Float16 (what the
                        // reference runs, /root/reference/hive/dataset_adaptors.py:1394-1401, 1415-1417): same MFMA shapes and rates
 
-#ifndef HIVE_GEMM_AHEAD
-#define HIVE_GEMM_AHEAD 3
-#endif
+constexpr int HIVE_GEMM_AHEAD = 3;  // fragment rows the residual loads of the GEMM epilogue run ahead (gemm_store_rows)
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESIDUAL = 2, EPI_QKV = 3, EPI_QKV_ALL = 4 };  // (_ALL: gemm_kernel only -- q | k and v^T tiles in ONE launch, chosen per tile)
 
 // v^T key order.  The attention's P.V step holds the probabilities of a lane in accumulator order: its 8 k-slots of one
@@ -125,31 +123,11 @@ constexpr int BN = 128, BK = 64;
 
 // (attention_kernel, tuning builds of rounds 4-5 that lost and were taken out: the softmax denominators from an extra all-ones channel block of P.V instead of 32 v_add_f32 per
 // tile -- 75.41 -> 75.85 ms per 107-frame forward, the four extra MFMAs cost more than the additions; the same sums as 16 v_pk_add_f32 -- 75.78-75.99 -> 75.96-76.19 ms.)
-#ifndef HIVE_GEMM_ABLATE
-#define HIVE_GEMM_ABLATE 0  // tuning builds only (make ablate_gemm; tools/probe_gemm_tiles.py with HIVE_AMD_LIB=...): 1 = gemm256p_kernel without its epilogue
-#endif
 
 // erf-GELU (nn.GELU default): 0.5 x (1 + erf(x / sqrt 2)) = max(x, 0) - |x| E(|x|) / 2 with E(a) = erfc(a / sqrt 2).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef HIVE_GELU_AS
-#define HIVE_GELU_AS 0  // tuning build (make gelu_as): 1 = rounds 1-4's form, erf by Abramowitz-Stegun 7.1.26 on rcp + exp2 (two transcendentals, ~16 issue slots per value)
-#endif
-#if HIVE_GELU_AS
-__device__ __forceinline__ f32x2 gelu_exact2(f32x2 x) {
-    const f32x2 ax = f32x2{fabsf(x.x), fabsf(x.y)};
-    const f32x2 z = ax * 0.70710678118654752440f;
-    const f32x2 d = 1.0f + 0.3275911f * z;
-    const f32x2 t = f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    const f32x2 poly = ((((1.061405429f * t - 1.453152027f) * t + 1.421413741f) * t - 0.284496736f) * t + 0.254829592f) * t;
-    const f32x2 a = -z * z * 1.44269504088896340736f;
-    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-    const f32x2 erf_abs = 1.0f - poly * e;
-    const f32x2 s = f32x2{copysignf(erf_abs.x, x.x), copysignf(erf_abs.y, x.y)};
-    return 0.5f * x * (1.0f + s);
-}
-#else
-// Round 5: ONE transcendental per value.  E(a) / 2 = 2^-(1 + a q(a)) with q a degree-4 polynomial fitted (weighted minimax of the GELU's absolute error,
+// Rounds 1-4: erf by Abramowitz-Stegun 7.1.26 on rcp + exp2 (two transcendentals, ~16 issue slots per value).  Round 5: ONE transcendental per value.  E(a) / 2 = 2^-(1 + a q(a)) with q a degree-4 polynomial fitted (weighted minimax of the GELU's absolute error,
 // tools/fit_gelu.py) so that |gelu - exact| <= 6e-7 for every float32 x -- the size of Abramowitz-Stegun's 1.5e-7 |x| / 2 at |x| = 4-8, three orders of
 // magnitude below a bfloat16 / two below a float16 output step -- and 1 + a q(a) increases monotonically to +inf, so large |x| need no clamp (2^-inf = 0).
 // Evaluated for two values at once on the packed f32 pipe (v_pk_fma_f32: IEEE per element): 5 packed + 2 v_and + 2 v_exp per pair, ~9.5 issue slots per value
@@ -164,8 +142,6 @@ __device__ __forceinline__ f32x2 gelu_exact2(f32x2 x) {
     const f32x2 e = f32x2{__builtin_amdgcn_exp2f(-P.x), __builtin_amdgcn_exp2f(-P.y)};
     return (x + ax) * 0.5f - ax * e;  // max(x, 0) = (x + |x|) / 2 exactly
 }
-#endif
-
 
 // Global -> LDS staging with LDS-DMA (global_load_lds_dwordx4): one wave instruction deposits 64 x 16 B =
 // 8 rows of 128 B, lane-linear.  The bank swizzle therefore lives on the SOURCE side: LDS slot (row, s)
@@ -186,12 +162,9 @@ __device__ __forceinline__ void stage_group(const T *__restrict__ src, int ld, i
 // Sum over the 8 lanes 8 g .. 8 g + 7 (half of a 16-lane DPP row), left in all of them: two quad permutes and a half-row mirror, three DPP
 // additions on the VALU (the ds_bpermute behind __shfl_xor goes through the LDS pipe, which the epilogue's turn-around already keeps busy)
 __device__ __forceinline__ float dpp_oct_total(float v) {
-#define HIVE_DPP_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
-    HIVE_DPP_ADD(0xB1);   // quad_perm [1, 0, 3, 2]
-    HIVE_DPP_ADD(0x4E);   // quad_perm [2, 3, 0, 1]
-    HIVE_DPP_ADD(0x141);  // row_half_mirror: lane i of an 8-lane half reads lane 7 - i, which holds the other quad's sum
-#undef HIVE_DPP_ADD
-    return v;
+    v = hive_mfma::dpp_add<0xB1>(v);      // quad_perm [1, 0, 3, 2]
+    v = hive_mfma::dpp_add<0x4E>(v);      // quad_perm [2, 3, 0, 1]
+    return hive_mfma::dpp_add<0x141>(v);  // row_half_mirror: lane i of an 8-lane half reads lane 7 - i, which holds the other quad's sum
 }
 
 // Epilogue of the A.W^T GEMM tiles (EPI_BIAS / _GELU / _RESIDUAL): bias, GELU or residual in f32, one rounding to bf16; through the
@@ -278,10 +251,7 @@ __device__ __forceinline__ void gemm_store_rows(const GemmParams<T> &p, const f3
         vec<T, 8> ov;
 #pragma unroll
         for (int k = 0; k < 8; ++k) ov[k] = (T)o[k];
-        if constexpr (HIVE_GEMM_ABLATE & 2)  // tuning build: everything but the store itself
-            asm volatile("" ::"v"(ov));
-        else
-            *reinterpret_cast<vec<T, 8> *>(p.C + (size_t)m * p.ldc + n) = ov;
+        *reinterpret_cast<vec<T, 8> *>(p.C + (size_t)m * p.ldc + n) = ov;
         if (ln_out) {
             // statistics of the STORED (rounded) values of this row's 64 columns: the 8 lanes of the row sit side by side (lane & 7); the sum
             // of squares is taken about the 64 values' own mean (ln_finalize_kernel merges the groups exactly: no E[x^2] - mean^2 cancellation)
@@ -346,22 +316,14 @@ __global__ __launch_bounds__(256) void ln_row_stats_kernel(const T *__restrict__
 
 // per-row groups (sum, M2 about the group's own mean) of 64 columns each -> (mean, rstd) of the row: Chan's merge of the groups.  16 lanes per row
 // (a DPP row; groups <= 16, i.e. D <= 1024): lane g reads group g -- a row's partials are 8 `groups` contiguous bytes, four rows per wave-instruction.
-__device__ __forceinline__ float dpp_row16_total(float v) {
-#define HIVE_DPP_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
-    HIVE_DPP_ADD(0x128);  // row_ror:8
-    HIVE_DPP_ADD(0x124);  // row_ror:4
-    HIVE_DPP_ADD(0x122);  // row_ror:2
-    HIVE_DPP_ADD(0x121);  // row_ror:1
-#undef HIVE_DPP_ADD
-    return v;
-}
+using hive_mfma::dpp_row_total;
 __global__ __launch_bounds__(256) void ln_finalize_kernel(const float *__restrict__ partial, int M, int groups, float eps, float *__restrict__ stats) {
     const int row = blockIdx.x * 16 + (threadIdx.x >> 4), g = threadIdx.x & 15;
     float2 pg = float2{0.f, 0.f};
     if (row < M && g < groups) pg = reinterpret_cast<const float2 *>(partial)[(size_t)row * groups + g];
-    const float mean = dpp_row16_total(pg.x) / (float)(64 * groups);
+    const float mean = dpp_row_total(pg.x) / (float)(64 * groups);
     const float d = pg.x * (1.0f / 64.0f) - mean;
-    const float m2 = dpp_row16_total(g < groups ? pg.y + 64.0f * d * d : 0.f);
+    const float m2 = dpp_row_total(g < groups ? pg.y + 64.0f * d * d : 0.f);
     if (row < M && g == 0) *reinterpret_cast<float2 *>(stats + 2 * (size_t)row) = float2{mean, rsqrtf(m2 / (float)(64 * groups) + eps)};
 }
 
@@ -428,8 +390,8 @@ __global__ __launch_bounds__(TM * 2, 1) void gemm_kernel(GemmParams<T> p) {
     // Items = tiles x split_k (split_k = 1 except at small M): item i multiplies K-steps [k0, k1) of tile i / split_k.
     const int S = p.split_k, KT = p.K / BK;
     const int tiles_n = p.N / BN, n_tiles = ((p.M + TM - 1) / TM) * tiles_n * S;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3, tq = n_tiles >> 3, tr = n_tiles & 7;
-    const int run0 = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq, run_n = tq + (xcd < tr ? 1 : 0);
+    int run0, run_n, per_xcd;
+    hive_mfma::xcd_run(n_tiles, run0, run_n, per_xcd);
     int tl = blockIdx.x >> 3;  // position in the XCD's run
     if (tl >= run_n) return;   // (whole workgroup)
     auto coords = [&](int item, int &m, int &n, int &ka, int &kb) {
@@ -575,8 +537,12 @@ __global__ __launch_bounds__(TM * 2, 1) void gemm_kernel(GemmParams<T> p) {
 // Large-M variant: C tile 256 x 256, K-step 64, EIGHT waves as 2 (M) x 4 (N), each a 128 x 64 sub-tile (8 x 4 MFMA
 // 16x16x32 accumulators, 128 VGPRs: two waves per SIMD).  Half the L2 operand bytes per flop of the 128 x 128 tile
 // (the operand stream, not the MFMAs or LDS, bounds that one: DESIGN.md section 5.3).  Two 64-KiB LDS-DMA stages.
-//
-// What the K-step costs, measured (tools/probe_gemm_stamps.py: per-workgroup clocks; timing builds with parts of the loop removed):
+// PERSISTENT workgroups (one per CU, XCD-aware runs of tiles as in csrc/conv.hip): the K-steps of a workgroup's tiles
+// form one stream, the first stage of the next tile is issued during the last K-step of the current one and lands under its epilogue.
+constexpr int T256 = 256, T256_STAGE = 2 * T256 / 8 * 1024;
+
+// What the K-step costs, measured in round 5 (per-workgroup phase clocks in a one-tile-per-workgroup form of this kernel, and timing builds
+// with parts of the loop removed: DESIGN_LOG.md):
 // 2700-2750 shader cycles against 2048 of MFMA issue.  Without the LDS-DMA stream the same loop (MFMAs, fragment reads, barrier) runs
 // 4096^3 at 1478 TFLOP/s instead of 1230-1290 (hipBLASLt: 1470); without the barrier as well, 1506.  It is not the pieces' latency:
 // a wave's own pieces have landed when it reaches the barrier (vmcnt wait: 10 % of its waiting), and a FOUR-stage ring of 32-deep
@@ -588,100 +554,9 @@ __global__ __launch_bounds__(TM * 2, 1) void gemm_kernel(GemmParams<T> p) {
 // writes cost the 20 %: fetching 64 KiB of distinct lines per 2048 MFMA cycles and CU from L2 does (32 B/clk/CU wanted, ~26 B/clk
 // delivered with all 256 CUs streaming: tools/ubench/ldsdma.hip).  At 256 x 256 x 64 the tile is L2-bandwidth-bound; a larger tile does
 // not fit the register file.
-constexpr int T256 = 256, T256_STAGE = 2 * T256 / 8 * 1024;
-
-#ifdef HIVE_GEMM_STAMPS  // tuning builds only (make stamps): per-workgroup phase clocks of gemm256_kernel, read back by tools/probe_gemm_stamps.py
-__device__ unsigned long long g_stamps[8 * 8192];
-extern "C" int hive_debug_read_stamps(void *host, size_t bytes) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-#define HIVE_STAMP(i) do { if (tid == 0 && blockIdx.x < 8192) g_stamps[blockIdx.x * 8 + (i)] = clock64(); } while (0)
-#define HIVE_STAMP_ADD(i, v) do { if (tid == 0 && blockIdx.x < 8192) g_stamps[blockIdx.x * 8 + (i)] = (v); } while (0)
-#else
-#define HIVE_STAMP(i) do { } while (0)
-#define HIVE_STAMP_ADD(i, v) do { } while (0)
-#endif
-
-template <typename T, int EPI>
-__global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmParams<T> p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];  // 2 stages x (A tile 256 x 64, W tile 256 x 64) + 8 x 4 KiB for the epilogue
-    constexpr int A_GROUPS = T256 / 8, GROUPS = 2 * A_GROUPS, PER_WAVE = GROUPS / 8;
-    static_assert(EPI != EPI_QKV, "the transposed v^T store stays with the 128-row kernel (N = 768)");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;  // 128 rows x 64 columns per wave
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-    const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    const int tiles_n = p.N / T256;
-    const int m0 = (tile / tiles_n) * T256, n0 = (tile % tiles_n) * T256;
-
-    // LDS-DMA addressing, hoisted: piece j of this wave (group g = wave + 8 j: j < 4 an A group, else a W group; 8 rows x 128 B) reads
-    // [uniform panel base + 128 kt] + [per-lane byte offset of (row, swizzled chunk)], and the per-lane part does not depend on kt --
-    // 8 registers computed once instead of a clamp, two 64-bit multiply-adds and three 64-bit adds per piece and K-step (~90 VALU
-    // instructions per wave and step beside its 64 MFMAs).
-    unsigned piece_off[PER_WAVE];
-#pragma unroll
-    for (int j = 0; j < PER_WAVE; ++j) {
-        const int g = wave + j * 8, row = (g & (A_GROUPS - 1)) * 8 + (lane >> 3), chunk = (lane & 7) ^ ((row >> 1) & 7);
-        const int rel = j < PER_WAVE / 2 ? min(row, p.M - 1 - m0) : min(row, p.N - 1 - n0);  // rows past the end: the last row again (never stored)
-        piece_off[j] = (unsigned)rel * (unsigned)p.K * 2u + (unsigned)chunk * 16u;
-    }
-    const char *a_panel = reinterpret_cast<const char *>(p.A + (size_t)m0 * p.K), *w_panel = reinterpret_cast<const char *>(p.W + (size_t)n0 * p.K);
-    auto issue_piece = [&](int kt, int stage, int j) {
-        const char *g = (j < PER_WAVE / 2 ? a_panel : w_panel) + (size_t)kt * (BK * 2) + piece_off[j];
-        __builtin_amdgcn_global_load_lds((const void *)g, (__attribute__((address_space(3))) void *)(lds + stage * T256_STAGE + (wave + j * 8) * 1024), 16, 0, 0);
-    };
-
-    f32x4 acc[4][8];  // acc[nt][mt] = W_frag . A_frag^T : rows = n, cols = m
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int KT = p.K / BK;
-    HIVE_STAMP(0);
-#pragma unroll
-    for (int j = 0; j < PER_WAVE; ++j) issue_piece(0, 0, j);
-    const int fr = lane & 15, fq = lane >> 4;
-#ifdef HIVE_GEMM_STAMPS
-    unsigned long long waited = 0, waited_vm = 0;
-#endif
-    hive_mfma::KPipe<T, 8, false> pipe;
-    pipe.a_row0 = wr * 128, pipe.w_row0 = wc * 64, pipe.fr = fr, pipe.fq = fq;
-    for (int kt = 0; kt < KT; ++kt) {
-#ifdef HIVE_GEMM_STAMPS
-        const unsigned long long w0 = clock64();
-#endif
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (lgkmcnt: the held-back slots' fragment reads of stage kt - 1)
-#ifdef HIVE_GEMM_STAMPS
-        const unsigned long long w1 = clock64();
-#endif
-        __builtin_amdgcn_s_barrier();  // everyone's stage kt landed; everyone finished reading stage kt - 1
-#ifdef HIVE_GEMM_STAMPS
-        if (kt == 0) HIVE_STAMP(1); else waited += clock64() - w0, waited_vm += w1 - w0;
-#endif
-        const int nk = min(kt + 1, KT - 1);  // next stage (past the end: the last one again), issued between the MFMA slots
-        const unsigned char *a_t = lds + (kt & 1) * T256_STAGE, *w_t = a_t + A_GROUPS * 1024;
-        pipe.begin(a_t, w_t);
-        if (kt > 0) pipe.flush(acc);  // the previous step's last slots, under the latency of this step's first reads
-        pipe.body(acc, PER_WAVE, [&](int j) { issue_piece(nk, (kt + 1) & 1, j); });
-    }
-    pipe.flush(acc);
-    HIVE_STAMP(2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the redundant last stage
-    HIVE_STAMP(3);
-    HIVE_STAMP_ADD(6, waited);
-    HIVE_STAMP_ADD(7, waited_vm);
-
-    gemm_store_rows<T, EPI, 8>(p, acc, m0 + wr * 128, n0 + wc * 64, lds + 2 * T256_STAGE + wave * 4096, lane);
-    HIVE_STAMP(4);
-#ifdef HIVE_GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    HIVE_STAMP(5);
-#endif
-}
-
-// What the epilogues cost at the bench batch (M = 130112; `make ablate_gemm`, tools/probe_gemm_tiles.py): without its epilogue the K loops of q|k run in 231 us
+//
+// What the epilogues cost at the bench batch (M = 130112; timing builds of round 5 that left the epilogue, or its stores alone, out;
+// tools/probe_gemm_tiles.py): without its epilogue the K loops of q|k run in 231 us
 // (1330 TFLOP/s) against 347 with it, proj 115 / 209, fc1 + GELU 417 / 756, fc2 507 / 572 -- 7.3 ms of a 76 ms forward; with everything but the store
 // instructions 261 / 174 / 587 / 541.  Measured INTERLEAVED in one process (the clock drifts over a run: a first comparison across processes showed gains that
 // were drift): non-temporal stores of C change nothing (+-0.5 %; fc1 1.4 % slower), nor does starting every other workgroup half a tile late so that the
@@ -689,8 +564,6 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmParams<T> p) {
 // vmcnt(0): the stage it needs is older than those stores).  The epilogue cannot overlap the next tile's K loop inside one workgroup (the accumulators are the registers), and two
 // co-resident workgroups need tiles of 128 x 256 at most (LDS), whose operand stream -- 1.5 x the bytes per flop through the CU's ~26 B/clk vector-memory path --
 // costs what the overlap gains (the 128 x 128 two-workgroup form measures 450 vs 347 us on q|k).
-// The same tile as PERSISTENT workgroups (one per CU, XCD-aware runs of tiles as in csrc/conv.hip): the K-steps of a workgroup's tiles
-// form one stream, the first stage of the next tile is issued during the last K-step of the current one and lands under its epilogue.
 template <typename T, int EPI>
 __global__ __launch_bounds__(512, 1) void gemm256p_kernel(GemmParams<T> p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -700,8 +573,8 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(GemmParams<T> p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     const int tiles_n = p.N / T256, n_tiles = ((p.M + T256 - 1) / T256) * tiles_n;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3, tq = n_tiles >> 3, tr = n_tiles & 7;
-    const int run0 = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq, run_n = tq + (xcd < tr ? 1 : 0);
+    int run0, run_n, per_xcd;
+    hive_mfma::xcd_run(n_tiles, run0, run_n, per_xcd);
     int tl = blockIdx.x >> 3;
     if (tl >= run_n) return;  // (whole workgroup)
     int m0, n0;
@@ -757,12 +630,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(GemmParams<T> p) {
             buf ^= 1;
         }
         pipe.flush(acc);
-        if constexpr (HIVE_GEMM_ABLATE & 1) {  // tuning build (make ablate_gemm): the K loops alone -- the accumulators are kept alive, nothing is stored
-#pragma unroll
-            for (int i = 0; i < (VT ? 8 : 4); ++i)
-#pragma unroll
-                for (int j = 0; j < (VT ? 4 : 8); ++j) asm volatile("" ::"v"(acc[i][j]));
-        } else if constexpr (!VT) {
+        if constexpr (!VT) {
             gemm_store_rows<T, EPI, 8>(p, acc, em0 + wr * 128, en0 + wc * 64, lds + 2 * T256_STAGE + wave * 4096, lane);
         } else {
             // v^T[b][h][c][token]: the wave's 128 tokens x 64 channels are two 64-token blocks of one head (Np % 64 == 0), each 64 rows of
@@ -1169,27 +1037,15 @@ constexpr int GEMM256_LDS = 2 * T256_STAGE + hive_mfma::STAGED_ROWS_LDS;
 
 template <typename T>
 static int launch_gemm256(hive_ctx *ctx, int epi, const GemmParams<T> &p) {
-    const dim3 grid((unsigned)(((p.M + T256 - 1) / T256) * (p.N / T256))), block(512);
+    // persistent workgroups, one per CU (+2-4 % against one tile per workgroup where a workgroup gets more than one tile: the next tile's first fill is hidden)
+    const long long tiles = (long long)((p.M + T256 - 1) / T256) * (p.N / T256);
+    const dim3 grid((unsigned)std::min<long long>((tiles + 7) / 8 * 8, (long long)ctx->num_cus / 8 * 8)), block(512);
     const size_t lds_bytes = GEMM256_LDS;
-    // persistent workgroups by default (+2-4 % where a workgroup gets more than one tile: the next tile's first fill is hidden);
-    // HIVE_GEMM_PERSIST=0 selects the one-tile-per-workgroup kernel, the one the phase clocks of `make stamps` instrument
-    static const char *persist = getenv("HIVE_GEMM_PERSIST");
-    if (!(persist && persist[0] == '0')) {
-        const dim3 pgrid((unsigned)std::min<long long>(((long long)grid.x + 7) / 8 * 8, (long long)ctx->num_cus / 8 * 8));
-        switch (epi) {
-            case EPI_BIAS: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_BIAS>), pgrid, block, lds_bytes, ctx->stream, p); break;
-            case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_BIAS_GELU>), pgrid, block, lds_bytes, ctx->stream, p); break;
-            case EPI_BIAS_RESIDUAL: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_BIAS_RESIDUAL>), pgrid, block, lds_bytes, ctx->stream, p); break;
-            case EPI_QKV: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_QKV>), pgrid, block, lds_bytes, ctx->stream, p); break;
-            default: return hive_fail(ctx, HIVE_ERR_INVALID, "gemm: unknown epilogue %d", epi);
-        }
-        HIVE_CHECK_HIP(ctx, hipGetLastError());
-        return HIVE_OK;
-    }
     switch (epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm256_kernel<T, EPI_BIAS>), grid, block, lds_bytes, ctx->stream, p); break;
-        case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm256_kernel<T, EPI_BIAS_GELU>), grid, block, lds_bytes, ctx->stream, p); break;
-        case EPI_BIAS_RESIDUAL: hipLaunchKernelGGL((gemm256_kernel<T, EPI_BIAS_RESIDUAL>), grid, block, lds_bytes, ctx->stream, p); break;
+        case EPI_BIAS: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_BIAS>), grid, block, lds_bytes, ctx->stream, p); break;
+        case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_BIAS_GELU>), grid, block, lds_bytes, ctx->stream, p); break;
+        case EPI_BIAS_RESIDUAL: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_BIAS_RESIDUAL>), grid, block, lds_bytes, ctx->stream, p); break;
+        case EPI_QKV: hipLaunchKernelGGL((gemm256p_kernel<T, EPI_QKV>), grid, block, lds_bytes, ctx->stream, p); break;
         default: return hive_fail(ctx, HIVE_ERR_INVALID, "gemm: unknown epilogue %d", epi);
     }
     HIVE_CHECK_HIP(ctx, hipGetLastError());
@@ -1206,9 +1062,7 @@ static int launch_gemm(hive_ctx *ctx, int epi, const GemmParams<T> &p) {
     const long long tiles256 = (long long)((p.M + T256 - 1) / T256) * (p.N / T256);
     const long long rounds = (tiles256 + ctx->num_cus - 1) / ctx->num_cus;
     const bool fills = tiles256 * 5 >= rounds * ctx->num_cus * 3;  // >= 60 % of the CU slots of its rounds (67 %: 635 / 763 vs 612 / 705 TFLOP/s for proj / fc2 at M = 29184; 44 %: 655 vs 858)
-    static const char *persist_env = getenv("HIVE_GEMM_PERSIST");
-    const bool one_tile_kernel = persist_env && persist_env[0] == '0';  // that kernel has no v^T epilogue
-    if ((epi != EPI_QKV || !one_tile_kernel) && p.N % T256 == 0 && ((force && force[0] == '2') || (!force && fills))) return launch_gemm256<T>(ctx, epi, p);
+    if (p.N % T256 == 0 && ((force && force[0] == '2') || (!force && fills))) return launch_gemm256<T>(ctx, epi, p);
     // persistent workgroups: two per CU (64 KiB of LDS each), a multiple of 8 so that every XCD gets the same number
     const long long tiles = (long long)((p.M + GEMM_TM - 1) / GEMM_TM) * (p.N / BN);
     // (Round 4, measured and taken out: 64-row tiles (two waves, 56 KiB of LDS) where fewer 128-row tiles than CUs exist -- the reference's literal
@@ -1255,8 +1109,8 @@ static int launch_gemm(hive_ctx *ctx, int epi, const GemmParams<T> &p) {
 
 template <typename T>
 static int ensure_gemm_attrs(hive_ctx *ctx) {
-    static bool set[64] = {false};
-    if (ctx->device < 64 && set[ctx->device]) return HIVE_OK;
+    static hive_device_latch latch;
+    if (latch.done(ctx)) return HIVE_OK;
 #define HIVE_GEMM_ATTR(EPI_)                                                                                                                                  \
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm_kernel<T, EPI_, GEMM_TM, GEMM_NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS)); \
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm_kernel<T, EPI_, GEMM_TM, GEMM_NST_DEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_DEEP)); \
@@ -1268,10 +1122,7 @@ static int ensure_gemm_attrs(hive_ctx *ctx) {
 #undef HIVE_GEMM_ATTR
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm_kernel<T, EPI_QKV_ALL, GEMM_TM, GEMM_NST_DEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_DEEP));
     HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm_kernel<T, EPI_QKV_ALL, GEMM_TM, GEMM_NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS));
-    HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm256_kernel<T, EPI_BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM256_LDS));
-    HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm256_kernel<T, EPI_BIAS_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM256_LDS));
-    HIVE_CHECK_HIP(ctx, hipFuncSetAttribute((const void *)gemm256_kernel<T, EPI_BIAS_RESIDUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM256_LDS));
-    if (ctx->device < 64) set[ctx->device] = true;
+    latch.mark(ctx);
     return HIVE_OK;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Does the long-K GEMM (fc2: K = 3072) lose its A-panel sharing between the N tiles of an M block?  Time per 64-deep K-step and round of 256 CUs for N = 256 (one N tile:
-nothing to share), 512, 768, at K = 768 and 3072.  Usage (GPU box): [HIVE_AMD_LIB=.../libhive_kloop.so] python tools/probe_gemm_nshare.py"""
+nothing to share), 512, 768, at K = 768 and 3072.  (Round 5 also ran it on a timing build of the K loops alone: DESIGN_LOG.md.)  Usage (GPU box): python tools/probe_gemm_nshare.py"""
 import os
 import sys
 

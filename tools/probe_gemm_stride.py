@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is fc2's K loop (K = 3072: 1.76 us per 64-deep step against 1.47 for the K = 768 GEMMs) slowed by its operands' row pitch (6144 B = 3 x 2^11: every row of an
 8-row LDS-DMA piece lands on the same few L2 channels)?  hive_vit_linear at N = 768 for K = 3072 and for neighbouring K whose pitch is not such a multiple (same
-work per step; time per K-step is what is compared).  Usage (GPU box): [HIVE_AMD_LIB=.../libhive_kloop.so] python tools/probe_gemm_stride.py"""
+work per step; time per K-step is what is compared).  (Round 5 also ran it on a timing build of the K loops alone: DESIGN_LOG.md.)  Usage (GPU box): python tools/probe_gemm_stride.py"""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the convolutions of one ResNetV2 bottleneck (stage 1: 120 x 160, 256 / 64 channels; stage 3: 30 x 40, 1024 / 256) at the bench batch,
-straight through the C ABI.  HIVE_AMD_LIB=hive_amd/lib/libhive_conv_abN.so times a tuning build (make -C hive_amd/csrc ablate_conv).
+straight through the C ABI.  HIVE_AMD_LIB=... times another build of the library.
 Usage: python tools/probe_resnet.py [batch]"""
 import ctypes
 import os
