@@ -423,6 +423,51 @@ int hive_inpaint_telea(hive_ctx *ctx, const void *image, int H, int W, int chann
 int hive_inpaint_frames(hive_ctx *ctx, const uint8_t *d_rgb, const uint16_t *d_depth, const uint8_t *d_mask, int n, int H, int W, int dilate_kh, int dilate_kw,
                         int dilate_iterations, int radius, uint8_t *d_rgb_out, uint16_t *d_depth_out, int32_t *levels_out);
 
+/* ---- rendering meshes from a camera pose -- render_mesh(camera_matrix, camera_pose, *meshes), scripts/experiments.py:861-883 (pyrender, RenderFlags.FLAT;
+ * scored against the frame at :835-852).  An exact z-buffer rasteriser; several meshes share one depth test through four calls on one key plane
+ * d_key u64 [H][W]:  hive_render_clear, hive_render_draw per mesh, hive_render_shade per mesh, hive_render_resolve.  The rules (float64, no fused multiply-add):
+ *   camera     K, R, t as for hive_project (world-to-camera), the project's camera frame as it stands: x right, y down, z forward.  The reference's
+ *              diag(1, -1, -1, 1) only converts to pyrender's OpenGL camera and is not restated.
+ *   vertex     hive_project's operation order: cam_r = ((R[r][0] x + R[r][1] y) + R[r][2] z) + t_r; c_r = (K[r][0] cam_0 + K[r][1] cam_1) + K[r][2] cam_2;
+ *              sx = c_0 / c_2, sy = c_1 / c_2, z = c_2 (hive_project's depth; the camera-space z for a K whose last row is 0 0 1) -- a vertex lands where
+ *              world2image puts it.  Snapped to 8 sub-pixel bits: X = (int)floor(sx * 256 + 0.5), Y likewise.
+ *   samples    pixel (i, j) samples the screen point x = j, y = i: world2image's convention (it rounds to the pixel index), not OpenGL's half-pixel offset.  A
+ *              mesh built from a frame and rendered from that frame's pose puts every vertex back on its pixel.
+ *   rejection  a face is discarded when a vertex has !(z >= near) -- no clipping: triangles here are voxel- or pixel-sized --, when a vertex has
+ *              !(|sx| < 65536 && |sy| < 65536) (the guard band keeps every edge function below 2^53: int64 -> double is exact), or when the snapped area
+ *              A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) is 0.  near > 0 (0.05 in the Python wrapper); no far plane.
+ *   coverage   exact in int64, no back-face culling: A < 0 swaps vertices 1 and 2 and uses |A|.  For the edge opposite vertex e, from p = e + 1 to q = e + 2
+ *              (mod 3): w_e = (Xq - Xp)(256 i - Yp) - (Yq - Yp)(256 j - Xp); inside iff for every edge w_e > 0 or (w_e == 0 and (dy < 0 or (dy == 0 and
+ *              dx > 0))) -- the top-left rule.  Candidates: the bounding box ceil(min / 256) .. floor(max / 256) clipped to the screen.
+ *   depth      q_e = (double)w_e / z_e; den = (q0 + q1) + q2; depth = (float)(1.0 / (den / (double)A)).
+ *   visibility key = (uint64)float_bits(depth) << 32 | global face index, and the pixel keeps the MINIMUM key (one 64-bit unsigned atomic minimum): the
+ *              nearest surface, on equal float32 depth the smaller face index, whatever the arrival order or the launch shape.  The global face index is
+ *              face_base + the face's row: the caller numbers the meshes' faces consecutively in argument order.  An empty pixel holds all ones.
+ *   shading    unlit and perspective-correct, as RenderFlags.FLAT: an attribute a is ((q0 a0 + q1 a1) + q2 a2) / den with the edge functions recomputed
+ *              from the snapped vertices at the winner.  Vertex colours: each channel (uint8)min(255, floor(c + 0.5)).  Textures: (u, v) in the atlas
+ *              convention of Pipeline._pack_textures (u = column / width, v = 1 - row / height), nearest texel col = clamp(floor(u Wt + 0.5), 0, Wt - 1),
+ *              row = clamp(floor((1 - v) Ht + 0.5), 0, Ht - 1).  Empty pixels: the background colour, depth 0, face -1.
+ * All pointers named d_ are device memory; K, R, t and background are host arrays.  Nothing synchronises. */
+/* Every pixel of the key plane to "empty" (all ones): the start of a picture, pyrender's fresh scene at experiments.py:861-883.  H W < 2^31. */
+int hive_render_clear(hive_ctx *ctx, uint64_t *d_key, int H, int W);
+/* The depth test of one mesh (experiments.py:871-881 adds the meshes to one scene): d_vertices f64 [nv][3], d_faces i32 [nf][3] with ids in [0, nv) (a face with
+ * another id is skipped, never read), its faces numbered face_base .. face_base + nf - 1 (< 2^32 - 1).  Scratch of the caller, filled here and read again by
+ * hive_render_shade: d_xy i32 [nv][2] the snapped (X, Y) and d_z f64 [nv] the depth of every vertex (0 marks a rejected vertex: a kept one has z >= near > 0);
+ * d_large i32 [nf]: the faces whose clipped box holds more than 64 pixels, drawn by one workgroup each (the others by one thread each); d_counts u32 [2] =
+ * {faces on that list, faces drawn by their own thread} of this call (faces rejected or off screen are in neither).  nv, nf < 2^31. */
+int hive_render_draw(hive_ctx *ctx, const double *d_vertices, int64_t nv, const int32_t *d_faces, int64_t nf, int64_t face_base, const double K[9], const double R[9],
+                     const double t[3], int H, int W, double near, int32_t *d_xy, double *d_z, int32_t *d_large, uint32_t *d_counts, uint64_t *d_key);
+/* The colour of the pixels whose winner lies in [face_base, face_base + nf) (experiments.py:861-883 renders with RenderFlags.FLAT), after EVERY mesh has been drawn:
+ * the same d_faces, nf, face_base, d_xy and d_z as the mesh's hive_render_draw; d_vertex_colors u8 [nv][3], or NULL and d_uv f64 [nv][2] with d_texture
+ * u8 [Ht][Wt][3]; d_color u8 [H][W][3].  Other pixels are left alone. */
+int hive_render_shade(hive_ctx *ctx, int64_t nv, const int32_t *d_faces, int64_t nf, int64_t face_base, const int32_t *d_xy, const double *d_z,
+                      const uint8_t *d_vertex_colors, const double *d_uv, const uint8_t *d_texture, int Ht, int Wt, const uint64_t *d_key, int H, int W,
+                      uint8_t *d_color);
+/* The planes of the finished picture (experiments.py:847 relies on the white background of :861-883): empty pixels of d_color u8 [H][W][3] (may be NULL) take
+ * background[3] (NULL = white); d_depth f32 [H][W] (may be NULL) the winner's depth, 0 where empty; d_face i32 [H][W] (may be NULL) its global face index, -1
+ * where empty (an index of 2^31 or more does not fit: keep the total below 2^31 when the face plane is wanted). */
+int hive_render_resolve(hive_ctx *ctx, const uint64_t *d_key, int H, int W, const uint8_t background[3], uint8_t *d_color, float *d_depth, int32_t *d_face);
+
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
  * (x 1/1000 as float32, > max_depth -> 0), optional mask (non-zero -> depth 0, fusion.py:121).
