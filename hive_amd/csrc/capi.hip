@@ -33,6 +33,12 @@ int hive_reserve_device(hive_ctx *ctx, void **ptr, size_t *cur, size_t bytes) {
     return HIVE_OK;
 }
 
+int hive_pinned_small(hive_ctx *ctx, void **out) {
+    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
+    *out = ctx->h_pinned_small;
+    return HIVE_OK;
+}
+
 int hive_splitk_workspace(hive_ctx *ctx, size_t bytes, void **ws, unsigned **count) {
     if (!ctx->d_splitk_count) {
         HIVE_CHECK_HIP(ctx, hipMalloc((void **)&ctx->d_splitk_count, HIVE_SPLITK_TILES * sizeof(unsigned)));
@@ -134,10 +140,9 @@ int hive_ctx_create(int device_id, void *stream, hive_ctx **out) {
             ctx->stream = (hipStream_t)stream;  // NULL = the default stream
         }
     }
-    // [0, 128): scalar blocks of the kernels; [128, 128 + 2048): HIVE_COUNT_SLOTS update counters, one per 128-byte line (tsdf.hip);
-    // [2304, 2304 + 2 x 512): the two scalar blocks of the fused sweep (tsdf.hip MS_BASE)
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_scalars, 4096 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(ctx->d_scalars, 0, 4096 * sizeof(unsigned));  // the TSDF scalar blocks start cleared (tsdf.hip prepare_frame)
+    // the scalar words of every translation unit (the map: hive_internal.hpp SC_*)
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_scalars, HIVE_SCALAR_WORDS * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(ctx->d_scalars, 0, HIVE_SCALAR_WORDS * sizeof(unsigned));  // the TSDF scalar blocks start cleared (tsdf.hip prepare_frame)
     if (e == hipSuccess) e = hipMalloc(&ctx->d_zeros, 256);
     if (e == hipSuccess) e = hipMemset(ctx->d_zeros, 0, 256);
     if (e != hipSuccess) {

@@ -25,8 +25,10 @@ constexpr unsigned long long KEY_NONE = ~0ull;
 constexpr uint8_t F_LOCKED = 1, F_REMOVED = 2;
 constexpr unsigned ERR_VERTEX = 1, ERR_DEGENERATE = 2, ERR_ROUNDS = 4;
 // scalar block (hive_ctx::d_scalars + DEC_SCALARS): [0] faces now, [1] done, [2] error word, [3] selected, [4] faces the selected remove, [5] rounds,
-// [6] collapses, [7] locked vertices, [8..9] threshold key (u64), [12..15] a scratch box for the output scan
-constexpr int DEC_SCALARS = 3712;
+// [6] collapses, [7] locked vertices, [8..9] threshold key (u64), [12..15] a scratch box for the output scan, [DEC_ENTRY ..] hive_mesh_decimate's own
+// counts.  DEC_SCALARS and its extent: the map in hive_internal.hpp
+constexpr int DEC_ENTRY = 16;
+static_assert(DEC_ENTRY + 4 <= DEC_SCALARS_WORDS, "hive_mesh_decimate keeps V, F in and vertices / faces out in four words behind the runner's sixteen");
 constexpr float DEC_FLT_MIN = 1.17549435e-38f;
 // a vertex's key keeps the top 5 bits of the mapped float32 cost (bands of 16 octaves): with all 32, a smooth cost field has few local minima and a
 // round applies ~2 collapses (426 rounds for a 2.5 k-face object against 200 with bands; tests/decimate_restatement.py)
@@ -530,8 +532,10 @@ int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int
     hipLaunchKernelGGL(dec_build_kernel, grid, blk, 0, s, p);
     hipLaunchKernelGGL(dec_quadric_kernel, grid, blk, 0, s, p);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
-    volatile unsigned *back = (volatile unsigned *)ctx->h_pinned_small;
+    void *pinned;
+    int rc = hive_pinned_small(ctx, &pinned);
+    if (rc) return rc;
+    volatile unsigned *back = (volatile unsigned *)pinned;
     // rounds in batches; between batches one small read-back says whether to go on (no kernel waits on the device for progress)
     for (int issued = 0;;) {
         for (int r = 0; r < DEC_BATCH; ++r, ++issued) {
@@ -547,7 +551,7 @@ int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int
             hipLaunchKernelGGL(dec_build_kernel, grid, blk, 0, s, p);
         }
         HIVE_CHECK_HIP(ctx, hipGetLastError());
-        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_pinned_small, p.sc, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(pinned, p.sc, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
         HIVE_CHECK_HIP(ctx, hipStreamSynchronize(s));
         if (back[1] || back[2] || (long long)back[0] <= job.budget) break;
         if (issued > DEC_MAX_ROUNDS + DEC_BATCH) return hive_fail(ctx, HIVE_ERR_STATE, "mesh_decimate: the round loop did not end");
@@ -558,8 +562,7 @@ int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int
         stats[1] = back[6];
         stats[2] = back[7];
     }
-    int rc = dec_error(ctx, err);
-    if (rc) return rc;
+    if ((rc = dec_error(ctx, err))) return rc;
     launch_compaction(ctx, p, l.bv, l.bf, l.nb, job.out_counts, (int *)(p.sc + 12), job.out_faces, job.out_face_cap, job.out_vertex_index);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
@@ -616,7 +619,7 @@ int hive_mesh_decimate(hive_ctx *ctx, const double *vertices, int64_t n_vertices
         job.out_faces = s_out_faces;
         job.out_vertex_index = s_out_vi;
     }
-    unsigned *sc = ctx->d_scalars + DEC_SCALARS + 16;  // [16] = V, [17] = F in, [18] / [19] = vertices / faces out
+    unsigned *sc = ctx->d_scalars + DEC_SCALARS + DEC_ENTRY;  // [0] = V, [1] = F in, [2] / [3] = vertices / faces out
     const unsigned counts[2] = {(unsigned)n_vertices, (unsigned)n_faces};
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(sc, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream));
     job.counts = sc;

@@ -328,8 +328,8 @@ constexpr int CC_ERR_TABLE = 1, CC_ERR_VERTEX = 2, CC_ERR_UNION = 4;
 constexpr int CC_CAS_CAP = 1 << 16;
 
 // scalar block of a clean-up (hive_ctx::d_scalars + CC_SCALARS): [0] vertices in, [1] faces in, [2] error word, [4..5] selection (u64),
-// [6] vertices out, [7] faces out, [8..11] the texture window's box (hive_fg_frame_mesh_cc): [0..11] is the frame path's one read-back
-constexpr int CC_SCALARS = 3584;
+// [6] vertices out, [7] faces out, [8..11] the texture window's box (hive_fg_frame_mesh_cc): [0..11] is the frame path's one read-back.  CC_SCALARS and its
+// extent: the map in hive_internal.hpp
 
 struct CCParams {
     const unsigned *counts;       // [0] V, [1] F (device)
@@ -697,8 +697,9 @@ int frame_mesh_run(hive_ctx *ctx, const FrameMeshJob &j) {
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     // 6. ONE read-back through pinned memory, of the words in use: [6..11] on the plain path, [0..11] with the clean-up, [0..13] with the decimation
     const int first = staged ? 0 : 6, last = j.decimate ? 14 : 12;
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
-    unsigned *back = (unsigned *)ctx->h_pinned_small;
+    static_assert(CC_SCALARS_WORDS >= 14, "the frame mesh runner uses words [0..13] of the clean-up's block");
+    unsigned *back;
+    if ((rc = hive_pinned_small(ctx, (void **)&back))) return rc;
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(back + first, sc + first, (size_t)(last - first) * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIVE_CHECK_HIP(ctx, hipStreamSynchronize(st));
     // when the clean-up's error word is checked: whenever the clean-up ran, before any result is handed out
@@ -768,7 +769,7 @@ int hive_grid_mesh(hive_ctx *ctx, const float *depth, const uint8_t *mask, int H
         }
         d_faces = s_faces;
     }
-    unsigned *d_tot = ctx->d_scalars + 32;  // [32] = vertices, [33] = faces
+    unsigned *d_tot = ctx->d_scalars + SC_GRID_TOTALS;  // [0] = vertices, [1] = faces
     GridParams p{H, W, max_pixel_distance, (float)max_depth_distance};
     hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, p, bv, bf);
     hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, nb, d_tot);
@@ -937,7 +938,7 @@ int hive_filter_faces(hive_ctx *ctx, const int32_t *points2d, const float *depth
         p.faces = s_faces;
         d_out = s_out;
     }
-    unsigned *d_tot = ctx->d_scalars + 34;
+    unsigned *d_tot = ctx->d_scalars + SC_FILTER_TOTAL;
     hipLaunchKernelGGL(filter_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, blk);
     hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, d_tot);
     hipLaunchKernelGGL(filter_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)blk, d_out);
@@ -966,7 +967,7 @@ int hive_texture_window(hive_ctx *ctx, const double *points, int64_t n, const do
         d_pts = (const double *)ctx->d_in;
         d_uv = (int32_t *)((char *)ctx->d_in + off_uv);
     }
-    int *d_box = (int *)(ctx->d_scalars + 40);
+    int *d_box = (int *)(ctx->d_scalars + SC_WINDOW_BOX);
     const int32_t init[4] = {0x7fffffff, 0x7fffffff, (int32_t)0x80000000, (int32_t)0x80000000};
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
     WindowParams p;

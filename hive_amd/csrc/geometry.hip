@@ -1,9 +1,11 @@
 // View frustum, depth <-> point-cloud (un)projection, mask dilation, depth hand-off.  gfx950 only.
 //
-//   hive_view_frustum   -> fusion.get_view_frustum            (call site hive/fusion.py:59)
+//   hive_view_frustum(_batch) -> fusion.get_view_frustum      (call site hive/fusion.py:59): max_depth_batch_kernel, one launch for any frame count
 //   hive_unproject      -> point_cloud_from_depth / _from_rgbd (hive/geometric.py:107-152, image2world :183-206)
 //   hive_project        -> world2image                         (hive/geometric.py:155-180)
-//   hive_dilate_mask    -> dilate_mask                         (hive/image_processing.py:30-45)
+//   hive_dilate_mask(_se), hive_depth_apply_mask(_se), hive_dilate_frames -> dilate_mask (hive/image_processing.py:30-45): ONE runner, dilate_run, over
+//                          frame sets: dilate_rows_batch_kernel + dilate_cols_batch_kernel / dilate_cols_apply_kernel (a full odd rectangle: one box),
+//                          dilate_se_kernel (+ zero_under_mask_kernel) iterated literally otherwise; keep_mask_kernel for the undilated foreground mask
 //   hive_depth_quantize -> uint16-mm PNG round trip            (hive/dataset_adaptors.py:1432-1433, hive/io.py:1032-1039)
 //
 // The geometric functions are float64 in the reference, and so are these kernels; the stream
@@ -15,17 +17,7 @@
 #include <cmath>
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void max_depth_kernel(const float *__restrict__ depth, int n, unsigned *max_bits) {
-    unsigned bits = 0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float d = depth[i];
-        if (d > 0.f) bits = max(bits, __float_as_uint(d));
-    }
-    for (int off = 32; off > 0; off >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, off));
-    if ((threadIdx.x & 63) == 0 && bits) atomicMax(max_bits, bits);
-}
-
-// one launch for a whole frame set: blockIdx.y = frame
+// max(depth) of every frame of a set in one launch: blockIdx.y = frame.  An integer maximum over positive floats' bit patterns: any grid width gives the same word
 __global__ __launch_bounds__(256) void max_depth_batch_kernel(const float *__restrict__ depth, int n_px, unsigned *max_bits) {
     const float *d = depth + (size_t)blockIdx.y * n_px;
     unsigned bits = 0;
@@ -214,26 +206,7 @@ __global__ __launch_bounds__(256) void image2world_kernel(const double *__restri
     for (int r = 0; r < 3; ++r) out_xyz[3 * i + r] = p.R[0 * 3 + r] * cam[0] + p.R[1 * 3 + r] * cam[1] + p.R[2 * 3 + r] * cam[2];
 }
 
-// separable (2r+1) box max with out-of-image pixels ignored
-__global__ __launch_bounds__(256) void dilate_rows_kernel(const uint8_t *__restrict__ in, int H, int W, int r, uint8_t *__restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= H * W) return;
-    const int v = i / W, u = i % W;
-    uint8_t m = 0;
-    for (int uu = max(0, u - r); uu <= min(W - 1, u + r); ++uu) m |= (in[v * W + uu] != 0);
-    out[i] = m;
-}
-
-__global__ __launch_bounds__(256) void dilate_cols_kernel(const uint8_t *__restrict__ in, int H, int W, int r, uint8_t *__restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= H * W) return;
-    const int v = i / W, u = i % W;
-    uint8_t m = 0;
-    for (int vv = max(0, v - r); vv <= min(H - 1, v + r); ++vv) m |= in[vv * W + u];
-    out[i] = m;
-}
-
-// frame-set versions of the two passes (blockIdx.y = frame; no bleeding across frame borders), and the masking itself:
+// separable (2r + 1) box maximum with out-of-image pixels ignored, over a frame set (blockIdx.y = frame; no bleeding across frame borders), and the masking itself:
 // mode 0 (background, hive/fusion.py:118-121): depth = 0 where the dilated mask is set;
 // mode 1 (foreground = the complement): depth = 0 where the (undilated) mask is clear or is another instance's.
 __global__ __launch_bounds__(256) void dilate_rows_batch_kernel(const uint8_t *__restrict__ in, int H, int W, int r, int instance,
@@ -386,51 +359,18 @@ static void frustum_corners(float max_depth, int H, int W, const float K[9], con
     }
 }
 
-extern "C" {
-
-int hive_view_frustum(hive_ctx *ctx, const float *depth, int H, int W, const float K[9], const double cam_pose[16], int mem,
-                      double out[15]) {
-    HIVE_ENTER(ctx);
-    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, depth && K && cam_pose && out, "view_frustum: NULL argument");
-    HIVE_REQUIRE(ctx, H > 0 && W > 0, "view_frustum: bad image size %dx%d", H, W);
-    const int n = H * W;
-    const void *d_depth;
-    int rc;
-    if (mem == HIVE_MEM_HOST && (rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, (size_t)n * 4))) return rc;
-    if ((rc = to_device(ctx, depth, (size_t)n * 4, 0, mem, &d_depth))) return rc;
-    unsigned *d_max = ctx->d_scalars + 16;
-    HIVE_CHECK_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(max_depth_kernel, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, ctx->stream, (const float *)d_depth, n,
-                       d_max);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    unsigned bits = 0;
-    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(&bits, d_max, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    float max_depth;
-    memcpy(&max_depth, &bits, 4);
-    frustum_corners(max_depth, H, W, K, cam_pose, out);
-    return HIVE_OK;
-}
-
-int hive_view_frustum_batch(hive_ctx *ctx, const float *depth, int n, int H, int W, const float K[9], const double *cam_poses, int mem,
-                            double *out) {
-    HIVE_ENTER(ctx);
-    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, depth && K && cam_poses && out, "view_frustum_batch: NULL argument");
-    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), "view_frustum_batch: bad sizes n=%d %dx%d", n, H, W);
+// The frusta of n depth maps: per-frame maxima in the generic scratch (n words), ONE launch (at most `groups` workgroups per frame) and ONE read-back
+static int view_frusta(hive_ctx *ctx, const float *depth, int n, int H, int W, const float K[9], const double *cam_poses, int mem, int groups, double *out) {
     const int n_px = H * W;
     const size_t bytes = (size_t)n * n_px * sizeof(float);
     const void *d_depth;
     int rc;
     if (mem == HIVE_MEM_HOST && (rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, bytes))) return rc;
     if ((rc = to_device(ctx, depth, bytes, 0, mem, &d_depth))) return rc;
-    // per-frame maxima in the generic scratch (n words), ONE launch and ONE read-back for the whole frame set
     if ((rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, (size_t)n * sizeof(unsigned)))) return rc;
     unsigned *d_max = (unsigned *)ctx->d_scratch;
     HIVE_CHECK_HIP(ctx, hipMemsetAsync(d_max, 0, (size_t)n * sizeof(unsigned), ctx->stream));
-    hipLaunchKernelGGL(max_depth_batch_kernel, dim3(std::min((n_px + 255) / 256, 64), n), dim3(256), 0, ctx->stream, (const float *)d_depth,
-                       n_px, d_max);
+    hipLaunchKernelGGL(max_depth_batch_kernel, dim3(std::min((n_px + 255) / 256, groups), n), dim3(256), 0, ctx->stream, (const float *)d_depth, n_px, d_max);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     std::vector<unsigned> bits((size_t)n);
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(bits.data(), d_max, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
@@ -440,29 +380,6 @@ int hive_view_frustum_batch(hive_ctx *ctx, const float *depth, int n, int H, int
         memcpy(&max_depth, &bits[f], 4);
         frustum_corners(max_depth, H, W, K, cam_poses + 16 * (size_t)f, out + 15 * (size_t)f);
     }
-    return HIVE_OK;
-}
-
-int hive_depth_apply_mask(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n, int H, int W, int iterations, int mode,
-                          int instance_id, float *d_out) {
-    HIVE_ENTER(ctx);
-    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, d_depth && d_mask && d_out, "depth_apply_mask: NULL argument");
-    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && iterations >= 0, "depth_apply_mask: bad arguments n=%d %dx%d, %d iterations", n, H, W, iterations);
-    HIVE_REQUIRE(ctx, mode == 0 || mode == 1, "depth_apply_mask: mode must be 0 (zero under the dilated mask) or 1 (keep the mask only)");
-    HIVE_REQUIRE(ctx, instance_id >= 0 && instance_id <= 255, "depth_apply_mask: instance id %d", instance_id);
-    const size_t n_px = (size_t)H * W, total = n_px * (size_t)n;
-    if (mode == 1) {
-        hipLaunchKernelGGL(keep_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_mask, total, instance_id, d_depth, d_out);
-    } else {
-        int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, total);
-        if (rc) return rc;
-        uint8_t *rows = (uint8_t *)ctx->d_scratch;
-        const dim3 grid((unsigned)((n_px + 255) / 256), n);
-        hipLaunchKernelGGL(dilate_rows_batch_kernel, grid, dim3(256), 0, ctx->stream, d_mask, H, W, iterations, instance_id, rows);
-        hipLaunchKernelGGL(dilate_cols_apply_kernel, grid, dim3(256), 0, ctx->stream, (const uint8_t *)rows, H, W, iterations, d_depth, d_out);
-    }
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
 }
 
@@ -487,111 +404,166 @@ static int check_se(hive_ctx *ctx, const uint8_t *se, int kh, int kw, Structurin
     HIVE_REQUIRE(ctx, any, "dilate: the structuring element has no set element");
     return HIVE_OK;
 }
-// `iterations` literal passes of the structuring element over n frames: d_in (instance ids on the first pass) -> result in *d_result
-// (one of the two scratch planes a, b; both n * H * W bytes)
-static int dilate_se_iterate(hive_ctx *ctx, const uint8_t *d_in, int n, int H, int W, const StructuringElement &se, int iterations, int instance, uint8_t *a,
-                             uint8_t *b, const uint8_t **d_result) {
-    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), n);
-    const uint8_t *src = d_in;
-    uint8_t *dst = a;
-    for (int it = 0; it < iterations; ++it) {
-        hipLaunchKernelGGL(dilate_se_kernel, grid, dim3(256), 0, ctx->stream, src, H, W, se, instance, it == 0 ? 1 : 0, dst);
-        src = dst;
-        dst = dst == a ? b : a;
+
+// One dilation of a frame set on the device, behind every entry point that dilates.  Sizes are the caller's to check; the element is checked here.
+struct DilateJob {
+    const uint8_t *mask;  // [n][H][W], device
+    int n, H, W;
+    int instance;       // "set" = this value; 0 = any non-zero value
+    const uint8_t *se;  // [kh][kw], host
+    int kh, kw, iterations;
+    uint8_t *a, *b;  // two scratch planes of n * H * W bytes (the separable path uses a alone)
+    // how it ends, one of: mask out -- the dilated masks (0 / 1) into out_mask, which may be b but neither a nor the input;
+    uint8_t *out_mask = nullptr;
+    // depth out -- out_depth = depth with zeros under the dilated masks (out_depth may be depth)
+    const float *depth = nullptr;
+    float *out_depth = nullptr;
+};
+static int dilate_run(hive_ctx *ctx, const DilateJob &j) {
+    StructuringElement el;
+    int rc = check_se(ctx, j.se, j.kh, j.kw, &el);
+    if (rc) return rc;
+    const size_t n_px = (size_t)j.H * j.W, total = n_px * (size_t)j.n;
+    const dim3 grid((unsigned)((n_px + 255) / 256), j.n), blk(256);
+    hipStream_t st = ctx->stream;
+    // THE rule: a full rectangle of odd sides iterated `iterations` times is one separable box of radii iterations * (kw / 2), iterations * (kh / 2); so are
+    // zero iterations of any element (radius 0: `mask != 0`, or `mask == instance`).  Anything else is iterated literally.
+    if (se_is_full_odd_rect(j.se, j.kh, j.kw) || j.iterations == 0) {
+        const int ru = j.iterations * (j.kw / 2), rv = j.iterations * (j.kh / 2);
+        hipLaunchKernelGGL(dilate_rows_batch_kernel, grid, blk, 0, st, j.mask, j.H, j.W, ru, j.instance, j.a);
+        if (j.out_depth)
+            hipLaunchKernelGGL(dilate_cols_apply_kernel, grid, blk, 0, st, (const uint8_t *)j.a, j.H, j.W, rv, j.depth, j.out_depth);
+        else
+            hipLaunchKernelGGL(dilate_cols_batch_kernel, grid, blk, 0, st, (const uint8_t *)j.a, j.H, j.W, rv, j.out_mask);
+    } else {
+        // the passes before the last alternate between a and b so that the last one reads a: its destination may be b
+        uint8_t *last = j.out_depth ? j.b : j.out_mask;
+        const uint8_t *src = j.mask;
+        for (int it = 0; it < j.iterations; ++it) {
+            uint8_t *dst = it == j.iterations - 1 ? last : ((j.iterations - it) & 1 ? j.b : j.a);
+            hipLaunchKernelGGL(dilate_se_kernel, grid, blk, 0, st, src, j.H, j.W, el, j.instance, it == 0 ? 1 : 0, dst);
+            src = dst;
+        }
+        if (j.out_depth) hipLaunchKernelGGL(zero_under_mask_kernel, dim3((unsigned)((total + 255) / 256)), blk, 0, st, (const uint8_t *)last, total, j.depth, j.out_depth);
     }
     HIVE_CHECK_HIP(ctx, hipGetLastError());
-    *d_result = src;
+    return HIVE_OK;
+}
+// the runner's two planes of `bytes` each, from the front of the generic scratch (stream order is all that protects it: every launch and copy of a job stays on
+// ctx->stream)
+static int dilate_planes(hive_ctx *ctx, size_t bytes, uint8_t **a, uint8_t **b) {
+    hive_scratch_layout lay;
+    lay.take<uint8_t>(bytes);
+    lay.take<uint8_t>(bytes);
+    int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, lay.bytes());
+    if (rc) return rc;
+    lay = hive_scratch_layout();
+    lay.base = (char *)ctx->d_scratch;
+    *a = lay.take<uint8_t>(bytes);
+    *b = lay.take<uint8_t>(bytes);
+    return HIVE_OK;
+}
+static const uint8_t BOX3[9] = {1, 1, 1, 1, 1, 1, 1, 1, 1};  // the reference's default element
+
+// hive_dilate_mask_se over a frame set on the device with the caller's planes (hive_internal.hpp; inpaint.hip dilates a batch's masks with it)
+int hive_dilate_frames(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, uint8_t *a, uint8_t *b) {
+    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && iterations >= 0, "dilate: bad arguments n=%d %dx%d, %d iterations", n, H, W, iterations);
+    DilateJob j{d_mask, n, H, W, 0, se, kh, kw, iterations, a, b};
+    j.out_mask = b;
+    return dilate_run(ctx, j);
+}
+
+// one mask in host or device memory: a host mask is staged in d_in and its result read back from plane b
+static int dilate_mask(hive_ctx *ctx, const uint8_t *mask, int H, int W, const uint8_t *se, int kh, int kw, int iterations, int mem, uint8_t *out) {
+    HIVE_REQUIRE(ctx, mask && out, "dilate_mask: NULL argument");
+    HIVE_REQUIRE(ctx, H > 0 && W > 0 && iterations >= 0, "dilate_mask: bad arguments %dx%d, %d iterations", H, W, iterations);
+    const size_t n = (size_t)H * W;
+    const bool host = mem == HIVE_MEM_HOST;
+    uint8_t *a, *b;
+    int rc = dilate_planes(ctx, n, &a, &b);
+    if (rc) return rc;
+    const void *d_mask;
+    if (host && (rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, n))) return rc;
+    if ((rc = to_device(ctx, mask, n, 0, mem, &d_mask))) return rc;
+    DilateJob j{(const uint8_t *)d_mask, 1, H, W, 0, se, kh, kw, iterations, a, b};
+    j.out_mask = host ? b : out;
+    if ((rc = dilate_run(ctx, j))) return rc;
+    if (host) {
+        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(out, b, n, hipMemcpyDeviceToHost, ctx->stream));
+        HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return HIVE_OK;
 }
 
-}  // extern "C"
-
-// hive_dilate_mask_se's two paths over a frame set on the device (hive_internal.hpp; inpaint.hip dilates a batch's masks with it)
-int hive_dilate_frames(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, uint8_t *a, uint8_t *b,
-                       const uint8_t **d_result) {
-    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && iterations >= 0, "dilate: bad arguments n=%d %dx%d, %d iterations", n, H, W, iterations);
-    StructuringElement el;
-    int rc = check_se(ctx, se, kh, kw, &el);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), n);
-    if (se_is_full_odd_rect(se, kh, kw) || iterations == 0) {  // (0 iterations: the box of radius 0 = `mask != 0`)
-        hipLaunchKernelGGL(dilate_rows_batch_kernel, grid, dim3(256), 0, ctx->stream, d_mask, H, W, iterations * (kw / 2), 0, a);
-        hipLaunchKernelGGL(dilate_cols_batch_kernel, grid, dim3(256), 0, ctx->stream, (const uint8_t *)a, H, W, iterations * (kh / 2), b);
+// the depth maps of a frame set with a mask applied: mode 1 keeps the UNDILATED mask (no element), mode 0 zeroes under the dilated one
+static int depth_apply_mask(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, int mode,
+                            int instance_id, float *d_out) {
+    HIVE_REQUIRE(ctx, d_depth && d_mask && d_out, "depth_apply_mask: NULL argument");
+    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && iterations >= 0, "depth_apply_mask: bad arguments n=%d %dx%d, %d iterations", n, H, W, iterations);
+    HIVE_REQUIRE(ctx, mode == 0 || mode == 1, "depth_apply_mask: mode must be 0 (zero under the dilated mask) or 1 (keep the mask only)");
+    HIVE_REQUIRE(ctx, instance_id >= 0 && instance_id <= 255, "depth_apply_mask: instance id %d", instance_id);
+    const size_t total = (size_t)H * W * (size_t)n;
+    if (mode == 1) {
+        hipLaunchKernelGGL(keep_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_mask, total, instance_id, d_depth, d_out);
         HIVE_CHECK_HIP(ctx, hipGetLastError());
-        *d_result = b;
         return HIVE_OK;
     }
-    return dilate_se_iterate(ctx, d_mask, n, H, W, el, iterations, 0, a, b, d_result);
+    uint8_t *a, *b;
+    int rc = dilate_planes(ctx, total, &a, &b);
+    if (rc) return rc;
+    DilateJob j{d_mask, n, H, W, instance_id, se, kh, kw, iterations, a, b};
+    j.depth = d_depth;
+    j.out_depth = d_out;
+    return dilate_run(ctx, j);
 }
 
 extern "C" {
 
+int hive_view_frustum(hive_ctx *ctx, const float *depth, int H, int W, const float K[9], const double cam_pose[16], int mem,
+                      double out[15]) {
+    HIVE_ENTER(ctx);
+    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
+    HIVE_REQUIRE(ctx, depth && K && cam_pose && out, "view_frustum: NULL argument");
+    HIVE_REQUIRE(ctx, H > 0 && W > 0, "view_frustum: bad image size %dx%d", H, W);
+    return view_frusta(ctx, depth, 1, H, W, K, cam_pose, mem, 1024, out);  // (one frame: up to 1024 workgroups)
+}
+
+int hive_view_frustum_batch(hive_ctx *ctx, const float *depth, int n, int H, int W, const float K[9], const double *cam_poses, int mem,
+                            double *out) {
+    HIVE_ENTER(ctx);
+    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
+    HIVE_REQUIRE(ctx, depth && K && cam_poses && out, "view_frustum_batch: NULL argument");
+    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), "view_frustum_batch: bad sizes n=%d %dx%d", n, H, W);
+    return view_frusta(ctx, depth, n, H, W, K, cam_poses, mem, 64, out);  // (a frame set: up to 64 workgroups per frame)
+}
+
+int hive_dilate_mask(hive_ctx *ctx, const uint8_t *mask, int H, int W, int iterations, int mem, uint8_t *out) {
+    HIVE_ENTER(ctx);
+    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
+    return dilate_mask(ctx, mask, H, W, BOX3, 3, 3, iterations, mem, out);
+}
+
 int hive_dilate_mask_se(hive_ctx *ctx, const uint8_t *mask, int H, int W, const uint8_t *se, int kh, int kw, int iterations, int mem, uint8_t *out) {
     HIVE_ENTER(ctx);
     if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, mask && out, "dilate_mask: NULL argument");
-    HIVE_REQUIRE(ctx, H > 0 && W > 0 && iterations >= 0, "dilate_mask: bad arguments %dx%d, %d iterations", H, W, iterations);
-    StructuringElement el;
-    int rc = check_se(ctx, se, kh, kw, &el);
-    if (rc) return rc;
-    const size_t n = (size_t)H * W;
-    const bool host = mem == HIVE_MEM_HOST;
-    // planes: [0] the input (host calls), [1], [2] ping-pong
-    if ((rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, 3 * align256(n)))) return rc;
-    uint8_t *base = (uint8_t *)ctx->d_in;
-    const uint8_t *d_mask = mask;
-    if (host) {
-        const void *dm;
-        if ((rc = to_device(ctx, mask, n, 0, mem, &dm))) return rc;
-        d_mask = (const uint8_t *)dm;
-    }
-    uint8_t *a = base + align256(n), *b = base + 2 * align256(n);
-    const uint8_t *res;
-    if (se_is_full_odd_rect(se, kh, kw)) {
-        const dim3 grid((unsigned)((n + 255) / 256));
-        hipLaunchKernelGGL(dilate_rows_kernel, grid, dim3(256), 0, ctx->stream, d_mask, H, W, iterations * (kw / 2), a);
-        hipLaunchKernelGGL(dilate_cols_kernel, grid, dim3(256), 0, ctx->stream, (const uint8_t *)a, H, W, iterations * (kh / 2), b);
-        HIVE_CHECK_HIP(ctx, hipGetLastError());
-        res = b;
-    } else if (iterations == 0) {  // cv2.dilate(iterations=0) copies; astype(bool) on the way out
-        hipLaunchKernelGGL(dilate_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_mask, H, W, 0, a);
-        HIVE_CHECK_HIP(ctx, hipGetLastError());
-        res = a;
-    } else if ((rc = dilate_se_iterate(ctx, d_mask, 1, H, W, el, iterations, 0, a, b, &res))) {
-        return rc;
-    }
-    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(out, res, n, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    if (host) HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return HIVE_OK;
+    return dilate_mask(ctx, mask, H, W, se, kh, kw, iterations, mem, out);
+}
+
+int hive_depth_apply_mask(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n, int H, int W, int iterations, int mode,
+                          int instance_id, float *d_out) {
+    HIVE_ENTER(ctx);
+    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
+    return depth_apply_mask(ctx, d_depth, d_mask, n, H, W, BOX3, 3, 3, iterations, mode, instance_id, d_out);
 }
 
 int hive_depth_apply_mask_se(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations,
                              int mode, int instance_id, float *d_out) {
     HIVE_ENTER(ctx);
     if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    StructuringElement el;
+    StructuringElement el;  // this entry point refuses a bad element before anything else, in mode 1 too, which has no use for it
     int rc = check_se(ctx, se, kh, kw, &el);
     if (rc) return rc;
-    if (mode == 1) return hive_depth_apply_mask(ctx, d_depth, d_mask, n, H, W, iterations, mode, instance_id, d_out);  // the foreground keeps the UNDILATED mask
-    HIVE_REQUIRE(ctx, d_depth && d_mask && d_out, "depth_apply_mask: NULL argument");
-    HIVE_REQUIRE(ctx, n > 0 && n <= 65535 && H > 0 && W > 0 && iterations >= 0, "depth_apply_mask: bad arguments n=%d %dx%d, %d iterations", n, H, W, iterations);
-    HIVE_REQUIRE(ctx, mode == 0, "depth_apply_mask: mode must be 0 (zero under the dilated mask) or 1 (keep the mask only)");
-    HIVE_REQUIRE(ctx, instance_id >= 0 && instance_id <= 255, "depth_apply_mask: instance id %d", instance_id);
-    if (kh % 2 == 1 && kh == kw && se_is_full_odd_rect(se, kh, kw))  // square box: the separable two-launch path (radius iterations * (k / 2))
-        return hive_depth_apply_mask(ctx, d_depth, d_mask, n, H, W, iterations * (kh / 2), mode, instance_id, d_out);
-    const size_t total = (size_t)H * W * (size_t)n;
-    if ((rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, 2 * align256(total)))) return rc;
-    uint8_t *a = (uint8_t *)ctx->d_scratch, *b = a + align256(total);
-    const uint8_t *res;
-    // (at least one literal pass, so that instance ids become set / clear; zero iterations = the undilated mask: a 1x1 pass)
-    StructuringElement one;
-    one.kh = one.kw = 1;
-    memset(one.m, 0, sizeof(one.m));
-    one.m[0] = 1;
-    if ((rc = dilate_se_iterate(ctx, d_mask, n, H, W, iterations ? el : one, iterations ? iterations : 1, instance_id, a, b, &res))) return rc;
-    hipLaunchKernelGGL(zero_under_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, res, total, d_depth, d_out);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    return HIVE_OK;
+    return depth_apply_mask(ctx, d_depth, d_mask, n, H, W, se, kh, kw, iterations, mode, instance_id, d_out);
 }
 
 int hive_depth_mm_to_m(hive_ctx *ctx, const uint16_t *d_mm, int64_t n, float depth_scale, float max_depth, float *d_out) {
@@ -630,7 +602,7 @@ int hive_unproject(hive_ctx *ctx, const float *depth, const uint8_t *mask, const
     unsigned *blk = mem == HIVE_MEM_HOST ? (unsigned *)((char *)ctx->d_in + off_blk) : (unsigned *)ctx->d_scratch;
     double *d_xyz = mem == HIVE_MEM_HOST ? (double *)((char *)ctx->d_in + off_xyz) : out_xyz;
     uint8_t *d_rgba = !out_rgba ? nullptr : (mem == HIVE_MEM_HOST ? (uint8_t *)ctx->d_in + off_rgba : out_rgba);
-    unsigned long long *d_total = (unsigned long long *)(ctx->d_scalars + 20);
+    unsigned long long *d_total = (unsigned long long *)(ctx->d_scalars + SC_UNPROJECT_TOTAL);
     hipLaunchKernelGGL(unproject_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)d_depth, (const uint8_t *)d_mask, n, blk);
     hipLaunchKernelGGL(scan1_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, d_total);
     UnprojectParams p;
@@ -743,7 +715,7 @@ int hive_project_bbox(hive_ctx *ctx, const double *points, int64_t n, const doub
     const void *d_pts;
     if (mem == HIVE_MEM_HOST && (rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, (size_t)n * 24))) return rc;
     if ((rc = to_device(ctx, points, (size_t)n * 24, 0, mem, &d_pts))) return rc;
-    int *d_out = (int *)(ctx->d_scalars + 24);
+    int *d_out = (int *)(ctx->d_scalars + SC_PROJECT_BBOX);
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
     ProjectParams p;
     memcpy(p.K, K, sizeof(p.K));
@@ -755,38 +727,6 @@ int hive_project_bbox(hive_ctx *ctx, const double *points, int64_t n, const doub
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
     HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return HIVE_OK;
-}
-
-int hive_dilate_mask(hive_ctx *ctx, const uint8_t *mask, int H, int W, int iterations, int mem, uint8_t *out) {
-    HIVE_ENTER(ctx);
-    if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
-    HIVE_REQUIRE(ctx, mask && out, "dilate_mask: NULL argument");
-    HIVE_REQUIRE(ctx, H > 0 && W > 0 && iterations >= 0, "dilate_mask: bad arguments %dx%d, %d iterations", H, W, iterations);
-    const size_t n = (size_t)H * W;
-    int rc;
-    const size_t off_tmp = align256(n), off_out = 2 * align256(n);
-    const void *d_mask;
-    uint8_t *d_tmp, *d_out;
-    if (mem == HIVE_MEM_HOST) {
-        if ((rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, 3 * align256(n)))) return rc;
-        if ((rc = to_device(ctx, mask, n, 0, mem, &d_mask))) return rc;
-        d_tmp = (uint8_t *)ctx->d_in + off_tmp;
-        d_out = (uint8_t *)ctx->d_in + off_out;
-    } else {
-        if ((rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, n))) return rc;
-        d_mask = mask;
-        d_tmp = (uint8_t *)ctx->d_scratch;
-        d_out = out;
-    }
-    const dim3 grid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(dilate_rows_kernel, grid, dim3(256), 0, ctx->stream, (const uint8_t *)d_mask, H, W, iterations, d_tmp);
-    hipLaunchKernelGGL(dilate_cols_kernel, grid, dim3(256), 0, ctx->stream, (const uint8_t *)d_tmp, H, W, iterations, d_out);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    if (mem == HIVE_MEM_HOST) {
-        HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        HIVE_CHECK_HIP(ctx, hipMemcpy(out, d_out, n, hipMemcpyDeviceToHost));
-    }
     return HIVE_OK;
 }
 

@@ -44,9 +44,9 @@ struct hive_ctx {
     void *d_in = nullptr;  // device copy of host inputs
     size_t in_bytes = 0;
     int tsdf_scalars = 0;           // which of the two TSDF scalar blocks the frame in flight uses (tsdf.hip prepare_frame)
-    int tsdf_multi_scalars = 0;     // the same for the multi-frame sweep's blocks (d_scalars + 64 / + 80)
-    unsigned *d_scalars = nullptr;  // [0]=max depth bits, [2..3]=u64 counter, ...
-    void *h_pinned_small = nullptr;  // 256 bytes of pinned host memory for small read-backs (mesh totals)
+    int tsdf_multi_scalars = 0;     // the same for the fused sweep's blocks (SC_TSDF_SWEEP_A / _B)
+    unsigned *d_scalars = nullptr;  // HIVE_SCALAR_WORDS words of small results and counters: the map of its regions is below (SC_*)
+    void *h_pinned_small = nullptr;  // 256 bytes of pinned host memory for small read-backs (mesh totals), allocated on first use: hive_pinned_small
     void *d_zeros = nullptr;        // 256 bytes of zeros: the source of padding taps in the implicit-GEMM convolutions
     // split-K of the MFMA tile kernels at small batches (mfma_pipe.hpp splitk_*): f32 partial tiles + one arrival counter per tile (zero between launches)
     void *d_splitk = nullptr;
@@ -67,6 +67,45 @@ struct hive_ctx {
     size_t ev_used = 0;
     hipEvent_t last_start = nullptr, last_stop = nullptr;
 };
+
+// The map of hive_ctx::d_scalars: every region, offset and extent in words, in ascending order.  A new user takes a gap (or the tail) and adds its
+// line here and to HIVE_SCALAR_MAP; the static_assert below refuses regions that overlap or leave the allocation.  Offsets INSIDE a region
+// (MS_NITEMS, MS_HIST, ... of a sweep block, the [4] of a per-frame block) belong to the kernels that use them and stay beside those kernels.
+constexpr int HIVE_SCALAR_WORDS = 4096;                // what hive_ctx_create allocates and zeroes
+constexpr int COUNT_SLOTS = 64, COUNT_STRIDE = 16;     // update counters of the TSDF COUNT kernels: 64 x u64, 128 bytes apart
+constexpr int MS_STRIDE = 512;                         // words of one scalar block of a fused TSDF sweep
+constexpr int SC_TSDF_FRAME_WORDS = 8;                 // words of one per-frame TSDF block (prep_frame_kernel clears the other block: this many)
+constexpr int SC_TSDF_FRAME_A = 0;                     // tsdf.hip: the two per-frame blocks alternate (A here, B below)
+constexpr int SC_MC_TOTALS = 8, SC_MC_TOTALS_WORDS = 4;            // mcubes.hip: vertex and face totals of an extraction (2 x u64)
+constexpr int SC_UNPROJECT_TOTAL = 20, SC_UNPROJECT_TOTAL_WORDS = 2;  // geometry.hip hive_unproject: the point count (u64)
+constexpr int SC_PROJECT_BBOX = 24, SC_PROJECT_BBOX_WORDS = 5;     // geometry.hip hive_project_bbox: min u, max u, min v, max v, count
+constexpr int SC_GRID_TOTALS = 32, SC_GRID_TOTALS_WORDS = 2;       // fgmesh.hip hive_grid_mesh: vertices, faces
+constexpr int SC_FILTER_TOTAL = 34, SC_FILTER_TOTAL_WORDS = 1;     // fgmesh.hip hive_filter_faces: faces kept
+constexpr int SC_WINDOW_BOX = 40, SC_WINDOW_BOX_WORDS = 4;         // fgmesh.hip hive_texture_window: the box of the projected points
+constexpr int SC_TSDF_FRAME_B = 48;                                // tsdf.hip: the other per-frame block
+constexpr int SC_TSDF_COUNTERS = 128, SC_TSDF_COUNTERS_WORDS = COUNT_SLOTS * COUNT_STRIDE * 2;  // tsdf.hip: COUNT_SLOTS * COUNT_STRIDE u64s
+constexpr int MS_BASE = 2304;                          // tsdf.hip: the two alternating blocks of the fused sweep, MS_STRIDE words each
+constexpr int CC_SCALARS = 3584, CC_SCALARS_WORDS = 14;            // fgmesh.hip: the clean-up's / the frame mesh runner's block, [0..13]
+constexpr int DEC_SCALARS = 3712, DEC_SCALARS_WORDS = 20;          // decimate.hip: [0..15] hive_decimate_run, [16..19] hive_mesh_decimate's counts
+struct hive_scalar_region {
+    int at, words;
+};
+constexpr hive_scalar_region HIVE_SCALAR_MAP[] = {
+    {SC_TSDF_FRAME_A, SC_TSDF_FRAME_WORDS},          {SC_MC_TOTALS, SC_MC_TOTALS_WORDS},       {SC_UNPROJECT_TOTAL, SC_UNPROJECT_TOTAL_WORDS},
+    {SC_PROJECT_BBOX, SC_PROJECT_BBOX_WORDS},        {SC_GRID_TOTALS, SC_GRID_TOTALS_WORDS},   {SC_FILTER_TOTAL, SC_FILTER_TOTAL_WORDS},
+    {SC_WINDOW_BOX, SC_WINDOW_BOX_WORDS},            {SC_TSDF_FRAME_B, SC_TSDF_FRAME_WORDS},   {SC_TSDF_COUNTERS, SC_TSDF_COUNTERS_WORDS},
+    {MS_BASE, MS_STRIDE},                            {MS_BASE + MS_STRIDE, MS_STRIDE},         {CC_SCALARS, CC_SCALARS_WORDS},
+    {DEC_SCALARS, DEC_SCALARS_WORDS},
+};
+constexpr bool hive_scalar_map_ok() {
+    int end = 0;
+    for (const hive_scalar_region &r : HIVE_SCALAR_MAP) {
+        if (r.at < end || r.words <= 0) return false;
+        end = r.at + r.words;
+    }
+    return end <= HIVE_SCALAR_WORDS;
+}
+static_assert(hive_scalar_map_ok(), "hive_ctx::d_scalars: each region starts at or after the end of the one before it, and the last ends inside the allocation");
 
 int hive_fail(hive_ctx *ctx, int code, const char *fmt, ...);
 
@@ -115,6 +154,8 @@ struct hive_device_latch {
 
 // grows *ptr to at least `bytes` of device memory
 int hive_reserve_device(hive_ctx *ctx, void **ptr, size_t *cur, size_t bytes);
+// the context's 256 bytes of pinned host memory for small read-backs (allocated on first use)
+int hive_pinned_small(hive_ctx *ctx, void **out);
 // copies `bytes` from host memory to device memory `dst` through the pinned ring; returns once the
 // host buffer may be reused by the caller
 int hive_upload(hive_ctx *ctx, void *dst, const void *src, size_t bytes);
@@ -173,9 +214,8 @@ int32_t *hive_decimate_vmap(void *scratch, long long vert_cap, long long face_ca
 // runs every round (polling the device between batches of rounds) and the output compaction on ctx->stream; stats = {rounds, collapses, locked vertices}
 int hive_decimate_run(hive_ctx *ctx, const hive_dec_job &job, void *scratch, int64_t stats[3]);
 // geometry.hip: hive_dilate_mask_se over n frames on the device (se in host memory).  a, b: two planes of n * H * W bytes; the dilated masks
-// (0 / 1) are left in *d_result, which is one of them
-int hive_dilate_frames(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, uint8_t *a, uint8_t *b,
-                       const uint8_t **d_result);
+// (0 / 1) are left in b
+int hive_dilate_frames(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, const uint8_t *se, int kh, int kw, int iterations, uint8_t *a, uint8_t *b);
 // event helpers for kernel timing
 int hive_time_begin(hive_ctx *ctx);
 int hive_time_end(hive_ctx *ctx);

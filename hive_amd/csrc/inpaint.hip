@@ -377,7 +377,8 @@ int hive_inpaint_frames(hive_ctx *ctx, const uint8_t *d_rgb, const uint16_t *d_d
         HIVE_REQUIRE(ctx, dilate_kh >= 1 && dilate_kw >= 1 && dilate_kh <= 32 && dilate_kw <= 32, "inpaint_frames: dilation element %dx%d", dilate_kh, dilate_kw);
         uint8_t ones[32 * 32];
         memset(ones, 1, sizeof(ones));
-        if ((rc = hive_dilate_frames(ctx, d_mask, n, H, W, ones, dilate_kh, dilate_kw, dilate_iterations, a, b, &d_holes))) return rc;
+        if ((rc = hive_dilate_frames(ctx, d_mask, n, H, W, ones, dilate_kh, dilate_kw, dilate_iterations, a, b))) return rc;
+        d_holes = b;
     }
     if (d_rgb && d_rgb_out != d_rgb) HIVE_CHECK_HIP(ctx, hipMemcpyAsync(d_rgb_out, d_rgb, total * 3, hipMemcpyDeviceToDevice, ctx->stream));
     if (d_depth && d_depth_out != d_depth) HIVE_CHECK_HIP(ctx, hipMemcpyAsync(d_depth_out, d_depth, total * 2, hipMemcpyDeviceToDevice, ctx->stream));

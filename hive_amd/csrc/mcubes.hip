@@ -386,14 +386,15 @@ int hive_tsdf_extract_mesh(hive_tsdf *v, int64_t *n_verts, int64_t *n_faces) {
         hipLaunchKernelGGL(mc_signs_row_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream, v->d_tsdf, p.Z, p.WZ, n_words, d_sign);
     if ((rc = hive_reserve_device(ctx, (void **)&v->d_blk, &v->blk_bytes, 2 * (size_t)nb * sizeof(unsigned)))) return rc;
     unsigned *blk_v = v->d_blk, *blk_t = v->d_blk + nb;
-    unsigned long long *d_tot = (unsigned long long *)(ctx->d_scalars + 8);
+    unsigned long long *d_tot = (unsigned long long *)(ctx->d_scalars + SC_MC_TOTALS);
     hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nb), dim3(MC_BLOCK), 0, ctx->stream, p, n_words, blk_v, blk_t);
     hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk_v, blk_t, (int)nb, d_tot);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     // the ONE read-back of an extraction: vertex and face totals, through pinned memory (a copy into pageable memory is staged by the runtime)
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
-    volatile unsigned long long *tot = (volatile unsigned long long *)ctx->h_pinned_small;
-    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_pinned_small, d_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    void *pinned;
+    if ((rc = hive_pinned_small(ctx, &pinned))) return rc;
+    volatile unsigned long long *tot = (volatile unsigned long long *)pinned;
+    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(pinned, d_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (tot[0] == 0) {
         v->n_verts = v->n_faces = -1;

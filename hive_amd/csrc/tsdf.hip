@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void prep_frame_kernel(const float *__restrict
 #endif
 constexpr int SEG_LANES = HIVE_SEG_LANES;
 constexpr int VPT = 4;  // consecutive z voxels per lane: one 16-byte access per lane and volume plane
-constexpr int COUNT_SLOTS = 64, COUNT_STRIDE = 16;  // update counters of the COUNT kernels: 64 x u64, 128 bytes apart (hive_ctx::d_scalars + 128)
+// (update counters of the COUNT kernels: COUNT_SLOTS x u64, COUNT_STRIDE u64s = 128 bytes apart, at hive_ctx::d_scalars + SC_TSDF_COUNTERS: hive_internal.hpp)
 struct WorkItem {
     unsigned xy;  // x | y << 16
     unsigned zz;  // segment start z | (voxels of the segment inside the row's interval - 1) << 16 | frames whose own interval meets the segment << 22 | image band << 26
@@ -774,7 +774,7 @@ struct MultiParams {
 
 // scalar block of a fused sweep (two alternate, hive_ctx::d_scalars + MS_BASE + which * MS_STRIDE): [MS_NITEMS] work-list length, [MS_HIST ..] items
 // per image band, [MS_CURSOR ..] the sort's per-band write cursors; the sweep's first kernel clears the OTHER block's first MS_CLEAR words
-constexpr int MS_BASE = 2304, MS_STRIDE = 512, MS_NITEMS = MAXF, MS_HIST = 8, MS_CURSOR = MS_HIST + NBINS, MS_CLEAR = MS_CURSOR + NBINS;
+constexpr int MS_NITEMS = MAXF, MS_HIST = 8, MS_CURSOR = MS_HIST + NBINS, MS_CLEAR = MS_CURSOR + NBINS;
 
 __global__ __launch_bounds__(1024) void build_worklist_multi_kernel(MultiParams mp, WorkItem *__restrict__ items, unsigned *n_items, unsigned *hist) {
     __shared__ unsigned wave_sum[16];
@@ -1169,8 +1169,8 @@ static int fill_volume(hive_tsdf *v) {
     return HIVE_OK;
 }
 
-// the scalar block of the frame in flight: d_scalars[0..7] or d_scalars[48..55]
-static inline unsigned *tsdf_scalars(hive_ctx *ctx) { return ctx->d_scalars + (ctx->tsdf_scalars ? 48 : 0); }
+// the scalar block of the frame in flight: one of the two SC_TSDF_FRAME_WORDS-word blocks
+static inline unsigned *tsdf_scalars(hive_ctx *ctx) { return ctx->d_scalars + (ctx->tsdf_scalars ? SC_TSDF_FRAME_B : SC_TSDF_FRAME_A); }
 
 // tiles of (32 << shift)^2 pixels, the smallest shift with at most MAX_TILES tiles (the work-list kernels keep MAXF tables in LDS)
 struct TileGrid {
@@ -1211,19 +1211,19 @@ static int prepare_frame(hive_tsdf *v, const uint8_t *color, const float *depth,
     const size_t tex_bytes = (npx * sizeof(uint2) + 255) & ~(size_t)255;
     int rc = hive_reserve_device(ctx, &ctx->d_frame, &ctx->frame_bytes, tex_bytes + MAX_TILES * sizeof(unsigned));
     if (rc) return rc;
-    // scalar block of this frame: [4] work-list length (update counters: d_scalars + 128).  Two blocks alternate (both zero after
+    // scalar block of this frame: [4] work-list length (update counters: d_scalars + SC_TSDF_COUNTERS).  Two blocks alternate (both zero after
     // hive_ctx_create); the prep kernel of a frame clears the block of the next one.
     ctx->tsdf_scalars ^= 1;
-    unsigned *next = ctx->d_scalars + (ctx->tsdf_scalars ? 0 : 48);
+    unsigned *next = ctx->d_scalars + (ctx->tsdf_scalars ? SC_TSDF_FRAME_A : SC_TSDF_FRAME_B);
     unsigned *tiles = (unsigned *)((char *)ctx->d_frame + tex_bytes);
     const bool vec = W % 4 == 0 && ((uintptr_t)*d_depth % 16 == 0) && ((uintptr_t)*d_color % 4 == 0);
     const dim3 grid((unsigned)(tg.tiles_x * tg.tiles_y), 1);
     if (vec)
         hipLaunchKernelGGL(prep_frame_kernel<true>, grid, dim3(256), 0, ctx->stream, *d_depth, *d_color, H, W, tg.shift, tg.tiles_x, (uint2 *)ctx->d_frame, tiles,
-                           MAX_TILES, next, 8);
+                           MAX_TILES, next, SC_TSDF_FRAME_WORDS);
     else
         hipLaunchKernelGGL(prep_frame_kernel<false>, grid, dim3(256), 0, ctx->stream, *d_depth, *d_color, H, W, tg.shift, tg.tiles_x, (uint2 *)ctx->d_frame, tiles,
-                           MAX_TILES, next, 8);
+                           MAX_TILES, next, SC_TSDF_FRAME_WORDS);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
 }
@@ -1380,7 +1380,7 @@ static int launch_integrate(hive_tsdf *v, float *accum, int H, int W, const floa
     fill_frame_params(v, H, W, K, pose, obs_weight, p);
     p.frame = (const uint2 *)ctx->d_frame;
     p.tile_max = (const unsigned *)((const char *)ctx->d_frame + (((size_t)H * W * sizeof(uint2) + 255) & ~(size_t)255));
-    p.n_updated = (unsigned long long *)(ctx->d_scalars + 128);
+    p.n_updated = (unsigned long long *)(ctx->d_scalars + SC_TSDF_COUNTERS);
     if (count) HIVE_CHECK_HIP(ctx, hipMemsetAsync(p.n_updated, 0, COUNT_SLOTS * COUNT_STRIDE * sizeof(unsigned long long), ctx->stream));
     const long long rows = (long long)p.X * p.Y;
     float *a0 = ACCUM ? accum : v->d_tsdf;
@@ -1601,7 +1601,7 @@ int hive_tsdf_integrate(hive_tsdf *vol, const uint8_t *color, const float *depth
     vol->n_verts = vol->n_faces = -1;
     if (n_updated) {
         unsigned long long slots[COUNT_SLOTS * COUNT_STRIDE];
-        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(slots, ctx->d_scalars + 128, sizeof(slots), hipMemcpyDeviceToHost, ctx->stream));
+        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(slots, ctx->d_scalars + SC_TSDF_COUNTERS, sizeof(slots), hipMemcpyDeviceToHost, ctx->stream));
         HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         unsigned long long n = 0;
         for (int i = 0; i < COUNT_SLOTS; ++i) n += slots[i * COUNT_STRIDE];

@@ -354,7 +354,8 @@ int hive_fts_optimise(hive_ctx *ctx, double *params, const double *gt_params, co
 
 /* ---- dilate_mask(mask, MaskDilationOptions(num_iterations)) -- hive/image_processing.py:30-45 */
 /* 3x3 rectangular structuring element applied `iterations` times == one (2*it+1)^2 box max
- * (cv2.dilate border = no contribution from outside).  mask/out u8 [H][W], non-zero = set. */
+ * (cv2.dilate border = no contribution from outside).  mask/out u8 [H][W], non-zero = set; out is written as 0 / 1 and must not
+ * overlap mask (both functions). */
 int hive_dilate_mask(hive_ctx *ctx, const uint8_t *mask, int H, int W, int iterations, int mem,
                      uint8_t *out);
 

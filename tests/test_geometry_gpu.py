@@ -127,6 +127,34 @@ def test_dilate_mask_matches_oracle(gpu_ctx, oracle_lib):
         dilate_mask(np.zeros((2, 3, 4)), MaskDilationOptions(1))
 
 
+def test_dilate_mask_c_abi_matches_oracle_and_se(gpu_ctx, oracle_lib):
+    """`hive_dilate_mask` (the 3 x 3 box, which no Python wrapper calls) straight through the C ABI, from host and from device memory: byte for byte the
+    oracle's literal iterated dilation and `hive_dilate_mask_se` with a 3 x 3 element of ones.  13 x 37: no multiple of 4, set pixels in all four corners."""
+    import torch
+    from hive_amd._lib import MEM_DEVICE, MEM_HOST, ptr
+    ctx = gpu_ctx
+    rng = np.random.default_rng(21)
+    m = rng.integers(0, 256, (13, 37)).astype(np.uint8) * (rng.random((13, 37)) < 0.02)
+    m[0, 0], m[0, -1], m[-1, 0], m[-1, -1] = 1, 255, 7, 128
+    box = np.ones((3, 3), np.uint8)
+    for mask in (m, np.array([[9]], np.uint8), np.zeros((1, 1), np.uint8)):
+        h, w = mask.shape
+        for it in (0, 1, 4):
+            expect = oracle_lib.dilate_mask(mask, it).astype(np.uint8)
+            assert it == 0 or mask.size == 1 or 0 < expect.sum() < expect.size
+            out, out_se = np.full_like(mask, 77), np.full_like(mask, 77)
+            ctx.check(ctx.lib.hive_dilate_mask(ctx.handle, ptr(mask), h, w, it, MEM_HOST, ptr(out)))
+            ctx.check(ctx.lib.hive_dilate_mask_se(ctx.handle, ptr(mask), h, w, ptr(box), 3, 3, it, MEM_HOST, ptr(out_se)))
+            assert np.array_equal(out, expect) and np.array_equal(out_se, expect), (mask.shape, it, "host")
+            d_mask = torch.from_numpy(mask).cuda()
+            d_out, d_out_se = torch.full_like(d_mask, 77), torch.full_like(d_mask, 77)
+            ctx.check(ctx.lib.hive_dilate_mask(ctx.handle, ptr(d_mask), h, w, it, MEM_DEVICE, ptr(d_out)))
+            ctx.check(ctx.lib.hive_dilate_mask_se(ctx.handle, ptr(d_mask), h, w, ptr(box), 3, 3, it, MEM_DEVICE, ptr(d_out_se)))
+            torch.cuda.synchronize()
+            assert np.array_equal(d_out.cpu().numpy(), expect) and np.array_equal(d_out_se.cpu().numpy(), expect), (mask.shape, it, "device")
+            assert np.array_equal(d_mask.cpu().numpy(), mask), "the input is left alone"
+
+
 def test_dilate_mask_any_structuring_element_matches_oracle(gpu_ctx, oracle_lib):
     """`MaskDilationOptions(num_iterations, dilation_filter)` with filters other than the default 3x3 box
     (/root/reference/hive/options.py:245-268): cross, ellipse-like, asymmetric, even-sized, a non-square rectangle (separable path)

@@ -176,18 +176,23 @@ def test_accumulate_stream_then_fuse_single_rank(gpu_ctx, oracle_lib):
 
 def test_view_frusta_batch_equals_single_calls(gpu_ctx, oracle_lib, small_sequence):
     """The bounds pass for a whole frame set in one launch == n calls of get_view_frustum == the oracle, bit for bit,
-    from host arrays and from depth maps already in HBM."""
+    from host arrays and from depth maps already in HBM.  The last frame has no depth at all: its maximum word stays 0."""
     import torch
     from hive_amd import fusion
     seq = small_sequence
-    batch = fusion.view_frusta(seq["depth"], seq["K"], seq["poses"], ctx=gpu_ctx)
-    batch_dev = fusion.view_frusta(torch.from_numpy(seq["depth"]).cuda(), seq["K"], seq["poses"], ctx=gpu_ctx)
-    assert batch.shape == (8, 3, 5) and np.array_equal(batch, batch_dev)
-    for i in range(8):
-        single = fusion.get_view_frustum(seq["depth"][i], seq["K"], seq["poses"][i], ctx=gpu_ctx)
+    depth = np.concatenate([seq["depth"], np.zeros_like(seq["depth"][:1])])
+    poses = np.concatenate([seq["poses"], seq["poses"][3:4]])
+    color = np.concatenate([seq["color"], seq["color"][:1]])
+    n = len(depth)
+    assert n == 9 and np.isfinite(oracle_lib.view_frustum(depth[-1], seq["K"], poses[-1])).all()
+    batch = fusion.view_frusta(depth, seq["K"], poses, ctx=gpu_ctx)
+    batch_dev = fusion.view_frusta(torch.from_numpy(depth).cuda(), seq["K"], poses, ctx=gpu_ctx)
+    assert batch.shape == (n, 3, 5) and np.array_equal(batch, batch_dev)
+    for i in range(n):
+        single = fusion.get_view_frustum(depth[i], seq["K"], poses[i], ctx=gpu_ctx)
         assert np.array_equal(batch[i], single)
-        assert np.array_equal(batch[i], oracle_lib.view_frustum(seq["depth"][i], seq["K"], seq["poses"][i]))
-    frames = fusion.DeviceFrames(torch.from_numpy(seq["color"]).cuda(), torch.from_numpy(seq["depth"]).cuda(), seq["poses"])
+        assert np.array_equal(batch[i], oracle_lib.view_frustum(depth[i], seq["K"], poses[i]))
+    frames = fusion.DeviceFrames(torch.from_numpy(color).cuda(), torch.from_numpy(depth).cuda(), poses)
     bnds = fusion.scene_bounds(frames, seq["K"], ctx=gpu_ctx)
     assert np.array_equal(bnds[:, 0], np.minimum(0, batch.min(axis=(0, 2)))) and np.array_equal(bnds[:, 1], np.maximum(0, batch.max(axis=(0, 2))))
 
@@ -218,7 +223,9 @@ def test_depth_apply_mask_matches_oracle(gpu_ctx, oracle_lib, iterations):
     assert (bg == 0).any() and (fg2 > 0).any()
     # the same with structuring elements other than the 3 x 3 box (MaskDilationOptions.filter, hive/options.py:245-268), per instance too
     cross = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], np.uint8)
-    for se in (cross, np.ones((5, 5), np.uint8), np.ones((2, 3), np.uint8), np.array([[1, 0, 0], [0, 0, 0], [0, 0, 1]], np.uint8)):
+    # (3 x 5 and 5 x 3: full odd rectangles that are not square, one separable box like the 5 x 5; 1 x 1: radius 0)
+    for se in (cross, np.ones((5, 5), np.uint8), np.ones((2, 3), np.uint8), np.array([[1, 0, 0], [0, 0, 0], [0, 0, 1]], np.uint8), np.ones((3, 5), np.uint8),
+               np.ones((5, 3), np.uint8), np.ones((1, 1), np.uint8)):
         bg_se = frames.masked_depth(iterations, fusion.MASK_BACKGROUND, ctx=gpu_ctx, dilation_filter=se).cpu().numpy()
         bg_se2 = frames.masked_depth(iterations, fusion.MASK_BACKGROUND, instance_id=2, ctx=gpu_ctx, dilation_filter=se).cpu().numpy()
         for i in range(n):
