@@ -99,14 +99,9 @@ __global__ __launch_bounds__(256) void prep_frame_kernel(const float *__restrict
 // A wave sweeps 64 / SEG_LANES segments at once (one per 16-lane group): the clipped intervals are short
 // (mean 120-190 voxels at 512^3), so with one 256-voxel item per wave 59 % of the lanes were padding --
 // 16-lane segments (64 voxels, 256 contiguous bytes per volume) cut the wave count by 40 %.
-#ifndef HIVE_SEG_LANES
-#define HIVE_SEG_LANES 16
-#endif
-#ifndef HIVE_GRID_MULT
-#define HIVE_GRID_MULT 16
-#endif
-constexpr int SEG_LANES = HIVE_SEG_LANES;
+constexpr int SEG_LANES = 16;
 constexpr int VPT = 4;  // consecutive z voxels per lane: one 16-byte access per lane and volume plane
+constexpr int GRID_MULT = 16;  // workgroups of a sweep per resident workgroup slot (launch_integrate)
 // (update counters of the COUNT kernels: COUNT_SLOTS x u64, COUNT_STRIDE u64s = 128 bytes apart, at hive_ctx::d_scalars + SC_TSDF_COUNTERS: hive_internal.hpp)
 struct WorkItem {
     unsigned xy;  // x | y << 16
@@ -114,7 +109,7 @@ struct WorkItem {
 };
 constexpr int ITEM_NLIVE_SHIFT = 16, ITEM_MASK_SHIFT = 22, ITEM_BIN_SHIFT = 26;
 constexpr int NBINS = 64;  // image bands (of the sweep's first frame) the fused sweep's work list is sorted by
-static_assert(HIVE_SEG_LANES * 4 <= 64, "a segment's live-voxel count - 1 takes 6 bits of WorkItem::zz");
+static_assert(SEG_LANES * VPT <= 64, "a segment's live-voxel count - 1 takes 6 bits of WorkItem::zz");
 __device__ __forceinline__ int item_nlive(unsigned zz) { return ((zz >> ITEM_MASK_SHIFT) & 15u) ? (int)((zz >> ITEM_NLIVE_SHIFT) & 63u) + 1 : 0; }  // 0: a dead (all-zero) item
 
 struct RowClip {
@@ -756,20 +751,13 @@ __global__ __launch_bounds__(256) void integrate_kernel(FrameParams p, const Wor
 // becomes bound by the per-frame arithmetic (the single-frame kernel keeps its SIMDs 56 % busy).  (Tried and taken out: giving each XCD
 // its own contiguous eighth of the work list, so that the texels of the four frames stay in its L2 -- 67 instead of 60 us per frame: the
 // eighths are not equally expensive.)
-#ifndef HIVE_TSDF_MAXF
-#define HIVE_TSDF_MAXF 4
-#endif
-constexpr int MAXF = HIVE_TSDF_MAXF;
+constexpr int MAXF = 4;
 static_assert(MAXF <= 4, "WorkItem::zz holds a 4-bit frame mask");
 struct MultiParams {
     FrameParams f[MAXF];  // the per-frame fields (R, T, frame / depth / rgb, tile_max) differ; the rest is the same in all
     int nf;
-    int frame_skip;  // 1: a wave skips the frames whose clip excludes all of its segments (work item masks)
-    int xcd_split;   // 1: the (band-sorted) work list's eighths go to the eight XCDs; 0: one grid-stride sweep over the whole list
-    int bins_x;      // the sort key's image tiling: NBINS = (NBINS / bins_x) rows x bins_x columns of tiles of the first frame (1: full-width bands)
     unsigned *clear_next;  // the other scalar block: MS_CLEAR words to zero for the next sweep
-    int lanes_along_x;     // work-list kernel: 1 = its lanes (neighbouring rows) run along x, 0 = along y
-    int quad_interleave;   // work-list kernel: 1 = the segments of four neighbouring rows are interleaved
+    int lanes_along_x;     // work-list kernel: 1 = its lanes (neighbouring rows) run along x, 0 = along y (the pose decides: launch_integrate_multi)
 };
 
 // scalar block of a fused sweep (two alternate, hive_ctx::d_scalars + MS_BASE + which * MS_STRIDE): [MS_NITEMS] work-list length, [MS_HIST ..] items
@@ -797,7 +785,7 @@ __global__ __launch_bounds__(1024) void build_worklist_multi_kernel(MultiParams 
     unsigned n_chunks = 0;
     int zstart = 0, z1 = 0, x = 0, y = 0;
     int fz0[MAXF], fz1[MAXF];  // the frames' own intervals (empty: 0, 0)
-    float ax0 = 0.f, ay0 = 0.f, az0 = 0.f;  // row constants of the sweep's first frame (image tile of a segment)
+    float ay0 = 0.f, az0 = 0.f;  // row constants of the sweep's first frame (image band of a segment)
     auto frames_of = [&](int zs) {  // frames whose own interval meets [zs, zs + CHUNK): the others cannot update a voxel of this segment
         unsigned mask = 0;
 #pragma unroll
@@ -823,7 +811,7 @@ __global__ __launch_bounds__(1024) void build_worklist_multi_kernel(MultiParams 
                 const float ax = q.R[0] * tx + q.R[3] * ty;
                 const float ay = q.R[1] * tx + q.R[4] * ty;
                 const float az = q.R[2] * tx + q.R[5] * ty;
-                if (f == 0) ax0 = ax, ay0 = ay, az0 = az;
+                if (f == 0) ay0 = ay, az0 = az;
                 const bool row_far = p.row_far == 2 || (p.row_far == 1 && row_far_pays(gsum[f], gmax[f], p.tiles_x * p.tiles_y));  // (workgroup-uniform)
                 const RowClip clip = clip_row(q, ax, ay, az, __uint_as_float(gmax[f]), row_far ? dil[f] : nullptr);
                 if (clip.z1 > clip.z0) {
@@ -854,27 +842,14 @@ __global__ __launch_bounds__(1024) void build_worklist_multi_kernel(MultiParams 
             const unsigned mask = frames_of(zs);
             if (!mask) continue;
             unsigned slot = quad_first;
-            if (mp.quad_interleave) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) slot += min(nq[j], e) + ((j < (lane & 3) && nq[j] > e) ? 1u : 0u);
-            } else {
-                slot = first + e;
-            }
+            for (int j = 0; j < 4; ++j) slot += min(nq[j], e) + ((j < (lane & 3) && nq[j] > e) ? 1u : 0u);
             ++e;
             // image band: the row v of the first frame the segment's middle projects to (clamped; any value is valid -- it only orders the list)
             const float tz = (p.oz + (float)(zs + CHUNK / 2) * p.vs) - p.T[2];
             const float cz = az0 + p.R[8] * tz;
             const float v = cz > 1.0e-6f ? p.fy * ((ay0 + p.R[7] * tz) / cz) + p.cy : 0.f;
-            // (round 5) the key is a 2-D image TILE where bins_x > 1: bins_y x bins_x tiles, row-major.  A 64-voxel segment is a radial image run of up to a few
-            // hundred pixels; with full-width bands (17 rows at 1080p) it crosses up to 16 of them and an XCD's gathers range over all of those stripes of four
-            // frames -- 16 MB against a 4 MB L2 (counters at 1920 x 1080 into 1024^3: L2 hit rate 46 %, FETCH_SIZE 4.7 GB per launch against 2.4 GB that must move;
-            // at 640 x 480: 83 %).  A compact tile keeps what the XCD is gathering from at any one time to a few tiles of each frame.
-            const int bins_y = NBINS / mp.bins_x;
-            int bin = min(max((int)(v * ((float)bins_y / (float)p.H)), 0), bins_y - 1);
-            if (mp.bins_x > 1) {
-                const float u = cz > 1.0e-6f ? p.fx * ((ax0 + p.R[6] * tz) / cz) + p.cx : 0.f;
-                bin = bin * mp.bins_x + min(max((int)(u * ((float)mp.bins_x / (float)p.W)), 0), mp.bins_x - 1);
-            }
+            const int bin = min(max((int)(v * ((float)NBINS / (float)p.H)), 0), NBINS - 1);
             atomicAdd(&bin_count[bin], 1u);
             WorkItem it;
             it.xy = (unsigned)x | ((unsigned)y << 16);
@@ -936,18 +911,13 @@ __global__ __launch_bounds__(1024) void sort_worklist_kernel(const WorkItem *__r
 }
 
 // UPD: 0 = any observation weight, 1 = obs_weight == 1, 2 = obs_weight == 1 with the division-free colour update (update_voxels FASTC)
-#ifdef HIVE_TSDF_WAVES
-#define HIVE_TSDF_OCC __attribute__((amdgpu_waves_per_eu(HIVE_TSDF_WAVES, HIVE_TSDF_WAVES)))
-#else
-#define HIVE_TSDF_OCC
-#endif
 // The work list is sorted by image band (sort_worklist_kernel) and the XCDs take the sorted list's eighths: workgroups with the same
 // blockIdx % 8 share an XCD (and its L2), so each XCD's gathers stay within one stripe of each frame.
 // (Round 4, measured and taken out: gather instruction k covering the 64 consecutive voxels of segment k -- one pixel run per instruction
 // instead of four runs of 16 voxels, i.e. 12 fewer distinct 64-byte lines per trip and frame -- with segment k's row constants from readlane:
 // 210 vs 190 us per launch on the room scene, 198 vs 184 on the bench scene: the four rows' constants per frame cost more than the lines save.)
 template <int RM, int UPD>
-__global__ __launch_bounds__(256) HIVE_TSDF_OCC void integrate_multi_kernel(MultiParams mp, const WorkItem *__restrict__ items, const unsigned *__restrict__ n_items_ptr,
+__global__ __launch_bounds__(256) void integrate_multi_kernel(MultiParams mp, const WorkItem *__restrict__ items, const unsigned *__restrict__ n_items_ptr,
                                                               float *__restrict__ v0, float *__restrict__ v1, float *__restrict__ v2) {
     constexpr int PER_WAVE = 64 / SEG_LANES, SEG_VOX = SEG_LANES * 4;
     typedef ItemShape Sh;
@@ -958,10 +928,10 @@ __global__ __launch_bounds__(256) HIVE_TSDF_OCC void integrate_multi_kernel(Mult
     const unsigned n_items = *n_items_ptr;
     const unsigned n_trips = (n_items + PER_WAVE - 1) / PER_WAVE;
     // XCD x = blockIdx % 8 sweeps trips [x per_xcd, (x + 1) per_xcd) with its gridDim / 8 workgroups (the host launches a multiple of 8)
-    const unsigned per_xcd = mp.xcd_split ? (n_trips + 7u) / 8u : n_trips;
-    const unsigned xcd = mp.xcd_split ? (blockIdx.x & 7u) : 0u;
-    const unsigned local_block = mp.xcd_split ? (blockIdx.x >> 3) : blockIdx.x;
-    const unsigned stride = (mp.xcd_split ? (gridDim.x >> 3) : gridDim.x) * 4;
+    const unsigned per_xcd = (n_trips + 7u) / 8u;
+    const unsigned xcd = blockIdx.x & 7u;
+    const unsigned local_block = blockIdx.x >> 3;
+    const unsigned stride = (gridDim.x >> 3) * 4;
     const unsigned trip_end = min(n_trips, (xcd + 1u) * per_xcd);
     const FrameParams &p0 = mp.f[0];
     const float trunc_rcp = refined_rcp(p0.trunc);
@@ -985,7 +955,7 @@ __global__ __launch_bounds__(256) HIVE_TSDF_OCC void integrate_multi_kernel(Mult
         unsigned wave_frames = (item.zz >> ITEM_MASK_SHIFT) & 15u;
 #pragma unroll
         for (int o = SEG_LANES; o < 64; o <<= 1) wave_frames |= (unsigned)__shfl_xor((int)wave_frames, o);
-        wave_frames = mp.frame_skip ? (unsigned)__builtin_amdgcn_readfirstlane((int)wave_frames) : 0xffu;
+        wave_frames = (unsigned)__builtin_amdgcn_readfirstlane((int)wave_frames);
         float t[VPT], w[VPT], cr[VPT], cg[VPT], cb[VPT];  // the colour as three channels while the voxels are in registers
         bool loaded = false;
         uint2 *mine = xchg + ((threadIdx.x >> 6) * PER_WAVE + seg) * SEG_VOX;
@@ -1185,50 +1155,75 @@ static TileGrid tile_grid(int H, int W) {
         if ((long long)g.tiles_x * g.tiles_y <= MAX_TILES) return g;
     }
 }
-static bool env_flag(const char *name, bool dflt) {  // tuning switches, read per call (A/B runs toggle them inside one process)
-    const char *e = getenv(name);
-    return e ? atoi(e) != 0 : dflt;
+// A sweep's inputs: the {depth, rgb} texels and the tile maxima of its frames (prep_frame_kernel).
+struct PreparedFrames {
+    const uint2 *texels;       // [n][H*W]
+    const unsigned *tile_max;  // [n][tile_stride], tiles of (32 << tile_grid(H, W).shift)^2 pixels
+    int tile_stride;
+};
+// The one prep launch, and the one place that lays its output out: frames [0, n) in device memory (H*W pixels apart) -> *buf = the n frames'
+// texels, padded to 256 bytes, then n x MAX_TILES tile maxima.  zero_next / zero_words: the scalar block the kernel clears on its way, or none.
+static int launch_prep(hive_ctx *ctx, void **buf, size_t *buf_bytes, int n, const uint8_t *color, const float *depth, int H, int W, unsigned *zero_next,
+                       int zero_words, PreparedFrames *out) {
+    const size_t npx = (size_t)H * W;
+    const TileGrid tg = tile_grid(H, W);
+    const size_t tex_bytes = ((size_t)n * npx * sizeof(uint2) + 255) & ~(size_t)255;
+    int rc = hive_reserve_device(ctx, buf, buf_bytes, tex_bytes + (size_t)n * MAX_TILES * sizeof(unsigned));
+    if (rc) return rc;
+    unsigned *d_tiles = (unsigned *)((char *)*buf + tex_bytes);
+    // the 4-pixels-per-lane form needs every frame's depth 16-byte and colour 4-byte aligned
+    const bool vec = W % 4 == 0 && (uintptr_t)depth % 16 == 0 && (uintptr_t)color % 4 == 0;
+    const dim3 grid((unsigned)(tg.tiles_x * tg.tiles_y), (unsigned)n);
+    if (vec)
+        hipLaunchKernelGGL(prep_frame_kernel<true>, grid, dim3(256), 0, ctx->stream, depth, color, H, W, tg.shift, tg.tiles_x, (uint2 *)*buf, d_tiles, MAX_TILES,
+                           zero_next, zero_words);
+    else
+        hipLaunchKernelGGL(prep_frame_kernel<false>, grid, dim3(256), 0, ctx->stream, depth, color, H, W, tg.shift, tg.tiles_x, (uint2 *)*buf, d_tiles, MAX_TILES,
+                           zero_next, zero_words);
+    HIVE_CHECK_HIP(ctx, hipGetLastError());
+    out->texels = (const uint2 *)*buf;
+    out->tile_max = d_tiles;
+    out->tile_stride = MAX_TILES;
+    return HIVE_OK;
 }
 
-static int prepare_frame(hive_tsdf *v, const uint8_t *color, const float *depth, int H, int W, int mem,
-                         const uint8_t **d_color, const float **d_depth) {
+// One frame (host memory: uploaded first) into hive_ctx::d_frame, for the single-frame kernel.
+static int prepare_frame(hive_tsdf *v, const uint8_t *color, const float *depth, int H, int W, int mem, PreparedFrames *out) {
     hive_ctx *ctx = v->ctx;
-    const size_t npx = (size_t)H * W;
     if (mem == HIVE_MEM_HOST) {
-        const size_t depth_bytes = npx * sizeof(float), color_bytes = npx * 3;
+        const size_t depth_bytes = (size_t)H * W * sizeof(float), color_bytes = (size_t)H * W * 3;
         const size_t color_off = (depth_bytes + 255) & ~(size_t)255;
         int rc = hive_reserve_device(ctx, &ctx->d_in, &ctx->in_bytes, color_off + color_bytes);
         if (rc) return rc;
         if ((rc = hive_upload(ctx, ctx->d_in, depth, depth_bytes))) return rc;
         if ((rc = hive_upload(ctx, (char *)ctx->d_in + color_off, color, color_bytes))) return rc;
-        *d_depth = (const float *)ctx->d_in;
-        *d_color = (const uint8_t *)ctx->d_in + color_off;
-    } else {
-        *d_depth = depth;
-        *d_color = color;
+        depth = (const float *)ctx->d_in;
+        color = (const uint8_t *)ctx->d_in + color_off;
     }
-    const TileGrid tg = tile_grid(H, W);
-    const size_t tex_bytes = (npx * sizeof(uint2) + 255) & ~(size_t)255;
-    int rc = hive_reserve_device(ctx, &ctx->d_frame, &ctx->frame_bytes, tex_bytes + MAX_TILES * sizeof(unsigned));
-    if (rc) return rc;
     // scalar block of this frame: [4] work-list length (update counters: d_scalars + SC_TSDF_COUNTERS).  Two blocks alternate (both zero after
-    // hive_ctx_create); the prep kernel of a frame clears the block of the next one.
+    // hive_ctx_create); the prep kernel of a frame clears the block of the next one, which is the one the frame before this used.
+    unsigned *next = tsdf_scalars(ctx);
+    const int rc = launch_prep(ctx, &ctx->d_frame, &ctx->frame_bytes, 1, color, depth, H, W, next, SC_TSDF_FRAME_WORDS, out);
+    if (rc) return rc;
     ctx->tsdf_scalars ^= 1;
-    unsigned *next = ctx->d_scalars + (ctx->tsdf_scalars ? SC_TSDF_FRAME_A : SC_TSDF_FRAME_B);
-    unsigned *tiles = (unsigned *)((char *)ctx->d_frame + tex_bytes);
-    const bool vec = W % 4 == 0 && ((uintptr_t)*d_depth % 16 == 0) && ((uintptr_t)*d_color % 4 == 0);
-    const dim3 grid((unsigned)(tg.tiles_x * tg.tiles_y), 1);
-    if (vec)
-        hipLaunchKernelGGL(prep_frame_kernel<true>, grid, dim3(256), 0, ctx->stream, *d_depth, *d_color, H, W, tg.shift, tg.tiles_x, (uint2 *)ctx->d_frame, tiles,
-                           MAX_TILES, next, SC_TSDF_FRAME_WORDS);
-    else
-        hipLaunchKernelGGL(prep_frame_kernel<false>, grid, dim3(256), 0, ctx->stream, *d_depth, *d_color, H, W, tg.shift, tg.tiles_x, (uint2 *)ctx->d_frame, tiles,
-                           MAX_TILES, next, SC_TSDF_FRAME_WORDS);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
 }
+// Frames [0, n) of a device-resident batch into hive_ctx::d_batch, for the fused sweeps.
+static int prepare_batch(hive_tsdf *v, int n, const uint8_t *color, const float *depth, int H, int W, PreparedFrames *out) {
+    hive_ctx *ctx = v->ctx;
+    return launch_prep(ctx, &ctx->d_batch, &ctx->batch_bytes, n, color, depth, H, W, nullptr, 0, out);
+}
 
-static void fill_frame_params(hive_tsdf *v, int H, int W, const float K[9], const double pose[16], float obs_weight, FrameParams &p) {
+// HIVE_TSDF_ROW_FAR = 0 never / 1 where the tile table says it pays (default) / 2 always: FrameParams::row_far, read once per launch.
+// This file's one remaining switch.  It stays because its three modes are a tested contract (each gives the oracle's volume:
+// tests/test_tsdf_gpu.py::test_per_row_far_cut_modes), and forcing the mode is the only way to run the per-row cut, and the frame-wide
+// cut, on a scene where the adaptive rule would choose the other; every other default here was settled by measurement (DESIGN_LOG.md).
+static int row_far_mode() {
+    const char *e = getenv("HIVE_TSDF_ROW_FAR");
+    return e ? std::min(2, std::max(0, atoi(e))) : 1;
+}
+
+static void fill_frame_params(hive_tsdf *v, int H, int W, const float K[9], const double pose[16], float obs_weight, int row_far, FrameParams &p) {
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c) p.R[3 * r + c] = (float)pose[4 * r + c];
         p.T[r] = (float)pose[4 * r + 3];
@@ -1253,47 +1248,13 @@ static void fill_frame_params(hive_tsdf *v, int H, int W, const float K[9], cons
     p.tile_shift = tg.shift;
     p.tiles_x = tg.tiles_x;
     p.tiles_y = tg.tiles_y;
-    {
-        const char *e = getenv("HIVE_TSDF_ROW_FAR");  // tuning: 0 never / 1 adaptive (default) / 2 always
-        p.row_far = e ? std::min(2, std::max(0, atoi(e))) : 1;
-    }
+    p.row_far = row_far;
     p.frame = nullptr;
     p.tile_max = nullptr;
     // the division-free colour update: the roundf contract, unit observation weight, and a volume whose weights are all integers
     // below 65534 -- true as long as every integrate since the last reset had obs_weight == 1 (hive_tsdf::unit_weights / unit_frames)
-    p.fast_colour = (v->round_mode == HIVE_ROUND_HALF_AWAY && obs_weight == 1.0f && v->unit_weights && env_flag("HIVE_TSDF_FAST_COLOUR", true)) ? 1 : 0;
+    p.fast_colour = (v->round_mode == HIVE_ROUND_HALF_AWAY && obs_weight == 1.0f && v->unit_weights) ? 1 : 0;
     p.n_updated = nullptr;
-}
-
-// The fused sweep's inputs: the {depth, rgb} texels and the tile maxima of every frame (prep_frame_kernel; one launch for a whole batch of frames).
-struct PreparedFrames {
-    const uint2 *texels;       // [nf][H*W]
-    const unsigned *tile_max;  // [nf][tile_stride], tiles of (32 << tile_grid(H, W).shift)^2 pixels
-    int tile_stride;
-};
-// One prep launch for frames [0, n) of a device-resident batch into hive_ctx::d_batch (texels, then the tile maxima).
-static int prepare_batch(hive_tsdf *v, int n, const uint8_t *color, const float *depth, int H, int W, PreparedFrames *out) {
-    hive_ctx *ctx = v->ctx;
-    const size_t npx = (size_t)H * W;
-    const TileGrid tg = tile_grid(H, W);
-    const size_t tex_bytes = ((size_t)n * npx * sizeof(uint2) + 255) & ~(size_t)255;
-    int rc = hive_reserve_device(ctx, &ctx->d_batch, &ctx->batch_bytes, tex_bytes + (size_t)n * MAX_TILES * sizeof(unsigned));
-    if (rc) return rc;
-    unsigned *d_tiles = (unsigned *)((char *)ctx->d_batch + tex_bytes);
-    // the 4-pixels-per-lane form needs every frame's depth 16-byte and colour 4-byte aligned
-    const bool vec = W % 4 == 0 && (uintptr_t)depth % 16 == 0 && (uintptr_t)color % 4 == 0;
-    const dim3 grid((unsigned)(tg.tiles_x * tg.tiles_y), (unsigned)n);
-    if (vec)
-        hipLaunchKernelGGL(prep_frame_kernel<true>, grid, dim3(256), 0, ctx->stream, depth, color, H, W, tg.shift, tg.tiles_x, (uint2 *)ctx->d_batch, d_tiles, MAX_TILES,
-                           (unsigned *)nullptr, 0);
-    else
-        hipLaunchKernelGGL(prep_frame_kernel<false>, grid, dim3(256), 0, ctx->stream, depth, color, H, W, tg.shift, tg.tiles_x, (uint2 *)ctx->d_batch, d_tiles, MAX_TILES,
-                           (unsigned *)nullptr, 0);
-    HIVE_CHECK_HIP(ctx, hipGetLastError());
-    out->texels = (const uint2 *)ctx->d_batch;
-    out->tile_max = d_tiles;
-    out->tile_stride = MAX_TILES;
-    return HIVE_OK;
 }
 
 // nf (2 .. MAXF) prepared frames in ONE sweep (integrate_multi_kernel): one work list over the union of the frames' clips, sorted by image
@@ -1308,34 +1269,16 @@ static int launch_integrate_multi(hive_tsdf *v, int nf, int H, int W, const floa
     ctx->tsdf_multi_scalars ^= 1;
     unsigned *sc = ctx->d_scalars + MS_BASE + (ctx->tsdf_multi_scalars ? MS_STRIDE : 0);
     unsigned *idle_block = ctx->d_scalars + MS_BASE + (ctx->tsdf_multi_scalars ? 0 : MS_STRIDE);
-    const uint2 *texels = prepared.texels;
-    const unsigned *tiles = prepared.tile_max;
-    const int tile_stride = prepared.tile_stride;
-    const bool sorted = env_flag("HIVE_TSDF_SORT", true);  // work list sorted by image band, its eighths to the eight XCDs
     MultiParams mp;
     mp.nf = nf;
-    mp.frame_skip = env_flag("HIVE_TSDF_FRAME_SKIP", true) ? 1 : 0;
-    mp.xcd_split = sorted ? 1 : 0;
     mp.clear_next = idle_block;
-    // the camera's "down" axis in world coordinates is column 1 of the pose's rotation: lanes run along the volume axis it has less of
-    const double *pose0 = poses;
-    const bool auto_x = fabs(pose0[0 * 4 + 1]) <= fabs(pose0[1 * 4 + 1]);
-    const char *lanes_env = getenv("HIVE_TSDF_LANES");  // tuning: "x" / "y" force the lane axis
-    mp.lanes_along_x = lanes_env ? (lanes_env[0] == 'x') : (auto_x ? 1 : 0);
-    mp.quad_interleave = env_flag("HIVE_TSDF_QUAD", true) ? 1 : 0;
-    {
-        const char *e = getenv("HIVE_TSDF_BINS_X");  // tuning: columns of the sort key's image tiling (1 = full-width bands, the rule of round 4)
-        int bx = e ? atoi(e) : 1;
-        if (bx != 1 && bx != 2 && bx != 4 && bx != 8 && bx != 16) bx = 1;
-        mp.bins_x = bx;
-    }
+    // the camera's "down" axis in world coordinates is column 1 of the first pose's rotation: lanes run along the volume axis it has less of
+    mp.lanes_along_x = fabs(poses[0 * 4 + 1]) <= fabs(poses[1 * 4 + 1]) ? 1 : 0;
+    const int row_far = row_far_mode();
     for (int f = 0; f < nf; ++f) {
-        fill_frame_params(v, H, W, K, poses + 16 * (size_t)f, obs_weight, mp.f[f]);
-        mp.f[f].frame = texels + (size_t)f * npx;
-        mp.f[f].tile_max = tiles + (size_t)f * tile_stride;
-#ifdef HIVE_TSDF_TUNING  // tuning builds only (make tsdf_variants): a TIMING experiment with WRONG results -- every frame gathers from frame 0's texels
-        if (env_flag("HIVE_TSDF_TIMING_SAME_TEXELS", false)) mp.f[f].frame = texels;
-#endif
+        fill_frame_params(v, H, W, K, poses + 16 * (size_t)f, obs_weight, row_far, mp.f[f]);
+        mp.f[f].frame = prepared.texels + (size_t)f * npx;
+        mp.f[f].tile_max = prepared.tile_max + (size_t)f * prepared.tile_stride;
     }
     for (int f = nf; f < MAXF; ++f) mp.f[f] = mp.f[0];
     const FrameParams &p = mp.f[0];
@@ -1344,15 +1287,14 @@ static int launch_integrate_multi(hive_tsdf *v, int nf, int H, int W, const floa
     const size_t max_items = (size_t)rows * (size_t)((p.Z + seg - 1) / seg);
     // two lists: as built (row order), and sorted by image band
     if ((rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, 2 * max_items * sizeof(WorkItem)))) return rc;
-    WorkItem *built = (WorkItem *)ctx->d_scratch, *items = sorted ? built + max_items : built;
+    WorkItem *built = (WorkItem *)ctx->d_scratch, *items = built + max_items;
     unsigned *n_items = sc + MS_NITEMS;
     v->last_n_items = n_items;
     hipLaunchKernelGGL(build_worklist_multi_kernel, dim3((unsigned)((rows + 1023) / 1024)), dim3(1024), 0, ctx->stream, mp, built, n_items, sc + MS_HIST);
-    if (sorted)
-        hipLaunchKernelGGL(sort_worklist_kernel, dim3((unsigned)((max_items + 1023) / 1024)), dim3(1024), 0, ctx->stream, (const WorkItem *)built, items,
-                           (const unsigned *)n_items, (const unsigned *)(sc + MS_HIST), sc + MS_CURSOR);
+    hipLaunchKernelGGL(sort_worklist_kernel, dim3((unsigned)((max_items + 1023) / 1024)), dim3(1024), 0, ctx->stream, (const WorkItem *)built, items,
+                       (const unsigned *)n_items, (const unsigned *)(sc + MS_HIST), sc + MS_CURSOR);
     const long long max_trips = (long long)((max_items + 64 / SEG_LANES - 1) / (64 / SEG_LANES));
-    const long long blocks = std::min<long long>((long long)ctx->num_cus * 8 * HIVE_GRID_MULT, (max_trips + 3) / 4);
+    const long long blocks = std::min<long long>((long long)ctx->num_cus * 8 * GRID_MULT, (max_trips + 3) / 4);
     const dim3 grid((unsigned)((blocks + 7) / 8 * 8)), block(256);  // (a multiple of 8: the XCDs' shares)
     if ((rc = hive_time_begin(ctx))) return rc;
     const int upd = p.fast_colour ? 2 : (obs_weight == 1.0f ? 1 : 0);
@@ -1374,12 +1316,12 @@ static int launch_integrate_multi(hive_tsdf *v, int nf, int H, int W, const floa
 
 template <bool ACCUM>
 static int launch_integrate(hive_tsdf *v, float *accum, int H, int W, const float K[9], const double pose[16],
-                            float obs_weight, bool count) {
+                            float obs_weight, bool count, const PreparedFrames &prepared) {
     hive_ctx *ctx = v->ctx;
     FrameParams p;
-    fill_frame_params(v, H, W, K, pose, obs_weight, p);
-    p.frame = (const uint2 *)ctx->d_frame;
-    p.tile_max = (const unsigned *)((const char *)ctx->d_frame + (((size_t)H * W * sizeof(uint2) + 255) & ~(size_t)255));
+    fill_frame_params(v, H, W, K, pose, obs_weight, row_far_mode(), p);
+    p.frame = prepared.texels;
+    p.tile_max = prepared.tile_max;
     p.n_updated = (unsigned long long *)(ctx->d_scalars + SC_TSDF_COUNTERS);
     if (count) HIVE_CHECK_HIP(ctx, hipMemsetAsync(p.n_updated, 0, COUNT_SLOTS * COUNT_STRIDE * sizeof(unsigned long long), ctx->stream));
     const long long rows = (long long)p.X * p.Y;
@@ -1394,11 +1336,11 @@ static int launch_integrate(hive_tsdf *v, float *accum, int H, int W, const floa
     v->last_n_items = n_items;
     const dim3 wl_grid((unsigned)((rows + 1023) / 1024));
     hipLaunchKernelGGL(build_worklist_kernel, wl_grid, dim3(1024), 0, ctx->stream, p, items, n_items);
-    // grid-stride sweep: HIVE_GRID_MULT (16) x the resident workgroup count (8 workgroups of 4 waves per CU), so that the
+    // grid-stride sweep: GRID_MULT (16) x the resident workgroup count (8 workgroups of 4 waves per CU), so that the
     // dispatcher evens out trips of unequal cost (room scene, 512^3: x2 97, x4 90-94, x8 91, x16 87, x32 95 us; at x16 the
     // 32768 workgroups hold ~0.5 trips each: most waves run exactly one); a wave takes 64 / SEG_LANES items per trip
     const long long max_trips = (long long)((max_items + 64 / SEG_LANES - 1) / (64 / SEG_LANES));
-    const dim3 grid((unsigned)std::min<long long>((long long)ctx->num_cus * 8 * HIVE_GRID_MULT, (max_trips + 3) / 4)), block(256);
+    const dim3 grid((unsigned)std::min<long long>((long long)ctx->num_cus * 8 * GRID_MULT, (max_trips + 3) / 4)), block(256);
     if ((rc = hive_time_begin(ctx))) return rc;
 #define HIVE_LAUNCH(RM, CNT)                                                                                      \
     hipLaunchKernelGGL((integrate_kernel<RM, CNT, ACCUM>), grid, block, 0, ctx->stream, p, items, n_items, a0, \
@@ -1593,11 +1535,10 @@ int hive_tsdf_integrate(hive_tsdf *vol, const uint8_t *color, const float *depth
     int rc = check_frame_args(vol, color, depth, H, W, K, cam_pose, mem);
     if (rc) return rc;
     hive_ctx *ctx = vol->ctx;
-    const uint8_t *d_color;
-    const float *d_depth;
+    PreparedFrames frame;
     note_observations(vol, obs_weight, 1);
-    if ((rc = prepare_frame(vol, color, depth, H, W, mem, &d_color, &d_depth))) return rc;
-    if ((rc = launch_integrate<false>(vol, nullptr, H, W, K, cam_pose, obs_weight, n_updated != nullptr))) return rc;
+    if ((rc = prepare_frame(vol, color, depth, H, W, mem, &frame))) return rc;
+    if ((rc = launch_integrate<false>(vol, nullptr, H, W, K, cam_pose, obs_weight, n_updated != nullptr, frame))) return rc;
     vol->n_verts = vol->n_faces = -1;
     if (n_updated) {
         unsigned long long slots[COUNT_SLOTS * COUNT_STRIDE];
@@ -1619,25 +1560,21 @@ int hive_tsdf_integrate_batch(hive_tsdf *vol, int n, const uint8_t *color, const
     note_observations(vol, obs_weight, n);
     const size_t npx = (size_t)H * W;
     // device-resident frames on the vector path: groups of up to MAXF consecutive frames per sweep (bit-identical to one sweep each)
-    static const char *frames_env = getenv("HIVE_TSDF_FRAMES_PER_LAUNCH");  // "1": the single-frame kernel (tuning / A-B)
-    const int group = frames_env ? std::max(1, std::min(MAXF, atoi(frames_env))) : MAXF;
-    const bool multi = mem == HIVE_MEM_DEVICE && group > 1;  // any volume shape, any image size (rows of any length take the 16-byte path)
+    const bool multi = mem == HIVE_MEM_DEVICE;  // any volume shape, any image size (rows of any length take the 16-byte path)
     // Fusing pays when the frames look at (almost) the same voxels -- consecutive frames of a video; frames far apart share little and
     // every voxel of the union still runs every frame's tests.  Measured on the room scene (640 x 480 into 512^3, us per frame: alone |
     // pairs | fours): 2.4 degrees apart 90 | 70 | 62; 12 degrees 90 | - | 75; 15 degrees 85 | 77 | 82; 20 degrees 85 | 81 | 93; 30 degrees
     // 85 | 80 | 96; 45 degrees 85 | 85 | 122.  A group therefore grows only while the optical axis stays within 36 degrees of its FIRST
     // frame's (and the camera within a quarter of the volume's longest side).
     const double max_side = voxel_extent(vol);
-    static const char *cos_env = getenv("HIVE_TSDF_FUSE_COS");  // tuning: cosine of the largest angle to the group's first frame
-    const double fuse_cos = cos_env ? atof(cos_env) : 0.809017;  // cos 36 deg
-    static const char *dist_env = getenv("HIVE_TSDF_FUSE_DIST");  // tuning: camera distance to the group's first frame, in longest volume sides
-    const double fuse_dist = dist_env ? atof(dist_env) : 0.25;
+    constexpr double FUSE_COS = 0.809017;  // cos 36 deg: the largest angle to the group's first frame
+    constexpr double FUSE_DIST = 0.25;     // the largest camera distance to the group's first frame, in longest volume sides
     auto fusable = [&](int a, int b) {
         const double *pa = cam_poses + 16 * (size_t)a, *pb = cam_poses + 16 * (size_t)b;
         const double dot = pa[2] * pb[2] + pa[6] * pb[6] + pa[10] * pb[10];
         const double na = sqrt(pa[2] * pa[2] + pa[6] * pa[6] + pa[10] * pa[10]), nb = sqrt(pb[2] * pb[2] + pb[6] * pb[6] + pb[10] * pb[10]);
         const double dx = pa[3] - pb[3], dy = pa[7] - pb[7], dz = pa[11] - pb[11];
-        return dot >= fuse_cos * na * nb && dx * dx + dy * dy + dz * dz <= fuse_dist * fuse_dist * max_side * max_side;
+        return dot >= FUSE_COS * na * nb && dx * dx + dy * dy + dz * dz <= FUSE_DIST * FUSE_DIST * max_side * max_side;
     };
     vol->last_groups.clear();
     // One prep launch (texels + tile maxima) serves up to PREP_CHUNK frames of the batch: at 4 frames per sweep a prep per sweep was 27 small
@@ -1649,7 +1586,7 @@ int hive_tsdf_integrate_batch(hive_tsdf *vol, int n, const uint8_t *color, const
     while (f < n) {
         int nf = 1;
         if (multi)
-            while (nf < group && f + nf < n && fusable(f, f + nf)) ++nf;
+            while (nf < MAXF && f + nf < n && fusable(f, f + nf)) ++nf;
         if (nf > 1) {
             if (f + nf > prep_hi) {
                 prep_lo = f;
@@ -1661,10 +1598,9 @@ int hive_tsdf_integrate_batch(hive_tsdf *vol, int n, const uint8_t *color, const
             mine.tile_max += (size_t)(f - prep_lo) * chunk.tile_stride;
             if ((rc = launch_integrate_multi(vol, nf, H, W, K, cam_poses + 16 * (size_t)f, obs_weight, mine))) return rc;
         } else {
-            const uint8_t *d_color;
-            const float *d_depth;
-            if ((rc = prepare_frame(vol, color + f * npx * 3, depth + f * npx, H, W, mem, &d_color, &d_depth))) return rc;
-            if ((rc = launch_integrate<false>(vol, nullptr, H, W, K, cam_poses + 16 * (size_t)f, obs_weight, false))) return rc;
+            PreparedFrames frame;
+            if ((rc = prepare_frame(vol, color + f * npx * 3, depth + f * npx, H, W, mem, &frame))) return rc;
+            if ((rc = launch_integrate<false>(vol, nullptr, H, W, K, cam_poses + 16 * (size_t)f, obs_weight, false, frame))) return rc;
         }
         vol->last_groups.push_back(nf);
         f += nf;
@@ -1735,11 +1671,10 @@ int hive_tsdf_accum_integrate(hive_tsdf *vol, float *d_accum, const uint8_t *col
     int rc = check_frame_args(vol, color, depth, H, W, K, cam_pose, mem);
     if (rc) return rc;
     HIVE_REQUIRE(vol->ctx, d_accum, "accum_integrate: d_accum is NULL");
-    const uint8_t *d_color;
-    const float *d_depth;
-    if ((rc = prepare_frame(vol, color, depth, H, W, mem, &d_color, &d_depth))) return rc;
+    PreparedFrames frame;
+    if ((rc = prepare_frame(vol, color, depth, H, W, mem, &frame))) return rc;
     ++vol->frames_seen;  // (the volume's own planes are untouched: unit_weights / unit_frames do not move)
-    return launch_integrate<true>(vol, d_accum, H, W, K, cam_pose, obs_weight, false);
+    return launch_integrate<true>(vol, d_accum, H, W, K, cam_pose, obs_weight, false, frame);
 }
 
 int hive_tsdf_accum_from_volume(hive_tsdf *v, float *d_accum) {

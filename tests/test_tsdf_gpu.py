@@ -541,3 +541,38 @@ def test_per_row_far_cut_modes(gpu_ctx, oracle_lib, monkeypatch, mode):
             one.integrate(seq["color"][i], depth[i], seq["K"], seq["poses"][i])
         _volumes_equal(one, ora)
     assert items["masked"] < items["room"]
+
+
+@pytest.mark.parametrize("round_mode", [0, 1])
+def test_fused_sweep_with_the_camera_rolled_a_quarter_turn(gpu_ctx, oracle_lib, round_mode):
+    """The fused sweep's work-list kernel runs its lanes along the volume axis (x or y) the camera's down axis has less of (tsdf.hip
+    launch_integrate_multi).  Every synthetic trajectory keeps the camera's down axis along world y (lanes along x); rolling the camera a
+    quarter turn about its optical axis (new right = old down, new down = -old right) puts it along world x, which selects the
+    lanes-along-y form -- asserted on the input, by the host's own rule.  Four frames 2.4 degrees apart in one sweep of four (asserted)
+    into 80 x 64 x 80 voxels (X != Y: a swapped row decomposition cannot pass), all three planes against the oracle's four integrates
+    bit for bit, and the single-frame kernel's update counts against the oracle's; the upright poses beside it as the control."""
+    import torch
+    from hive_amd import fusion, synthetic
+    bounds, voxel = np.array([[0.0, 5.0], [0.5, 4.5], [0.0, 5.0]]), 0.0625  # (every quotient exact in binary)
+    upright = synthetic.circular_trajectory(4, yaw_step_deg=2.4)
+    roll = np.array([[0.0, -1.0, 0.0, 0.0], [1.0, 0.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
+    rolled = upright @ roll
+    assert np.array_equal(rolled[:, :3, 0], upright[:, :3, 1]) and np.array_equal(rolled[:, :3, 1], -upright[:, :3, 0])
+    assert abs(rolled[0][0, 1]) > abs(rolled[0][1, 1]), "the rolled camera's down axis must lie along world x: lanes along y"
+    assert abs(upright[0][0, 1]) <= abs(upright[0][1, 1]), "the control keeps the lanes along x"
+    for poses in (rolled, upright):
+        color, depth, K = _render(poses)
+        assert color.shape == (4, 120, 160, 3) and np.array_equal(K, synthetic.scaled_intrinsics(120, 160)) and (depth == 0).any()
+        ora = oracle_lib.TSDFVolume(bounds, voxel, round_mode=round_mode)
+        n_ora = []
+        for i in range(4):
+            ora.integrate(color[i], depth[i], K, poses[i])
+            n_ora.append(ora.last_n_updated)
+        assert min(n_ora) > 0
+        fused = fusion.TSDFVolume(bounds, voxel, ctx=gpu_ctx, round_mode=round_mode)
+        assert tuple(fused.vol_dim) == (80, 64, 80)
+        fused.integrate_batch(torch.from_numpy(color).cuda(), torch.from_numpy(depth).cuda(), K, poses)
+        assert fused.last_batch_groups() == [4]
+        _volumes_equal(fused, ora)
+        one = fusion.TSDFVolume(bounds, voxel, ctx=gpu_ctx, round_mode=round_mode)
+        assert [one.integrate(color[i], depth[i], K, poses[i], return_n_updated=True) for i in range(4)] == n_ora

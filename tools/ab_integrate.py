@@ -3,7 +3,7 @@
 (placement of the volume in HBM), so every library is probed in `--rounds` fresh processes, interleaved, and
 the minimum and the median of the per-process averages are reported.
 
-    python tools/ab_integrate.py --rounds 5 exp/libhive_A.so exp/libhive_B.so [--env HIVE_TSDF_FAST_AXIS=x]
+    python tools/ab_integrate.py --rounds 5 exp/libhive_A.so exp/libhive_B.so [--env HIVE_TSDF_ROW_FAR=0]
 """
 import argparse
 import os

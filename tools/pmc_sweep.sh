@@ -1,8 +1,8 @@
 #!/bin/bash
 # Counter passes (separate rocprofv3 --pmc runs: no tracing beside them) for integrate_multi_kernel on both scenes of tools/probe_sweep_ab.py.
-# Usage: tools/pmc_sweep.sh <outdir-name> [PROBE_CONFIGS]   -> gpurun_out/<outdir-name>/summary.txt
+# Usage: tools/pmc_sweep.sh <outdir-name> [PROBE_ROW_FAR]   -> <outdir-name>/summary.txt in the output directory ($OUT below)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1
-export PROBE_CONFIGS=${2:-"SORT=1"}
+export PROBE_ROW_FAR=${2:-1}  # one mode per run: the averages below are per launch
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 pass() { n=$1; shift; timeout -k 10 150 rocprofv3 --pmc "$@" --output-format csv -d $OUT/p$n -- python3 $GRAFT_REPO_ROOT/tools/probe_sweep_ab.py 16 > $OUT/p$n.log 2>&1 || echo "pass $n failed"; }

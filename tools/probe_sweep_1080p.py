@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """BASELINE config 4's TSDF side alone: 8 consecutive 1920 x 1080 frames (2.4 degrees apart, analytic room depth) into a 1024^3 volume (5 mm voxels): HIP-event time of
-the integrate launches (hive_ctx_set_timing) and of the whole hive_tsdf_integrate_batch leg.  The tuning switches come from the environment (one process per variant:
-HIVE_TSDF_FRAMES_PER_LAUNCH is read once).  Usage (GPU box): [HIVE_TSDF_...=..] python tools/probe_sweep_1080p.py [label]"""
+the integrate launches (hive_ctx_set_timing) and of the whole hive_tsdf_integrate_batch leg.  Usage: [HIVE_TSDF_ROW_FAR=0|1|2] python tools/probe_sweep_1080p.py [label]"""
 import json
 import os
 import sys
@@ -40,5 +39,5 @@ for rep in range(3):
         best = cur
 w = vol.device_tensors()[1]
 best["weight_sum"] = int(w.double().sum().item())
-best["env"] = {k: v for k, v in os.environ.items() if k.startswith("HIVE_TSDF")}
+best["row_far"] = os.environ.get("HIVE_TSDF_ROW_FAR", "1")
 print(json.dumps(best), flush=True)

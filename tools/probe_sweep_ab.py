@@ -1,11 +1,10 @@
 #!/usr/bin/env python3
-"""A/B of the fused TSDF sweep's switches in ONE process, on both scenes of bench.py (room: analytic depth; dpt: DPT-Hybrid depth of the
-seeded weights), 32 consecutive frames 2.4 degrees apart into 512^3.  Switches (HIVE_TSDF_<name>, all default 1): ROW_FAR (per-row far cut from the
-depth tiles), FRAME_SKIP (work-item frame masks), FAST_COLOUR (division-free colour update), SORT (work list sorted by image band, eighths to the XCDs), QUAD (segments of four neighbouring rows interleaved); LANES=x|y forces the lane axis of the work-list kernel.
-PROBE_CONFIGS = ';'-separated configurations, each a ','-separated list of NAME=0/1 (the first is the reference the others' volumes are compared
-with); default: everything off, then everything on.
-Per configuration: us per frame of the whole leg (prep + work list + sort + sweep, HIP events), us per sweep launch (the library's own events), work-list
-voxels of the last sweep, and a check that the volume is bit-identical to the first configuration's.  Usage: probe_sweep_ab.py [frames] [scene ...]"""
+"""The shipped fused TSDF sweep timed in ONE process, on both scenes of bench.py (room: analytic depth; dpt: DPT-Hybrid depth of the
+seeded weights), 32 consecutive frames 2.4 degrees apart into 512^3, under each mode of the sweep's one switch: HIVE_TSDF_ROW_FAR (per-row far cut
+from the depth tiles: 1 = where the tile table says it pays, the default; 0 never; 2 always).
+PROBE_ROW_FAR = ','-separated modes (the first is the reference the others' volumes are compared with); default: 1,0,2.
+Per mode: us per frame of the whole leg (prep + work list + sort + sweep, HIP events), us per sweep launch (the library's own events), work-list
+voxels of the last sweep, and a check that the volume is bit-identical to the first mode's.  Usage: probe_sweep_ab.py [frames] [scene ...]"""
 import json
 import os
 import sys
@@ -37,19 +36,14 @@ if "dpt" in scenes:
     depths["dpt"] = stream.depth(color)[0].clone()
     del model, stream
 out = {}
-NAMES = ("ROW_FAR", "FRAME_SKIP", "FAST_COLOUR", "SORT", "QUAD")  # on / off switches (default on); any other HIVE_TSDF_<NAME>=value may be given too (LANES=x|y)
-spec = os.environ.get("PROBE_CONFIGS") or (",".join(n + "=0" for n in NAMES) + ";" + ",".join(n + "=1" for n in NAMES))
-configs = [dict(kv.split("=") for kv in c.split(",") if kv) for c in spec.split(";")]
+configs = [{"ROW_FAR": m} for m in (os.environ.get("PROBE_ROW_FAR") or "1,0,2").split(",")]
 for scene, depth in depths.items():
     # N_upd per frame (counting single-frame kernel) and N_union per sweep of four
     vol.reset()
     n_upd = [vol.integrate(color[i], depth[i], seq["K"], seq["poses"][i], return_n_updated=True) for i in range(min(frames, 8))]
     ref = None
     for cfg in configs:
-        for key in [k for k in os.environ if k.startswith("HIVE_TSDF_") and k != "HIVE_TSDF_TIMING_SAME_TEXELS"]:
-            del os.environ[key]
-        for name, value in cfg.items():
-            os.environ["HIVE_TSDF_" + name] = str(value)
+        os.environ["HIVE_TSDF_ROW_FAR"] = cfg["ROW_FAR"]
         leg, k_us = [], []
         for rep in range(5):
             vol.reset()
