@@ -11,11 +11,16 @@ whatever device their operands live on; for these integers they are exact (every
 The generators return the operands as int64 (or float64 where they are scaled by a power of two) CPU tensors together with ``bound``, an upper
 bound of max over outputs of sum |a| |w| + |bias| + |residuals| (max |a| times the largest absolute row sum of the weights, plus the largest
 bias and residuals -- never below the true maximum).  ``bound < 2^24`` is asserted: it is the condition for exactness, not a tolerance.  They
-also assert coverage: at least 80 % of the activations are non-zero, and every K position has a non-zero weight in some output channel."""
+also assert coverage: at least 80 % of the activations are non-zero, and every K position has a non-zero weight in some output channel.
+
+The last three sections do the same for the bottleneck convolution (csrc/bneck.hip), the x2 bilinear upsampling (csrc/dpt_ops.hip) and the fused depth head
+(csrc/dpt_head.hip), each with its own conditions stated at its head; the epilogue of the head is norm_reference.head_tail_reference (the test tree's)."""
 import math
 
 import numpy as np
 import torch
+
+import norm_reference as R
 
 LIMIT = 2 ** 24
 Q_SCALE = np.float32(0.125) * np.float32(1.4426950408889634)  # head_dim^-0.5 * log2(e) as the kernel holds it: a float32 (0.125 f is exact)
@@ -525,3 +530,316 @@ def conv_path(M, cin, cout, k, cus, env):
         split = max(1, min(int(sk), kt)) if sk is not None else splitk_ways(tiles128, kt, cus)
         return ("deep", max(1, min(split, cus // tiles128)))
     return ("tile", tm, tn)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the bottleneck convolution (csrc/bneck.hip): GroupNorm + ReLU applied while the 3 x 3 convolution stages its input
+#
+# The test hands the kernel the sums of the GroupNorm in front itself, so the statistics are what it chooses: an integer mean m in -2..2 and a variance v in
+# {0, 0.75} per (image, group).  With eps = 0.25, gn_finalize_tiles_kernel (double: mean = s / cnt, var = q / cnt - mean^2, rstd = (float)(1 / sqrt(var + eps)))
+# gives mean = m and rstd = 2 or 1 exactly.  gamma = +-1 and an integer beta make a = rstd gamma and b = beta - m a small integers, and
+# u = relu(t a + b) an integer of at most 16: the convolution's input, product by product exact, padded with zeros of u (not with relu(b)).
+
+BNECK_EPS = 0.25
+BNECK_TH, BNECK_TW = 16, 32   # the kernel's output tile
+# (n or None, h, w, keep, rows): n None = chosen by the CU count so that 2 cus < tiles < 3 cus (``bneck_batch``); keep = the share of non-zero weights (0.25
+# where the kernel leaves GroupNorm sums: the sums of squares of a tile stay below 2^24); rows = "image" (one row of input partials per image) or
+# "straddle" (rows of 2/3 of an image: most hold the pieces of two images)
+BNECK_CASES = [
+    (2, 24, 32, 0.25, "image"),       # sums; the last tile row is ragged (8 of 16 rows)
+    (3, 37, 45, 0.5, "straddle"),     # ragged both ways, no sums
+    (2, 16, 32, 0.25, "image"),       # exactly one tile per image; sums
+    (1, 1, 1, 0.5, "image"),
+    (1, 3, 70, 0.5, "image"),         # three tiles in a row, the last one 6 columns wide
+    (None, 17, 33, 0.5, "image"),     # 4 mostly empty tiles per image, more than two trips of the tile loop, no sums
+    (None, 24, 32, 0.25, "image"),    # the same with sums
+]
+
+
+def bneck_tiles(h, w):
+    """(tiles per image, tiles along x)."""
+    tx, ty = -(-w // BNECK_TW), -(-h // BNECK_TH)
+    return tx * ty, tx
+
+
+def bneck_has_sums(h, w):
+    """launch_bneck's rule: the kernel leaves GroupNorm sums where the width is whole tiles and the tiles per image divide the pixels."""
+    return w % BNECK_TW == 0 and (h * w) % bneck_tiles(h, w)[0] == 0
+
+
+def bneck_batch(case, cus):
+    """The case's batch on a device of ``cus`` CUs (grid = min(tiles, cus)); for the multi-trip cases the premise is asserted: 2 cus < tiles < 3 cus, so
+    some workgroups make three trips and the rest two, and a workgroup's consecutive trips (cus tiles apart) lie in different images."""
+    n, h, w = case[:3]
+    if n is not None:
+        return n
+    per = bneck_tiles(h, w)[0]
+    n = (5 * cus // 2) // per
+    assert 2 * cus < n * per < 3 * cus and cus >= per, f"{cus} CUs: {n * per} tiles do not lie between two and three trips"
+    return n
+
+
+def bneck_statistics(n):
+    """m [n][32] int64 in -2..2 and v [n][32] float64 in {0, 0.75}, by formula from the pair index i = 32 img + g as norm_reference.gn_offset: m changes between
+    neighbouring groups and between ANY two images whose distance is no multiple of 5; v changes between two consecutive images in two cases of three."""
+    img, g = torch.arange(n)[:, None], torch.arange(32)[None, :]
+    i = img * 32 + g
+    m = (i * 7 + 3) % 5 - 2
+    v = ((img + g + img // 3) % 2).double() * 0.75
+    return m, v
+
+
+def bneck_partials(m, v, hw, tile_rows):
+    """The input partials float64 [tiles][2][2][64] in the layout of norm_reference.gn_tile_partials (tiles of ``tile_rows`` rows of the [n hw][64] matrix; h = 0:
+    the rows of the image the tile starts in, h = 1: those of the next one): a piece of r rows of image i holds sum = r m and sq = r (m^2 + v) in both
+    channels of a group -- over an image hw m and hw (m^2 + v): mean m, variance v.  All are multiples of 1/4 below 2^24: exact floats."""
+    n = m.shape[0]
+    mc, vc = m.double().repeat_interleave(2, dim=1), v.repeat_interleave(2, dim=1)  # per channel
+    assert 0 < tile_rows <= hw
+    tiles = -(-n * hw // tile_rows)
+    partial = torch.zeros(tiles, 2, 2, 64, dtype=torch.float64)
+    for t in range(tiles):
+        r0, r1 = t * tile_rows, min((t + 1) * tile_rows, n * hw)
+        split = min(r1, (r0 // hw + 1) * hw)
+        for h_, (img, r) in enumerate(((r0 // hw, split - r0), (r0 // hw + 1, r1 - split))):
+            if r > 0:
+                partial[t, h_, 0], partial[t, h_, 1] = r * mc[img], r * (mc[img] ** 2 + vc[img])
+    assert torch.equal(partial.float().double(), partial) and float(partial.abs().max()) < LIMIT
+    return partial
+
+
+def bneck_finalize(partial, n, hw, tile_rows, eps=BNECK_EPS):
+    """gn_finalize_tiles_kernel restated (float64, C = 64, G = 32): (mean, rstd) [n][32] as it stores them, in float32."""
+    mean, rstd = np.empty((n, 32), dtype=np.float32), np.empty((n, 32), dtype=np.float32)
+    p = partial.numpy()
+    for img in range(n):
+        t0, t1 = img * hw // tile_rows, (img * hw + hw - 1) // tile_rows
+        s, q = np.zeros(64), np.zeros(64)
+        for t in range(t0, t1 + 1):
+            h_ = 0 if t * tile_rows // hw == img else 1
+            s, q = s + p[t, h_, 0], q + p[t, h_, 1]
+        s, q, cnt = s.reshape(32, 2).sum(1), q.reshape(32, 2).sum(1), float(hw * 2)
+        mu = s / cnt
+        var = np.maximum(q / cnt - mu * mu, 0.0)
+        mean[img], rstd[img] = mu.astype(np.float32), (1.0 / np.sqrt(var + float(np.float32(eps)))).astype(np.float32)
+    return mean, rstd
+
+
+def bneck_operands(n, h, w, keep, rows, seed=0):
+    """t [n][h][w][64] in -2..2 with a border ring of 3..5, the input partials [tiles][2][2][64] (float64) and their tile rows, gamma [64] +-1, beta [64] in
+    -2..2, weight [64][64][3][3] in {-1, 0, 1}, a and b [n][64] (int64: y = t a + b), and the bound.  Asserts every condition named above."""
+    hw = h * w
+    g = _gen(seed * 22801763 + n * 1009 + h * 3 + w)
+    m, v = bneck_statistics(n)
+    tile_rows = hw if rows == "image" else max(1, 2 * hw // 3)
+    partial = bneck_partials(m, v, hw, tile_rows)
+    mean, rstd = bneck_finalize(partial, n, hw, tile_rows)
+    want_rstd = torch.where(v == 0, 2.0, 1.0)
+    assert np.array_equal(mean.astype(np.float64), m.double().numpy()) and np.array_equal(rstd.astype(np.float64), want_rstd.numpy()), "mean, rstd are not m and 2 / 1"
+    if n > 1:  # a neighbouring image's statistics are wrong ones
+        assert bool((m[1:] != m[:-1]).all()) and float((want_rstd[1:] != want_rstd[:-1]).double().mean()) > 0.5, "consecutive images share statistics"
+        assert bool((m[:, 1:] != m[:, :-1]).all())
+    gamma = torch.randint(0, 2, (64,), generator=g, dtype=torch.int64) * 2 - 1
+    beta = torch.tensor([-2, -1, 0, 0, 1, 1, 1, 2, 2, 2])[torch.randint(0, 10, (64,), generator=g)]  # (more often positive: b > 0 for more than 40 % of the pairs)
+    a = want_rstd.long().repeat_interleave(2, dim=1) * gamma[None, :]
+    b = beta[None, :] - m.repeat_interleave(2, dim=1) * a
+    t = draw(g, (n, h, w, 64), 2)
+    if h >= 3 and w >= 3:
+        ring_border(t, base=3)
+    wt = draw(g, (64, 64, 3, 3), 1, 1.0 - keep)
+    u = bneck_normalised(t, a, b)
+    assert 0 <= int(u.min()) and int(u.max()) <= 16
+    frac = float((u != 0).double().mean())
+    assert frac >= 0.4, f"only {frac:.3f} of the normalised input is non-zero"
+    shown = float((b > 0).double().mean())
+    assert shown >= 0.4, f"relu(b) != 0 for only {shown:.3f} of the (image, channel) pairs: a normalised zero in the padding would not show"
+    wm = weight_matrix(wt)
+    assert bool((wm != 0).any(dim=0).all()), "a K position has no non-zero weight in any output channel"
+    bound = upper_bound(u, wm)
+    assert bound < LIMIT
+    return t, partial, tile_rows, gamma, beta, wt, a, b, bound
+
+
+def bneck_normalised(t, a, b):
+    """u = relu(t a + b): the tensor the convolution reads (the same dtype and device as t; a, b [n][64])."""
+    return (t * a[:, None, None, :].to(t.device, t.dtype) + b[:, None, None, :].to(t.device, t.dtype)).clamp_min(0)
+
+
+def conv3x3_exact(x, wt, chunk=16):
+    """3 x 3 convolution, stride 1, one pixel of zeros all round, in float64 on x's device, ``chunk`` images at a time (the im2col matrix stays small)."""
+    n, h, w, _ = x.shape
+    wd = wt.to(x.device)
+    return torch.cat([conv_exact(x[i:i + chunk].double(), wd, 1, 1, 1, h, w) for i in range(0, n, chunk)])
+
+
+def bneck_tile_sums(y, h, w):
+    """Sum and sum of squares of y [n][h][w][64] (float64) over the pixels of every 16 x 32 tile, tiles numbered as the kernel numbers them: [tiles][2][64]."""
+    n = y.shape[0]
+    per, tx = bneck_tiles(h, w)
+    yy, xx = torch.arange(h, device=y.device)[:, None], torch.arange(w, device=y.device)[None, :]
+    tile = ((yy // BNECK_TH) * tx + xx // BNECK_TW).reshape(-1)
+    idx = (torch.arange(n, device=y.device)[:, None] * per + tile[None, :]).reshape(-1)
+    rows = y.reshape(n * h * w, 64)
+    out = torch.zeros(n * per, 2, 64, dtype=torch.float64, device=y.device)
+    out[:, 0].index_add_(0, idx, rows)
+    out[:, 1].index_add_(0, idx, rows * rows)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# bilinear x2 upsampling, align_corners=True (csrc/dpt_ops.hip upsample2x_kernel / upsample2x_lds_kernel, and phase (b) of csrc/dpt_head.hip): both files
+# are built without contraction, so the result is a fixed sequence of float32 operations -- restated here in numpy float32, one rounded operation per step
+
+UPSAMPLE_CASES = [(1, 8, 1, 1), (1, 8, 1, 9), (1, 16, 9, 1), (2, 32, 7, 5), (1, 128, 24, 32), (2, 256, 15, 20), (1, 1024, 6, 5)]  # (N, C, H, W); C = 1024: the gather form by the rule
+
+
+def upsample_axis(size):
+    """Per output index 0 .. 2 size - 1: (i0, i1, l0, l1) -- s = f32(size - 1) / f32(2 size - 1), f = s * f32(o), i0 = int(f), i1 = min(i0 + 1, size - 1),
+    l1 = f - f32(i0), l0 = 1 - l1, every operation in float32."""
+    one = np.float32
+    out = 2 * size
+    s = one(size - 1) / one(out - 1) if out > 1 else one(0)
+    f = s * np.arange(out).astype(np.float32)
+    i0 = f.astype(np.int32)
+    i1 = np.minimum(i0 + 1, size - 1)
+    l1 = f - i0.astype(np.float32)
+    l0 = one(1) - l1
+    assert f.dtype == l0.dtype == l1.dtype == np.float32 and int(i0.min()) >= 0 and int(i1.max()) <= size - 1
+    return i0, i1, l0, l1
+
+
+def upsample2x_blend_f32(v):
+    """v float32 [N][H][W][C] -> float32 [N][2 H][2 W][C]: y = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11), before the rounding to the element type."""
+    assert v.dtype == np.float32
+    y0, y1, h0, h1 = upsample_axis(v.shape[1])
+    x0, x1, w0, w1 = upsample_axis(v.shape[2])
+    w0, w1, h0, h1 = w0[None, None, :, None], w1[None, None, :, None], h0[None, :, None, None], h1[None, :, None, None]
+    r0, r1 = v[:, y0], v[:, y1]
+    top = w0 * r0[:, :, x0] + w1 * r0[:, :, x1]
+    bot = w0 * r1[:, :, x0] + w1 * r1[:, :, x1]
+    out = h0 * top + h1 * bot
+    assert out.dtype == np.float32
+    return out
+
+
+def upsample2x_f32(x, bias=None):
+    """x [N][H][W][C] of a 16-bit type (CPU) -> [N][2 H][2 W][C] of that type: the optional bias [C] first, (T)(x + b) with the sum in float32; the blend
+    in float32; one rounding to the element type."""
+    dtype = x.dtype
+    assert dtype in (torch.bfloat16, torch.float16)
+    v = x.float()
+    if bias is not None:
+        v = (v + bias.float()[None, None, None, :]).to(dtype).float()
+    assert bool(torch.isfinite(v).all())
+    return torch.from_numpy(upsample2x_blend_f32(v.numpy())).to(dtype)
+
+
+def upsample_operands(N, C, H, W, dtype, seed=0):
+    """x [N][H][W][C] and bias [C] of the element type: normal values x 2^(-6..6) (at least 2^-10 in magnitude), one in sixteen an exact zero, one in sixteen within a few steps of the largest
+    finite value (either sign); the bias in -4..4 in steps of 1/8 (x + bias stays finite: half a step of the largest values is 16 in float16)."""
+    g = _gen(seed * 2750159 + N * 1009 + C * 131 + H * 3 + W)
+    shape = (N, H, W, C)
+    x = torch.randn(shape, generator=g, dtype=torch.float32) * torch.exp2(torch.randint(-6, 7, shape, generator=g).float())
+    x = torch.where(x.abs() < 2.0 ** -10, torch.copysign(torch.full_like(x, 2.0 ** -10), x), x)  # (no subnormal inputs)
+    kind = torch.randint(0, 16, shape, generator=g)
+    big = torch.finfo(dtype).max * (1.0 - torch.randint(0, 8, shape, generator=g).float() * torch.finfo(dtype).eps) * (torch.randint(0, 2, shape, generator=g) * 2 - 1).float()
+    x = torch.where(kind == 0, torch.zeros_like(x), torch.where(kind == 1, big, x)).to(dtype)
+    bias = (torch.randint(-32, 33, (C,), generator=g).float() / 8.0).to(dtype)
+    assert bool(torch.isfinite(x).all()) and bool(torch.isfinite((x.float() + bias.float()).to(dtype)).all())
+    if x.numel() >= 256:
+        assert bool((x == 0).any()) and bool((x.float().abs() > 0.99 * torch.finfo(dtype).max).any())
+    tiny = torch.finfo(dtype).tiny
+    assert bool(((x == 0) | (x.float().abs() >= tiny)).all()), "a subnormal input"
+    return x, bias
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the fused depth head (csrc/dpt_head.hip): x2 upsampling -> conv 3 x 3 (128 -> 32) + bias -> ReLU -> conv 1 x 1 + bias -> ReLU -> inversion -> hand-off
+#
+# x in 1..5 and b0 in 0..3: every upsampled value lies in [1, 8], a multiple of 2^-10 (float16) or 2^-7 (bfloat16).  w3 in -1..1 and an integer b3 in -8..8: a
+# 3 x 3 sum has sum |terms| <= 1152 * 8 + 8 = 9224 < 2^14, i.e. below 2^24 in units of 2^-10: exact in float32 in any order, the four-wave exchange included.
+# The same holds for the 1 x 1 sums while sum |feat w1| + |b1| < 2^14 (asserted per pixel).  From there the epilogue is norm_reference.head_tail_reference.
+
+HEAD_UNIT = 2.0 ** -10
+HEAD_SCALE, HEAD_SHIFT, HEAD_DEPTH_SCALE, HEAD_MAX_DEPTH = 2.0 ** -8, 0.1378, 0.001, 10.0
+HEAD_TH, HEAD_TW = 8, 16      # the kernel's output tile
+HEAD_GRID = "grid"            # every (b0, non_negative, invert), and each output on its own
+# (N or None, H, W, variants): N None = chosen by the CU count so that 4 cus < tiles < 6 cus (the grid is 2 cus: ``head_batch``); variants = HEAD_GRID or a
+# list of (b0 given, non_negative, invert)
+HEAD_CASES = [
+    (1, 2, 2, [(False, 1, 1)]),                   # the 10 x 18 patch is larger than the 4 x 4 output on all sides
+    (1, 2, 40, HEAD_GRID),                        # 5 tiles in a row, half of each below the map
+    (2, 13, 21, [(True, 1, 0)]),                  # ragged both ways
+    (1, 48, 64, [(False, 1, 1)]),                 # 96 whole tiles, as the network calls it (no b0)
+    (None, 5, 9, [(True, 1, 1), (False, 1, 1)]),  # 4 ragged tiles per image; two and three trips of the tile loop: the LDS-DMA prefetch of the next tile's patch
+]
+
+
+def head_tiles(H, W):
+    return -(-2 * H // HEAD_TH) * -(-2 * W // HEAD_TW)
+
+
+def head_batch(case, cus):
+    N, H, W = case[:3]
+    if N is not None:
+        return N
+    per = head_tiles(H, W)
+    N = (5 * cus) // per
+    assert 4 * cus < N * per < 6 * cus, f"{cus} CUs: {N * per} tiles do not lie between two and three trips of a grid of {2 * cus}"
+    return N
+
+
+def head_variants(case):
+    if case[3] != HEAD_GRID:
+        return list(case[3])
+    return [(b0, nn, inv) for b0 in (False, True) for nn in (0, 1) for inv in (0, 1)]
+
+
+def head_sums(x, b0, w3, dtype, device="cpu"):
+    """The exact 3 x 3 sums float64 [N][2 H][2 W][32] (on ``device``) over the restated upsampling of x + b0 in the element type, zero padding.  Asserts that
+    the upsampled values lie in [1, 8] and are multiples of 2^-10."""
+    up = upsample2x_f32(x.to(dtype), None if b0 is None else b0.to(dtype)).double()
+    assert float(up.min()) >= 1.0 and float(up.max()) <= 8.0 and torch.equal(torch.round(up / HEAD_UNIT) * HEAD_UNIT, up)
+    return conv3x3_exact(up.to(device), w3, chunk=8)
+
+
+def head_pre(feat, b3, w1, b1):
+    """The 1 x 1 sums before the last ReLU, float64 [pixels], and the largest sum |relu(feat + b3) w1| + |b1| of a pixel."""
+    f = (feat.reshape(-1, 32) + b3.double().to(feat.device)).clamp_min(0.0)
+    w = w1.double().to(feat.device)
+    return f @ w + float(b1), float((f @ w.abs()).max()) + abs(float(b1))
+
+
+def head_operands(N, H, W, seed=0):
+    """x [N][H][W][128] in 1..5, b0 [128] in 0..3, w3 [32][128][3][3] in -1..1, b3 [32] in -8..8, w1 [32] in -2..2 (all int64), and the integers b1 = (without b0,
+    with b0): minus the median of the 1 x 1 sums of the float16 form (every form's share of clipped pixels is asserted by ``head_expected``)."""
+    g = _gen(seed * 39916801 + N * 1009 + H * 3 + W)
+    x = torch.randint(1, 6, (N, H, W, 128), generator=g, dtype=torch.int64)
+    b0 = torch.randint(0, 4, (128,), generator=g, dtype=torch.int64)
+    w3, b3, w1 = draw(g, (32, 128, 3, 3), 1), draw(g, (32,), 8), draw(g, (32,), 2)
+    assert bool((weight_matrix(w3) != 0).any(dim=0).all()) and int((w1 != 0).sum()) >= 16
+    if N > 1:
+        assert bool((x[1:] != x[:-1]).reshape(N - 1, -1).any(dim=1).all()), "two consecutive images are equal"
+    b1 = tuple(-int(torch.round(head_pre(head_sums(x, b, w3, torch.float16), b3, w1, 0)[0].median())) for b in (None, b0))
+    return x, b0, w3, b3, w1, b1
+
+
+def head_expected(feat, b3, w1, b1, non_negative, invert):
+    """(depth float32, millimetres uint16, metres float32) [pixels] from the exact 3 x 3 sums: norm_reference.head_tail_reference on them in units of 2^-10 (its
+    operands are integers then; scale / 2^10 times the integer accumulator is the product scale * acc, exactly).  Without the inversion the depth is the
+    accumulator itself: scaled back exactly, and handed off in millimetres as the epilogue states it.  Asserts the exactness condition of the 1 x 1
+    sums and that the last ReLU clips between 10 % and 90 % of the pixels."""
+    pre, worst = head_pre(feat, b3, w1, b1)
+    assert worst < 2 ** 14, f"sum |feat w1| + |b1| reaches {worst}"
+    clipped = float((pre < 0).double().mean())
+    assert 0.1 <= clipped <= 0.9, f"the last ReLU clips {clipped:.3f} of the pixels"
+    one = np.float32
+    units = (feat.reshape(-1, 32) / HEAD_UNIT).cpu().numpy()
+    args = (units, b3.double().numpy() / HEAD_UNIT, True, w1.numpy().astype(np.float32), float(b1) / HEAD_UNIT, non_negative)
+    if invert:
+        return R.head_tail_reference(*args, True, HEAD_SCALE * HEAD_UNIT, HEAD_SHIFT, HEAD_DEPTH_SCALE, HEAD_MAX_DEPTH)
+    acc = R.head_tail_reference(*args, False, 1.0, 0.0, HEAD_DEPTH_SCALE, HEAD_MAX_DEPTH)[0]
+    depth = acc * one(HEAD_UNIT)
+    assert np.array_equal(depth.astype(np.float64), pre.clamp_min(0.0).cpu().numpy() if non_negative else pre.cpu().numpy())
+    mm = np.minimum(np.maximum(depth * one(1000), one(0)), one(65535)).astype(np.int32).astype(np.uint16)
+    return depth, mm, R.depth_mm_to_m_reference(mm, HEAD_DEPTH_SCALE, HEAD_MAX_DEPTH)

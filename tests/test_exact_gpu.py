@@ -6,6 +6,10 @@ order, the split-K partition or the tile shape.  Every comparison below is ``tor
 exceptions (the GELU epilogue, the counting case of attention) state their bound.  The references are index arithmetic and float64 matmuls written in
 the test tree (tests/test_exact_reference_cpu.py checks them against nested loops); nothing comes from ``hive_amd.dpt.models``.
 
+The same holds for the persistent kernels of csrc/bneck.hip (hive_bneck_gn_conv3x3: the test supplies the GroupNorm sums, so mean and rstd are small integers of its own
+choosing per image and group) and csrc/dpt_head.hip (hive_dpt_head_fused: integer inputs whose upsampled values lie on a 2^-10 grid), both through more than two trips of
+their tile loops, and for hive_nhwc_upsample2x, whose un-contracted float32 arithmetic exact_reference.upsample2x_f32 restates operation by operation.
+
 The shapes are the smallest that reach each kernel, ring depth, split and tail by the launch rules of launch_gemm / qkv_t / attention_t / launch_conv_t on
 the MI355X's 256 CUs; where a case's path depends on the CU count the rule (restated in exact_reference.gemm_path / conv_path) is asserted to select it on
 this device, and the context's launch counters are asserted to have moved accordingly.  A device where it does not fails -- nothing is skipped."""
@@ -480,3 +484,161 @@ def test_gram_parts_exact(gpu_ctx, half, n, cin, cout, stride, h, w):
     S_want, s_want = E.gram_exact(x64.cuda(), stride)
     assert torch.equal(S.double().sum(1), S_want), f"X^T X: max difference {(S.double().sum(1) - S_want).abs().max().item()}"
     assert torch.equal(s.double().sum(1), s_want), f"sum x: max difference {(s.double().sum(1) - s_want).abs().max().item()}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# hive_bneck_gn_conv3x3 (csrc/bneck.hip) through the C ABI: the test supplies the GroupNorm sums, so the statistics are its own
+
+SENTINEL = -123456.0  # float buffers the kernel may not write
+
+
+def _bneck_case(case):
+    """The operands (CPU, int64 / float64) and the exact convolution float64 [n][h][w][64] on the device, computed 16 images at a time."""
+    def make():
+        n = E.bneck_batch(case, _cus())
+        t, partial, tile_rows, gamma, beta, wt, a, b, _ = E.bneck_operands(n, *case[1:])
+        exact = E.conv3x3_exact(E.bneck_normalised(t.cuda(), a, b), wt)
+        return n, t, partial, tile_rows, gamma, beta, wt, exact
+    return _cached(("bneck",) + tuple(case), make)
+
+
+def _bneck(ctx, half, t, partial, tile_rows, gamma, beta, w, n, h, wd, C=64, eps=E.BNECK_EPS):
+    """One call into a poisoned output and a sentinel-filled buffer for the sums, both with a guard region behind.  -> (out buffer (int16 view), out, sums, tile rows, fused)"""
+    import ctypes
+    tiles = n * E.bneck_tiles(h, wd)[0]
+    buf, out = _poisoned(n * h * wd * 64 + GUARD, half)
+    sums = torch.full((tiles * 4 * 64 + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    rows, fused = ctypes.c_int(-1), ctypes.c_int(-1)
+    ctx.check(ctx.lib.hive_bneck_gn_conv3x3(ctx.handle, t.data_ptr(), _code(half), n, h, wd, C, None if partial is None else partial.data_ptr(), tile_rows,
+                                            gamma.data_ptr(), beta.data_ptr(), eps, w.data_ptr(), out.data_ptr(), sums.data_ptr(), tiles * 4 * 64,
+                                            ctypes.byref(rows), ctypes.byref(fused)))
+    torch.cuda.synchronize()
+    return buf, out, sums, rows.value, fused.value
+
+
+@pytest.mark.parametrize("case", E.BNECK_CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_bneck_exact(gpu_ctx, half, case):
+    """conv2(relu(norm1(t))) bit for bit: round_once of the integer convolution of u = relu(t a + b) with zero padding, for statistics that differ from image to
+    image (so a neighbouring image's a, b -- or a normalised zero in the padding -- gives other integers), through more than two trips of the tile loop.  Where the
+    kernel leaves GroupNorm sums, row ``tile`` holds exactly the integer sum and sum of squares of THAT tile's stored outputs; where not, it writes none."""
+    n, t64, partial64, tile_rows, gamma64, beta64, wt64, exact = _bneck_case(case)
+    h, w = case[1:3]
+    cus, (per, _) = _cus(), E.bneck_tiles(h, w)
+    tiles = n * per
+    if case[0] is None:  # the premise, on this device: grid = min(tiles, CUs)
+        print(f"  premise: {tiles} tiles on {cus} workgroups: {tiles - 2 * cus} of them make three trips, the rest two; trips {cus // per} images apart")
+        assert 2 * cus < tiles < 3 * cus and cus % per == 0 and (cus // per) % 5 != 0, "three and two trips, consecutive trips in images with other statistics"
+    t, gamma, beta = _dev(t64, half), _dev(gamma64, half), _dev(beta64, half)
+    wgt = _dev(wt64.permute(0, 2, 3, 1).contiguous(), half)  # [co][(ky, kx, ci)]
+    partial = partial64.to(device="cuda", dtype=torch.float32)
+    buf, out, sums, rows, fused = _bneck(gpu_ctx, half, t, partial, tile_rows, gamma, beta, wgt, n, h, w)
+    assert fused == 1
+    assert _untouched(buf, n * h * w * 64), "the guard region behind the output was written"
+    got, want = out[:n * h * w * 64].view(n, h, w, 64), E.round_once(exact, half)
+    assert torch.equal(got, want), f"{int((got != want).sum())} of {want.numel()} outputs differ, first in image {int((got != want).reshape(n, -1).any(1).nonzero()[0])}"
+    if E.bneck_has_sums(h, w):
+        assert rows == h * w // per
+        stored = E.bneck_tile_sums(want.double(), h, w)  # [tiles][2][64]
+        assert float(stored[:, 1].max()) < E.LIMIT and float(stored[:, 0].abs().max()) < E.LIMIT, "a tile's sum is not exact in float32"
+        left = sums[:tiles * 4 * 64].view(tiles, 2, 2, 64).double()
+        assert torch.equal(left[:, 0], stored), f"{int((left[:, 0] != stored).sum())} sums differ, first in tile {int((left[:, 0] != stored).reshape(tiles, -1).any(1).nonzero()[0])}"
+        assert float(left[:, 1].abs().max()) == 0.0, "the h = 1 half must be zero"
+        assert bool((sums[tiles * 4 * 64:] == SENTINEL).all()), "the guard region behind the sums was written"
+    else:
+        assert rows == 0 and bool((sums == SENTINEL).all()), "no sums are left here: the buffer must stay untouched"
+
+
+def test_bneck_not_eligible_writes_nothing(gpu_ctx, half):
+    """C != 64, no input sums, or no tile rows: *fused == 0, *gn_tile_rows == 0, and neither the output nor the sums are touched."""
+    case = E.BNECK_CASES[2]
+    n, t64, partial64, tile_rows, gamma64, beta64, wt64, _ = _bneck_case(case)
+    h, w = case[1:3]
+    t, gamma, beta, wgt = _dev(t64, half), _dev(gamma64, half), _dev(beta64, half), _dev(wt64.permute(0, 2, 3, 1).contiguous(), half)
+    partial = partial64.to(device="cuda", dtype=torch.float32)
+    for what, kw in (("C = 32", dict(partial=partial, tile_rows=tile_rows, C=32)), ("NULL d_in_partial", dict(partial=None, tile_rows=tile_rows)),
+                     ("in_tile_rows = 0", dict(partial=partial, tile_rows=0)), ("in_tile_rows = -1", dict(partial=partial, tile_rows=-1))):
+        buf, _, sums, rows, fused = _bneck(gpu_ctx, half, t, kw["partial"], kw["tile_rows"], gamma, beta, wgt, n, h, w, C=kw.get("C", 64))
+        assert fused == 0 and rows == 0, what
+        assert _untouched(buf, 0) and bool((sums == SENTINEL).all()), f"{what}: a buffer was written"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# hive_nhwc_upsample2x (csrc/dpt_ops.hip): both forms against the float32 restatement
+
+@pytest.mark.parametrize("N,C,H,W", E.UPSAMPLE_CASES)
+def test_upsample2x_bit_exact(gpu_ctx, half, monkeypatch, N, C, H, W):
+    """The LDS-tile form (C <= 512) and the gather form (HIVE_UPSAMPLE_GATHER, and C = 1024 by the rule), with and without the folded bias: equal to
+    exact_reference.upsample2x_f32 bit for bit -- small values, exact zeros and values next to the largest finite one included."""
+    x, bias = E.upsample_operands(N, C, H, W, half)
+    xd, bd = x.cuda(), bias.cuda()
+    n_out = N * 4 * H * W * C
+    for with_bias in (False, True):
+        want = _cached(("up", N, C, H, W, half, with_bias), lambda: E.upsample2x_f32(x, bias if with_bias else None).cuda())
+        for gather in (False, True):
+            if gather:
+                monkeypatch.setenv("HIVE_UPSAMPLE_GATHER", "1")
+            else:
+                monkeypatch.delenv("HIVE_UPSAMPLE_GATHER", raising=False)
+            buf, out = _poisoned(n_out + GUARD, half)
+            gpu_ctx.check(gpu_ctx.lib.hive_nhwc_upsample2x(gpu_ctx.handle, xd.data_ptr(), bd.data_ptr() if with_bias else None, _code(half), N, H, W, C, out.data_ptr()))
+            torch.cuda.synchronize()
+            assert _untouched(buf, n_out), "guard region written"
+            got = out[:n_out].view(N, 2 * H, 2 * W, C)
+            what = f"{'gather' if gather or C > 512 else 'LDS tile'} form, {'with' if with_bias else 'no'} bias"
+            assert torch.equal(got, want), f"{what}: {int((got != want).sum())} of {n_out} elements differ"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# hive_dpt_head_fused (csrc/dpt_head.hip)
+
+def _head_case(case):
+    def make():
+        N = E.head_batch(case, _cus())
+        return (N,) + E.head_operands(N, case[1], case[2])
+    return _cached(("head",) + tuple(case[:3]), make)
+
+
+def _head(ctx, half, x, b0, w3, b3, w1, b1, N, H, W, non_negative, invert, outputs=(True, True, True)):
+    """One call; the outputs not requested are passed as NULL and stay sentinel-filled, a guard region behind each stays untouched.  -> (depth, mm, m) numpy"""
+    n_px = N * 4 * H * W
+    depth = torch.full((n_px + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    mm = torch.full((n_px + GUARD,), 0x5A5A, dtype=torch.int16, device="cuda")
+    m = torch.full((n_px + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    ptr = [b.data_ptr() if on else None for b, on in zip((depth, mm, m), outputs)]
+    ctx.check(ctx.lib.hive_dpt_head_fused(ctx.handle, x.data_ptr(), None if b0 is None else b0.data_ptr(), _code(half), N, H, W, 128, 32, w3.data_ptr(), b3.ctypes.data,
+                                          w1.ctypes.data, float(b1), int(non_negative), int(invert), E.HEAD_SCALE, E.HEAD_SHIFT, ptr[0], E.HEAD_DEPTH_SCALE,
+                                          E.HEAD_MAX_DEPTH, ptr[1], ptr[2]))
+    torch.cuda.synchronize()
+    for buf, on, fill in ((depth, outputs[0], SENTINEL), (mm, outputs[1], 0x5A5A), (m, outputs[2], SENTINEL)):
+        assert bool((buf[n_px if on else 0:] == fill).all()), "an output that was not requested, or a guard region, was written"
+    return depth[:n_px].cpu().numpy(), mm[:n_px].cpu().numpy().view("uint16"), m[:n_px].cpu().numpy()
+
+
+@pytest.mark.parametrize("case", E.HEAD_CASES, ids=lambda c: "x".join(str(v) for v in c[:3]))
+def test_head_fused_exact(gpu_ctx, half, case):
+    """depth, millimetres and metres bit for bit: the restated upsampling of x + b0 (not the product's kernel), exact 3 x 3 sums with zero padding, exact 1 x 1
+    sums, then the epilogue as norm_reference.head_tail_reference states it -- with b0 and with NULL (as the network calls it), non_negative and invert on and
+    off, every output on its own, and through two and three trips of the tile loop (the LDS-DMA prefetch of the next tile's patch)."""
+    import numpy as np
+    N, x64, b0_64, w3_64, b3_64, w1_64, b1 = _head_case(case)
+    H, W = case[1:3]
+    cus, tiles = _cus(), N * E.head_tiles(H, W)
+    if case[0] is None:  # the premise, on this device: grid = min(tiles, 2 CUs)
+        print(f"  premise: {tiles} tiles on {2 * cus} workgroups: {tiles - 4 * cus} of them make three trips, the rest two")
+        assert 4 * cus < tiles < 6 * cus
+    x, w3 = _dev(x64, half), _dev(w3_64.permute(2, 3, 0, 1).contiguous(), half)  # [tap][oc][ic]
+    b0 = b0_64.to(device="cuda", dtype=torch.float32)
+    b3, w1 = b3_64.numpy().astype(np.float32), w1_64.numpy().astype(np.float32)
+    variants = E.head_variants(case)
+    for with_b0 in sorted({v[0] for v in variants}):
+        feat = _cached(("head-sums", half, with_b0) + tuple(case[:3]), lambda: E.head_sums(x64, b0_64 if with_b0 else None, w3_64, half, device="cuda"))
+        for _, nn, inv in [v for v in variants if v[0] == with_b0]:
+            want = E.head_expected(feat, b3_64, w1_64, b1[with_b0], nn, inv)
+            got = _head(gpu_ctx, half, x, b0 if with_b0 else None, w3, b3, w1, b1[with_b0], N, H, W, nn, inv)
+            for name, a, b in zip(("depth", "millimetres", "metres"), got, want):
+                assert a.dtype == b.dtype and np.array_equal(a, b), f"b0 {with_b0}, non_negative {nn}, invert {inv}: {int((a != b).sum())} of {a.size} {name} differ"
+            if case[3] == E.HEAD_GRID and (with_b0, nn, inv) == (True, 1, 1):  # any one output alone
+                for k in range(3):
+                    outputs = tuple(j == k for j in range(3))
+                    alone = _head(gpu_ctx, half, x, b0, w3, b3, w1, b1[True], N, H, W, nn, inv, outputs)
+                    assert np.array_equal(alone[k], want[k]), f"output {k} alone"

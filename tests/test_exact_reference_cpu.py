@@ -300,3 +300,155 @@ def test_other_operands_meet_their_conditions():
     for n, cin, cout, stride, h, w in E.GRAM_CASES:
         oh, ow = (h + stride - 1) // stride, (w + stride - 1) // stride
         assert E.gram_operands(n, cin, h, w, oh, ow)[1] < E.LIMIT
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# bottleneck convolution, x2 upsampling, fused depth head
+
+import norm_reference as R
+
+HALVES = [torch.bfloat16, torch.float16]
+
+
+def _same(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return torch.equal(a, b) if torch.is_tensor(a) else a == b
+
+
+def test_bneck_partials_are_in_the_layout_of_gn_tile_partials():
+    """With v = 0 the rows equal norm_reference.gn_tile_partials of a tensor that holds m in every pixel of an (image, group); with v they finalise to (m, 2 | 1)."""
+    for n, hw, tile_rows in ((3, 300, 200), (2, 37, 37), (3, 131, 128), (4, 768, 512)):
+        m, v = E.bneck_statistics(n)
+        x = m.repeat_interleave(2, dim=1)[:, None, :].expand(n, hw, 64).numpy()
+        got = E.bneck_partials(m, torch.zeros_like(v), hw, tile_rows)
+        assert np.array_equal(got.numpy(), R.gn_tile_partials(x, tile_rows).astype(np.float64))
+        assert tile_rows == hw or R.gn_straddling_tiles(n, hw, tile_rows) >= 1
+        mean, rstd = E.bneck_finalize(E.bneck_partials(m, v, hw, tile_rows), n, hw, tile_rows)
+        assert np.array_equal(mean, m.numpy().astype(np.float32)) and np.array_equal(rstd, np.where(v.numpy() == 0, 2.0, 1.0).astype(np.float32))
+        assert set(np.unique(rstd)) == {1.0, 2.0} and set(np.unique(mean)) == {-2.0, -1.0, 0.0, 1.0, 2.0}
+    for d in (1, 2, 3, 4, 64, 128):  # two images this far apart never share a group's mean (bneck_batch: a workgroup's consecutive trips at 256 CUs are 64 / 128 images apart)
+        m, _ = E.bneck_statistics(d + 7)
+        assert bool((m[d:] != m[:-d]).all())
+
+
+@pytest.mark.parametrize("case", E.BNECK_CASES, ids=str)
+def test_bneck_operands_meet_their_conditions(case):
+    """The generator's own assertions at every case (256 CUs), determinism, the premise of the multi-trip cases, and from the reference: where the kernel leaves sums
+    every tile / channel sum of squares of the stored outputs is below 2^24 in both element types."""
+    n = E.bneck_batch(case, 256)
+    h, w, keep, rows = case[1:]
+    ops = E.bneck_operands(n, h, w, keep, rows)
+    assert _same(ops, E.bneck_operands(n, h, w, keep, rows)), "the generator is not deterministic"
+    t, partial, tile_rows, gamma, beta, wt, a, b, bound = ops
+    per, _ = E.bneck_tiles(h, w)
+    assert (keep == 0.25) == E.bneck_has_sums(h, w) and bound < E.LIMIT
+    assert (tile_rows == h * w) == (rows == "image") and (rows == "image" or R.gn_straddling_tiles(n, h * w, tile_rows) >= 1)
+    if case[0] is None:
+        assert 2 * 256 < n * per < 3 * 256
+    for tt in (t, gamma, beta, wt):
+        assert torch.equal(tt.to(torch.bfloat16).long(), tt) and torch.equal(tt.to(torch.float16).long(), tt)
+    if h >= 3 and w >= 3:
+        assert int(t[:, 0].abs().min()) >= 3 and int(t[:, :, -1].abs().min()) >= 3 and int(t[:, 1:-1, 1:-1].abs().max()) <= 2
+    u = E.bneck_normalised(t, a, b)
+    y = E.conv3x3_exact(u, wt)
+    assert float(y.abs().max()) <= bound
+    if E.bneck_has_sums(h, w):
+        for dtype in HALVES:
+            sums = E.bneck_tile_sums(E.round_once(y, dtype).double(), h, w)
+            assert sums.shape == (n * per, 2, 64) and float(sums[:, 1].max()) < E.LIMIT and float(sums[:, 0].abs().max()) < E.LIMIT
+
+
+def test_bneck_cases_round_in_bfloat16_and_tile_sums_against_a_loop():
+    """At least one case with half of the weights kept has |y| above 256 (the single rounding to bfloat16 is exercised); bneck_tile_sums against slices."""
+    above, changed = 0, 0
+    for case in [c for c in E.BNECK_CASES if c[3] == 0.5]:
+        n = E.bneck_batch(case, 256)
+        t, _, _, _, _, wt, a, b, _ = E.bneck_operands(n, *case[1:])
+        y = E.conv3x3_exact(E.bneck_normalised(t, a, b), wt)
+        above += int(float(y.abs().max()) > 256)
+        changed += int(not torch.equal(E.round_once(y, torch.bfloat16).double(), y))
+    assert above >= 1 and changed >= 1, f"{above} cases above 256, {changed} with an output that bfloat16 rounds"
+    n, h, w = 2, 24, 64
+    z = torch.arange(n * h * w * 64, dtype=torch.float64).reshape(n, h, w, 64) % 13 - 6
+    got = E.bneck_tile_sums(z, h, w)
+    assert E.bneck_tiles(h, w) == (4, 2)
+    for img in range(n):
+        for ty in range(2):
+            for tx in range(2):
+                blk = z[img, ty * 16:ty * 16 + 16, tx * 32:tx * 32 + 32].reshape(-1, 64)
+                assert torch.equal(got[img * 4 + ty * 2 + tx, 0], blk.sum(0)) and torch.equal(got[img * 4 + ty * 2 + tx, 1], (blk * blk).sum(0))
+
+
+@pytest.mark.parametrize("N,C,H,W", [(1, 8, 1, 1), (1, 8, 1, 9), (1, 8, 9, 1), (2, 8, 7, 5), (1, 8, 24, 32), (1, 8, 15, 20)])
+def test_upsample2x_restatement_against_interpolate_in_float64(N, C, H, W):
+    """The float32 restatement against F.interpolate(align_corners=True) of the same values in float64.  Bound: the source coordinate f = s * o carries two
+    float32 roundings (s, the product), at most 2^-23 (size - 1) per axis, and moves the blend by at most that times the difference of two neighbours
+    (<= 2 max |v|); the blend itself is five rounded operations deep (w0 = 1 - w1, the products, two sums, the outer product and sum: 8 roundings of values
+    of at most max |v|).  The integer parts agree wherever f is not within that error of an integer -- the blend is continuous there."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(H * 100 + W)
+    v = torch.randn((N, H, W, C), generator=g, dtype=torch.float32)
+    got = E.upsample2x_blend_f32(v.numpy()).astype(np.float64)
+    ref = F.interpolate(v.double().permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=True).permute(0, 2, 3, 1).numpy()
+    vmax = float(v.abs().max())
+    bound = (2.0 ** -23 * (H + W) * 2 + 8 * 2.0 ** -24) * vmax
+    assert got.shape == ref.shape == (N, 2 * H, 2 * W, C) and float(np.abs(got - ref).max()) <= bound
+    # the corners are copied (align_corners), and both element types round the same blend once
+    assert np.array_equal(got[:, 0, 0], v.numpy()[:, 0, 0].astype(np.float64))
+    for dtype in HALVES:
+        x = v.to(dtype)
+        assert torch.equal(E.upsample2x_f32(x), torch.from_numpy(E.upsample2x_blend_f32(x.float().numpy())).to(dtype))
+        bias = torch.full((C,), 0.375, dtype=dtype)
+        assert torch.equal(E.upsample2x_f32(x, bias), E.upsample2x_f32((x.float() + 0.375).to(dtype)))
+
+
+def test_upsample2x_is_exact_on_a_constant_map():
+    for dtype in HALVES:
+        for c in (1.0, -3.140625, 0.0, 65504.0 if dtype == torch.float16 else 3.3895313892515355e38, 2.0 ** -10):
+            x = torch.full((1, 7, 5, 8), c, dtype=dtype)
+            assert torch.equal(E.upsample2x_f32(x), torch.full((1, 14, 10, 8), c, dtype=dtype))
+    for size in (1, 2, 5, 24, 240, 320):  # the weights: l0 + l1 = 1 up to one rounding, sources inside the map, the last output on the last source
+        i0, i1, l0, l1 = E.upsample_axis(size)
+        assert float(l1.min()) >= 0 and float(l1.max()) < 1 and i0[0] == 0 and l1[0] == 0 and int(i1[-1]) == size - 1
+        assert bool((np.diff(i0) >= 0).all()) and bool((np.diff(i0) <= 1).all())
+
+
+@pytest.mark.parametrize("N,C,H,W", E.UPSAMPLE_CASES)
+def test_upsample_operands_meet_their_conditions(N, C, H, W):
+    for dtype in HALVES:
+        x, bias = E.upsample_operands(N, C, H, W, dtype)
+        assert _same((x, bias), E.upsample_operands(N, C, H, W, dtype)) and x.dtype == bias.dtype == dtype
+        for b in (None, bias):
+            assert bool(torch.isfinite(E.upsample2x_f32(x, b)).all())
+    assert (C > 512) == (C == 1024), "C = 1024 only takes the gather form by the launch rule"
+
+
+@pytest.mark.parametrize("case", E.HEAD_CASES, ids=lambda c: str(c[:3]))
+def test_head_operands_meet_their_conditions(case):
+    """head_sums / head_expected assert theirs (upsampled values in [1, 8] on the 2^-10 grid, sum |feat w1| + |b1| < 2^14 per pixel, the last ReLU clips 10 - 90 %)
+    for every variant and element type; here also: determinism, the sums' bound, the premise of the multi-trip case at 256 CUs and that the outputs vary."""
+    N = E.head_batch(case, 256)
+    H, W = case[1:3]
+    ops = E.head_operands(N, H, W)
+    assert _same(ops, E.head_operands(N, H, W)), "the generator is not deterministic"
+    x, b0, w3, b3, w1, b1 = ops
+    if case[0] is None:
+        assert 4 * 256 < N * E.head_tiles(H, W) < 6 * 256
+    assert 1 <= int(x.min()) and int(x.max()) <= 5 and 0 <= int(b0.min()) and int(b0.max()) <= 3 and int(w3.abs().max()) == 1 and int(b3.abs().max()) <= 8
+    variants = E.head_variants(case)
+    assert len(variants) == (8 if case[3] == E.HEAD_GRID else len(case[3]))
+    for dtype in HALVES:
+        for with_b0 in sorted({v[0] for v in variants}):
+            feat = E.head_sums(x, b0 if with_b0 else None, w3, dtype)
+            assert float(feat.abs().max()) <= 9224 - 8 and torch.equal(torch.round(feat / E.HEAD_UNIT) * E.HEAD_UNIT, feat)
+            for _, nn, inv in [v for v in variants if v[0] == with_b0]:
+                depth, mm, m = E.head_expected(feat, b3, w1, b1[with_b0], nn, inv)
+                assert depth.dtype == np.float32 and mm.dtype == np.uint16 and m.dtype == np.float32 and depth.shape == (N * 4 * H * W,)
+                assert len(np.unique(depth)) > depth.size // 8 and np.isfinite(depth).all()
+
+
+def test_head_variants_cover_every_option():
+    seen = {v for case in E.HEAD_CASES for v in E.head_variants(case)}
+    assert seen == {(b0, nn, inv) for b0 in (False, True) for nn in (0, 1) for inv in (0, 1)}
+    assert sum(1 for c in E.HEAD_CASES if c[3] == E.HEAD_GRID) == 1
