@@ -179,7 +179,8 @@ def render_mesh(camera_matrix, camera_pose, *meshes, size=None, background=(255,
 
 def psnr(a, b, mask=None):
     """Peak signal-to-noise ratio of two uint8 pictures, ``10 log10(255^2 / mse)`` in float64 (the score of experiments.py:835-852), over the pixels where
-    ``mask`` is true when one is given.  A host helper (device tensors are copied back); inf for identical pictures."""
+    ``mask`` is true when one is given.  A host helper on the colour values (device tensors are copied back); inf for identical pictures.  The reference's
+    own scores -- SSIM and PSNR of the gray pictures, MS-SSIM, on the device -- are ``hive_amd.evaluation.image_similarity``."""
     x, y = _host(a).astype(np.float64), _host(b).astype(np.float64)
     if x.shape != y.shape:
         raise ValueError(f"shapes differ: {x.shape} and {y.shape}")

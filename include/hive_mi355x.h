@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 2
+#define HIVE_ABI_VERSION 3
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -468,6 +468,61 @@ int hive_render_shade(hive_ctx *ctx, int64_t nv, const int32_t *d_faces, int64_t
  * background[3] (NULL = white); d_depth f32 [H][W] (may be NULL) the winner's depth, 0 where empty; d_face i32 [H][W] (may be NULL) its global face index, -1
  * where empty (an index of 2^31 or more does not fit: keep the total below 2^31 when the face plane is wanted). */
 int hive_render_resolve(hive_ctx *ctx, const uint64_t *d_key, int H, int W, const uint8_t background[3], uint8_t *d_color, float *d_depth, int32_t *d_face);
+
+/* ---- scoring a render against a held-out frame -- compare_images(ref_image, est_image), scripts/compare_image_pair.py:110-133, and ms_ssim as called at
+ * scripts/experiments.py:1627-1635; the loops that use them are experiments.py:775-858 (LLFF) and :1554-1637 (HyperNeRF).  Pictures are u8 [N][H][W][3] in
+ * device memory and stay there.  Three libraries are restated from their published definitions; none of them can be run beside this code, so the numbers are
+ * not pinned against cv2 (gray), not pinned against skimage (SSIM, PSNR) and not pinned against pytorch_msssim (MS-SSIM).  tests/similarity_restatement.py states
+ * the same rules in numpy / torch-CPU float64.  The rules (no fused multiply-add anywhere):
+ *   gray       cv2's 8-bit COLOR_BGR2GRAY of OpenCV 3.4, from recall: g = (1868 c0 + 9617 c1 + 4899 c2 + 8192) >> 14, c0 c1 c2 the channels in memory order,
+ *              all integer, result u8.  The reference hands RGB pictures to this BGR conversion, so channel 0 gets the blue weight: that is what its numbers
+ *              contain and it is the default (rgb_order = 0).  rgb_order = 1 swaps the two outer weights (true luma of an RGB picture).
+ *   mask       variant 1 (`variants` = 2) is masked_frame[color_np == [255, 255, 255]] = 255 of experiments.py:846-848 / :1605-1607.  The comparison
+ *              broadcasts, so the rule is per CHANNEL, not per pixel: a channel value of the reference picture reads as 255 wherever the estimate's value in
+ *              that same channel is 255.  Applied while loading; the whitened frame is never written.  Variant 0 is the plain pair.
+ *   SSIM       skimage.metrics.structural_similarity(ref_gray, est_gray, win_size=7) on u8: data_range 255, K1 0.01, K2 0.03, uniform 7 x 7 window, sample
+ *              covariance, float64; the score is the mean of the map cropped by 3 pixels a side, so every window lies inside the picture and no border rule
+ *              exists.  The five window sums Sx, Sy, Sxx, Syy, Sxy (x = ref gray, y = est gray; at most 49 * 255^2) are exact int32.  Then in float64, in
+ *              exactly this order:
+ *                ux = Sx / 49.0, uy, uxx, uyy, uxy likewise;  vx = (49.0 / 48.0) * (uxx - ux * ux), vy likewise;  vxy = (49.0 / 48.0) * (uxy - ux * uy);
+ *                C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
+ *                S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2)),   sums evaluated left to right.
+ *              The map S [H - 6][W - 6] is reproducible bit for bit in numpy.
+ *   SSIM sum   a workgroup owns a 32 x 32 tile of the map (row-major, p = 32 r + c).  Thread t of 256 adds its valid S(p) for p = t, t + 256, t + 512, t + 768 in
+ *              that order to 0.0; then v[t] += v[t + off] for t < off, off = 128, 64, ..., 1; v[0] is the tile's partial.  hive_similarity_finish sums the
+ *              partials of one picture: thread t adds partials t, t + 256, ... in ascending order to 0.0, the same tree follows, and the sum is divided by the
+ *              divisor.  No floating-point atomic exists, so a score has the same bits on every run and in whatever batch the picture came.
+ *   PSNR       skimage.metrics.peak_signal_noise_ratio on the two gray planes: the device returns the exact integer sum of squared differences over all H W
+ *              pixels (one 64-bit integer atomic per workgroup); the caller computes 10 * log10(65025.0 / (sse / (H * W))) in float64, inf when sse == 0.
+ *   MS-SSIM    pytorch_msssim.ms_ssim(X, Y, data_range=1.0, size_average=True): the three colour channels as float64 c / 255.0 (the mask rule applies to X);
+ *              window g[11] given by the caller (a Gaussian, sigma 1.5: exp(-(i - 5)^2 / (2 sigma^2)) over its sum), applied separably, first along H then
+ *              along W, no padding, each a sum of g[k] * value over ascending k.  Per level and channel with C1 = 0.01 * 0.01, C2 = 0.03 * 0.03:
+ *                mu1 = G(X), mu2 = G(Y);  s1 = G(X X) - mu1 mu1, s2 = G(Y Y) - mu2 mu2, s12 = G(X Y) - mu1 mu2;
+ *                cs = (2 s12 + C2) / (s1 + s2 + C2);  ssim = ((2 mu1 mu2 + C1) / (mu1 mu1 + mu2 mu2 + C1)) * cs.
+ *              Five levels, weights 0.0448 0.2856 0.3001 0.2363 0.1333; levels 0-3 contribute relu(mean(cs)), level 4 relu(mean(ssim)); between levels both
+ *              pictures pass a 2 x 2 average pool of stride 2, padded by size % 2 at the low end of each axis, the padding zeros counted (every window is
+ *              divided by 4, avg_pool2d's count_include_pad=True).  The score is the mean over the channels of the product of value ^ weight.  The smaller
+ *              side must exceed 160 (the original asserts).  Sums over a map: a workgroup owns 16 x 32 values (p = 32 r + c, thread t adds p = t, t + 256) and
+ *              reduces as above; hive_similarity_finish then gives the mean.
+ * LPIPS (AlexNet weights) and MIFD (SIFT) are not restated.  Nothing synchronises; every call is ordered on the context's stream. */
+/* compare_images' SSIM and PSNR sums (compare_image_pair.py:120-124) for N pairs and `variants` (1: plain; 2: plain, then masked) at once.  H, W >= 7, N >= 1,
+ * variants * N <= 65535.  d_partials f64 [variants][N][ceil((H - 6) / 32) * ceil((W - 6) / 32)]: the tile sums of S, for hive_similarity_finish with the divisor
+ * (H - 6)(W - 6).  d_sse i64 [variants][N]: zeroed here, then the sum of squared gray differences.  Optional (NULL = not stored): d_map f64 [variants][N][H - 6][W - 6],
+ * d_gray_ref u8 [variants][N][H][W], d_gray_est u8 [N][H][W]. */
+int hive_similarity_ssim_psnr(hive_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_est, int N, int H, int W, int rgb_order, int variants, double *d_partials,
+                              int64_t *d_sse, double *d_map, uint8_t *d_gray_ref, uint8_t *d_gray_est);
+/* One level of ms_ssim (experiments.py:1630-1635).  Input, exactly one of: the pictures d_ref_u8 / d_est_u8 u8 [N][h][w][3] (level 0), or the planes d_x f64
+ * [variants][N][3][h][w] and d_y f64 [N][3][h][w] a previous level left.  h, w >= 11.  window: host f64 [11].  d_partials f64 [2][variants * N * 3][T] with
+ * T = ceil((h - 10) / 16) * ceil((w - 10) / 32): tile sums of the cs map, then of the ssim map, rows in (variant, picture, channel) order, for
+ * hive_similarity_finish with the divisor (h - 10)(w - 10).  d_x_next f64 [variants][N][3][h2][w2] and d_y_next f64 [N][3][h2][w2], h2 = (h + 1) / 2, w2 = (w + 1) / 2:
+ * the pooled planes of the next level (both NULL after the last level).  variants * N * 3 <= 65535. */
+int hive_similarity_msssim_level(hive_ctx *ctx, const uint8_t *d_ref_u8, const uint8_t *d_est_u8, const double *d_x, const double *d_y, int N, int h, int w,
+                                 int variants, const double window[11], double *d_partials, double *d_x_next, double *d_y_next);
+/* d_out[r] = (the sum of d_partials[r][0 .. per_row), in the fixed order above) / divisor, for r < rows: a picture's score does not depend on the batch. */
+int hive_similarity_finish(hive_ctx *ctx, const double *d_partials, int64_t rows, int64_t per_row, double divisor, double *d_out);
+/* The product over the levels: d_means f64 [5][2][count][3] (level; cs mean, ssim mean; variant * N + picture; channel) as hive_similarity_finish left them ->
+ * d_out f64 [count] = mean over the channels of prod_l max(value_l, 0) ^ weight_l, value_l the cs mean for l < 4 and the ssim mean for l = 4. */
+int hive_similarity_msssim_combine(hive_ctx *ctx, const double *d_means, int64_t count, double *d_out);
 
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
