@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 3
+#define HIVE_ABI_VERSION 4
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -504,7 +504,7 @@ int hive_render_resolve(hive_ctx *ctx, const uint64_t *d_key, int H, int W, cons
  *              divided by 4, avg_pool2d's count_include_pad=True).  The score is the mean over the channels of the product of value ^ weight.  The smaller
  *              side must exceed 160 (the original asserts).  Sums over a map: a workgroup owns 16 x 32 values (p = 32 r + c, thread t adds p = t, t + 256) and
  *              reduces as above; hive_similarity_finish then gives the mean.
- * LPIPS (AlexNet weights) and MIFD (SIFT) are not restated.  Nothing synchronises; every call is ordered on the context's stream. */
+ * LPIPS is restated below, above hive_lpips_create; MIFD (SIFT) is not restated.  Nothing synchronises; every call is ordered on the context's stream. */
 /* compare_images' SSIM and PSNR sums (compare_image_pair.py:120-124) for N pairs and `variants` (1: plain; 2: plain, then masked) at once.  H, W >= 7, N >= 1,
  * variants * N <= 65535.  d_partials f64 [variants][N][ceil((H - 6) / 32) * ceil((W - 6) / 32)]: the tile sums of S, for hive_similarity_finish with the divisor
  * (H - 6)(W - 6).  d_sse i64 [variants][N]: zeroed here, then the sum of squared gray differences.  Optional (NULL = not stored): d_map f64 [variants][N][H - 6][W - 6],
@@ -523,6 +523,48 @@ int hive_similarity_finish(hive_ctx *ctx, const double *d_partials, int64_t rows
 /* The product over the levels: d_means f64 [5][2][count][3] (level; cs mean, ssim mean; variant * N + picture; channel) as hive_similarity_finish left them ->
  * d_out f64 [count] = mean over the channels of prod_l max(value_l, 0) ^ weight_l, value_l the cs mean for l < 4 and the ssim mean for l = 4. */
 int hive_similarity_msssim_combine(hive_ctx *ctx, const double *d_means, int64_t count, double *d_out);
+
+/* ---- LPIPS: the third score of a render -- lpips.LPIPS(net='alex') as scripts/compare_image_pair.py:29-41 feeds it and :110-133 returns it; the loops and tables
+ * that use it are scripts/experiments.py:663-684, :844-852 (plain and masked), :1384-1426 and scripts/compare_image_pairs.py:40-84.  The lpips package and
+ * torchvision are absent, so the network is restated from its published definition (lpips 0.1, eval mode, version 0.1 linear layers over torchvision's AlexNet
+ * features) and the numbers are not pinned against lpips / torchvision.  tests/lpips_restatement.py states the same rules in torch-CPU and numpy.  The rules (no
+ * fused multiply-add outside the MFMA's own chain):
+ *   input      u8 [N][H][W][3]; channel k of the picture is channel k of the network (no reordering: the reference hands LPIPS whatever order its pictures are
+ *              in).  The value of a byte v is ((v / 255) * 2.0 - 1.0) in float64, rounded to float32 (compare_image_pair.py:30-33); the scaling layer then
+ *              gives (x - shift[k]) / scale[k] in float32, shift = (-.030, -.088, -.188), scale = (.458, .448, .450).  The host builds this 3 x 256 float32
+ *              table once with exactly these operations and the kernel looks values up.
+ *   mask       variant 1 (`variants` = 2) is experiments.py:846-848 as for hive_similarity_ssim_psnr: per CHANNEL, a reference byte reads as 255 where the
+ *              estimate's byte of the same pixel and channel is 255; applied while loading, the whitened frame is never written.
+ *   features   the five ReLU maps, float32 [pictures][h][w][C] (channels last), each a convolution with bias, then ReLU:
+ *                0: conv 3 -> 64, 11 x 11, stride 4, pad 2;   1: maxpool 3 / 2, conv 64 -> 192, 5 x 5, pad 2;   2: maxpool 3 / 2, conv 192 -> 384, 3 x 3, pad 1;
+ *                3: conv 384 -> 256, 3 x 3, pad 1;   4: conv 256 -> 256, 3 x 3, pad 1.   The maxpool is floor mode without padding: (h - 3) / 2 + 1.
+ *              Inputs, weights, accumulation and outputs are float32.  A value is the chain acc = fma(x_k, w_k, acc) from 0.0f over k = (ky, kx, ci) ascending
+ *              (__builtin_amdgcn_mfma_f32_32x32x2f32; padding and the tail of K add fma(0, 0, acc)), then acc + bias, then max with 0.  Its bits depend on the
+ *              receptive field and the weights alone: not on the picture's place in the batch, on N, or on the slot (reference / estimate).  There is no
+ *              split-K and no floating-point atomic.  Against exact arithmetic |error| <= gamma_K (sum |w| |x| + |b|), gamma_K = K u / (1 - K u), u = 2^-24, K the
+ *              layer's products plus the bias: 364, 1601, 1729, 3457, 2305.
+ *   tail       not pinned against lpips: the package does this in float32; here, per layer and pixel, from the float32 vectors a (reference) and b (estimate) of
+ *              C channels, in float64, every sum over c ascending, added left to right to 0.0:
+ *                na = sqrt(sum a_c a_c) + 1e-10, nb likewise;   t_c = a_c / na - b_c / nb;   d = sum w_c * (t_c * t_c),   w the layer's 1 x 1 linear weights.
+ *   sums       a workgroup owns 256 consecutive pixels p of one picture's map (thread t holds d(p), 0.0 past the end), the tree v[t] += v[t + off], off = 128 ..
+ *              1, gives its partial; hive_similarity_finish adds a picture's partials and divides by h w: the layer's score.  The LPIPS of a pair is
+ *              l0 + l1 + l2 + l3 + l4, added left to right.  The same bits on every run and in every batch.
+ * Nothing synchronises; every call is ordered on the context's stream (the workspace grows, with a synchronisation, when a call needs more than any before). */
+typedef struct hive_lpips hive_lpips;
+/* lpips.LPIPS(net='alex') from host float32 weights in torch's shapes: conv_w[l] OIHW [C_out][C_in][k][k], conv_b[l] [C_out], lin_w[l] [C_out] (the 1 x 1 linear
+ * layer lin{l}.model.1.weight, [1][C][1][1]) for the five rows above.  Repacks the weights on the device and builds the input table. */
+int hive_lpips_create(hive_ctx *ctx, const float *const conv_w[5], const float *const conv_b[5], const float *const lin_w[5], hive_lpips **out);
+/* Frees the model and its workspace (after the stream has drained). */
+int hive_lpips_destroy(hive_lpips *net);
+/* One row of the feature table of the network compare_image_pair.py:29-41 runs: d_in f32 [N][h][w][C_in], the previous row's ReLU map, un-pooled (layer 0: the scaled picture, [N][H][W][3]) -> d_out f32
+ * [N][ho][wo][C_out].  Both 16-byte aligned.  hive_lpips_forward runs the same launchers. */
+int hive_lpips_layer(hive_lpips *net, int layer, const float *d_in, int N, int h, int w, float *d_out);
+/* The LPIPS of N pairs (compare_image_pair.py:29-41; experiments.py:844-848 with variants = 2: plain, then masked).  H, W >= 31: the smallest picture with an
+ * output in every layer (7, 3, 1, 1, 1).  d_scores f64 [variants][N].  Optional (NULL = not stored): d_layer_scores f64 [5][variants][N]; d_features[l] f32
+ * [variants + 1][N][h_l][w_l][C_l], the features of the reference, of the masked reference when asked, then of the estimate (computed once for both variants);
+ * d_dist[l] f64 [variants][N][h_l][w_l], the maps d.  Any N: the pairs are run in chunks over one workspace. */
+int hive_lpips_forward(hive_lpips *net, const uint8_t *d_ref_u8, const uint8_t *d_est_u8, int N, int H, int W, int variants, double *d_scores,
+                       double *d_layer_scores, float *const d_features[5], double *const d_dist[5]);
 
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
