@@ -18,7 +18,7 @@ OK, ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_EMPTY, ERR_STATE = 0, -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
 ROUND_HALF_EVEN, ROUND_HALF_AWAY = 0, 1
 F32, F16, BF16 = 0, 1, 2
-ABI_VERSION = 4  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*
+ABI_VERSION = 5  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments)
 
 c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 P = ctypes.POINTER
@@ -69,6 +69,12 @@ SIGNATURES = {
     "hive_tsdf_accum_from_volume": (c_int, [c_void_p, c_void_p]),
     "hive_tsdf_accum_from_volume_sharded": (c_int, [c_void_p, c_void_p, c_int, c_int64]),
     "hive_tsdf_set_volume_range": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "hive_tsdf_mark_segments": (c_int, [c_void_p, c_int, c_void_p]),
+    "hive_mark_segments": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "hive_segment_list": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "hive_tsdf_accum_from_volume_segments": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p]),
+    "hive_accum_pack_segments": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p]),
+    "hive_tsdf_set_volume_segments": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p]),
     "hive_view_frustum": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "hive_view_frustum_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "hive_depth_apply_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

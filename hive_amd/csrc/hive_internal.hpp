@@ -239,7 +239,7 @@ struct hive_tsdf {
     std::vector<int> last_groups;
     // true while every weight of the volume is a whole number of unit observations: set by create / reset, kept by integrate calls with
     // obs_weight == 1 (at most 65533 frames: unit_frames), cleared by anything else that writes the planes (other observation weights,
-    // set_volume / set_volume_range / accum_finalize, hive_tsdf_planes_modified).  Selects the division-free colour update (tsdf.hip).
+    // set_volume / set_volume_range / set_volume_segments / accum_finalize, hive_tsdf_planes_modified).  Selects the division-free colour update (tsdf.hip).
     bool unit_weights = true;
     int64_t unit_frames = 0;
     // frames handed to the integrate entry points / integrate launches since creation or the last reset (hive_tsdf_stats)
@@ -266,4 +266,15 @@ template <int RM>
 __device__ __forceinline__ float hive_round(float x) {
     if (RM == 0) return rintf(x);
     return roundf(x);
+}
+
+// One voxel of a running-average volume (tsdf t, weight w, packed colour c) -> its five sums [t * w, w, r * w, g * w, b * w] at o[0], o[plane], ... o[4 * plane]:
+// what a rank contributes to the merge.  ONE statement of these products for every layout the sums are written in (tsdf.hip, merge.hip): the dense and the
+// sparse merge are bit-identical only as long as they share it.
+__device__ __forceinline__ void hive_voxel_sums(float t, float w, unsigned c, float *__restrict__ o, long long plane) {
+    o[0] = t * w;  // w == 0 (never observed): tsdf is 1, the sum is 0
+    o[plane] = w;
+    o[2 * plane] = (float)(c & 255u) * w;
+    o[3 * plane] = (float)((c >> 8) & 255u) * w;
+    o[4 * plane] = (float)(c >> 16) * w;
 }

@@ -1121,11 +1121,7 @@ __global__ __launch_bounds__(256) void to_accum_sharded_kernel(const float *__re
             t = tsdf[i];
             c = (unsigned)color[i];
         }
-        o[0] = t * w;
-        o[chunk] = w;
-        o[2 * chunk] = (float)(c & 255u) * w;
-        o[3 * chunk] = (float)((c >> 8) & 255u) * w;
-        o[4 * chunk] = (float)(c >> 16) * w;
+        hive_voxel_sums(t, w, c, o, chunk);
     }
 }
 

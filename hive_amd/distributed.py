@@ -19,6 +19,17 @@ sums are cut at tile boundaries counted from the start of the batch.  Frame-shar
 therefore integrate depth maps that differ from the one-GPU run's within the network's stated tolerance (median < 1 mm in float16, < 9 mm in
 bfloat16: tools/diag_splitk_bound.py) before the merge's own tolerance applies.  ``Context.set_deterministic(True)`` (hive_ctx_set_deterministic)
 removes the two threshold effects; the tile-boundary effect (~1e-7 relative in (mean, rstd)) remains unless the batch composition is kept.
+
+Sparse merge (``fuse_sharded(..., merge="sparse")``, opt-in): most of a scene's grid was never observed, and an unobserved voxel adds five exact zeros to the
+sums and comes back as the initial value it already has.  The volume is cut into SEGMENTS of ``segment`` consecutive voxels (linear C-order index, z fastest);
+a segment is inactive on a rank iff every weight word in it has the bit pattern of +0.0f; the ranks unite their active sets (one MAX all-reduce of one byte per
+segment) and only the united segments go through the reduce-scatter and the all-gather.  Contract: a voxel of weight +0.0f holds the initial values (tsdf 1,
+colour 0) -- true of every volume the integrate kernels produce, and what the fold writes for w == 0 -- so an inactive segment left untouched equals what the dense
+merge writes there.  Parity: per voxel the sparse merge adds the same float32 values over the same ranks as the dense one.  With one or two ranks a sum has one
+order, and the result is BIT FOR BIT the dense merge's (tsdf, weight and colour planes, on every rank).  With more ranks the collective's summation order may depend
+on a value's position in the buffer; the statement is then the dense merge's own, against the sequential fusion of the same depth maps: tsdf <= 1e-5, weights exact,
+colours +-2.  ``merge_plan`` is the cost model that picks the mode for ``merge="auto"``: COMPUTED from link and HBM rates, not measured -- no link has been timed on
+any multi-GPU node.
 """
 import os
 
@@ -162,7 +173,103 @@ def all_gather_pieces(mine, part):
     return out
 
 
-def fuse_sharded(volume, stream_or_accum=None):
+MERGE_MODES = ("dense", "sparse", "auto")
+# Voxels per segment of the sparse merge.  64, not VoxelPartition's 256: on the benchmark's scene 43.7 % of the 64-voxel segments are active against 52.4 % of the
+# 256-voxel ones (35.7 % of the voxels carry a weight), on a foreground volume 34.7 % against 41.6 % -- a sixth fewer bytes through both collectives -- and the local
+# passes are no slower (1.24 against 1.40 ms at 512^3; profiles/sparse_merge_probe.json).  The flags grow to 2 MiB at 512^3.
+DEFAULT_SEGMENT = 64
+# The rates of the merge's cost model (merge_plan).  They are the figures the design documents already use, NOT measurements of this code on a multi-GPU node:
+XGMI_LINKS, XGMI_LINK_GBS = 7, 153.0  # direct links per GPU and GB/s per link and direction ("7 links x ~153 GB/s per GPU")
+HBM_PEAK_GBS = 8000.0                 # HBM3E peak ("Peaks: HBM 8 TB/s spec")
+SPARSE_SYNC_MS = 0.05                 # assumed cost of the sparse merge's one host read-back (the segment count): a stream drain and an 8-byte copy
+
+
+def _check_merge_args(merge, segment):
+    if merge not in MERGE_MODES:
+        raise ValueError(f"merge must be one of {MERGE_MODES}, got {merge!r}")
+    if isinstance(segment, bool) or not isinstance(segment, int) or not 64 <= segment <= 4096 or segment & (segment - 1):
+        raise ValueError(f"segment must be a power of two in 64 .. 4096, got {segment!r}")
+
+
+def merge_plan(n_voxels, active_voxels, world, *, segment=DEFAULT_SEGMENT, link_gbs=XGMI_LINKS * XGMI_LINK_GBS, hbm_gbs=HBM_PEAK_GBS):
+    """Bytes per GPU and predicted milliseconds of the dense and the sparse merge of an ``n_voxels`` volume of which ``active_voxels`` lie in active segments
+    (A = ceil(active_voxels / segment) of S = ceil(n_voxels / segment)), over ``world`` ranks, and the mode that is predicted to be faster.  A pure function.
+
+    Bytes over the links, per GPU: dense (5 + 3) * 4 * N * (W - 1) / W; sparse (5 + 3) * 4 * A * L * (W - 1) / W + S (the flags).  Time = those bytes over
+    ``link_gbs`` (all of a GPU's links together: the direct reduce-scatter / all-gather spreads its W - 1 transfers over them) plus the local passes' HBM traffic
+    over ``hbm_gbs`` (dense: sums 3 + 5, fold (5 + 3) / W, copy back 3 + 3 floats per voxel; sparse: the same per ACTIVE voxel, plus one read of the weight plane,
+    the flags and the list) plus, for sparse, ``SPARSE_SYNC_MS``.  The model is COMPUTED from those rates: no link time has been measured on any multi-GPU node, and the
+    local passes run below the HBM peak (their measured times on one GPU: profiles/sparse_merge_probe.json).  Both errors scale the two modes alike; what decides
+    the choice is the active fraction."""
+    _check_merge_args("auto", segment)
+    n, w, seg = int(n_voxels), int(world), int(segment)
+    if n <= 0 or w <= 0 or not 0 <= int(active_voxels) <= n:
+        raise ValueError(f"merge_plan: {n_voxels} voxels, {active_voxels} active, world {world}")
+    n_segments, n_active = -(-n // seg), -(-int(active_voxels) // seg)
+    share = (w - 1) / w
+    packed = n_active * seg
+    plan = {"segment": seg, "segments": n_segments, "active": n_active, "world": w,
+            "bytes_dense": (5 + 3) * 4 * n * share, "bytes_sparse": (5 + 3) * 4 * packed * share + n_segments}
+    local_dense = 4 * n * ((3 + 5) + (5 + 3) / w + (3 + 3))
+    local_sparse = 4 * packed * ((3 + 5) + (5 + 3) / w + (3 + 3)) + 4 * n + 2 * n_segments + 4 * n_active
+    plan["ms_dense"] = plan["bytes_dense"] / (link_gbs * 1e6) + local_dense / (hbm_gbs * 1e6)
+    plan["ms_sparse"] = plan["bytes_sparse"] / (link_gbs * 1e6) + local_sparse / (hbm_gbs * 1e6) + SPARSE_SYNC_MS
+    plan["mode"] = "sparse" if plan["ms_sparse"] < plan["ms_dense"] else "dense"
+    return plan
+
+
+def segment_flags(weight, segment):
+    """weight float32 [N] -> uint8 [S]: 1 where segment s = [s * L, min((s + 1) * L, N)) holds a word whose BITS are not those of +0.0f (a -0.0f is active).  The
+    generic (torch) form of ``hive_tsdf_mark_segments``; serves CPU tensors under gloo, and the GPU tests compare the kernel with it."""
+    n = weight.numel()
+    n_segments = -(-n // segment)
+    bits = torch.zeros(n_segments * segment, dtype=torch.int32, device=weight.device)
+    bits[:n] = weight.reshape(-1).view(torch.int32)
+    return (bits.view(n_segments, segment) != 0).any(dim=1).to(torch.uint8)
+
+
+def _segment_voxels(seg_list, segment, n):
+    """Voxel indices [A * L] behind the listed segments, and which of them exist (the last segment may reach past N)."""
+    idx = (seg_list.to(torch.int64)[:, None] * segment + torch.arange(segment, device=seg_list.device)[None, :]).reshape(-1)
+    return idx, idx < n
+
+
+def pack_segments(planes, seg_list, segment, world):
+    """planes [P, N], seg_list [A] (ascending segment indices) -> [world, P, per * L] with per = ceil(A / world): list entry k in piece k // per at floats
+    [(k % per) * L, (k % per + 1) * L); zeros past A and past N.  The generic (torch) form of ``hive_tsdf_accum_from_volume_segments`` /
+    ``hive_accum_pack_segments``, stated by index list."""
+    p, n = planes.shape
+    a = seg_list.numel()
+    per = -(-a // world)
+    idx, ok = _segment_voxels(seg_list, segment, n)
+    slots = torch.zeros((p, world * per * segment), dtype=planes.dtype, device=planes.device)
+    slots[:, torch.nonzero(ok).reshape(-1)] = planes[:, idx[ok]]
+    return slots.view(p, world, per * segment).permute(1, 0, 2).contiguous()
+
+
+def unpack_segments(pieces, seg_list, segment, planes):
+    """The way back: pieces [world, P, per * L] -> the listed segments' voxels of planes [P, N], in place; no other voxel is touched.  The generic (torch) form
+    of ``hive_tsdf_set_volume_segments``."""
+    world, p, _ = pieces.shape
+    idx, ok = _segment_voxels(seg_list, segment, planes.shape[1])
+    slots = pieces.permute(1, 0, 2).reshape(p, -1)
+    planes[:, idx[ok]] = slots[:, torch.nonzero(ok).reshape(-1)]
+    return planes
+
+
+def unite_segment_flags(flags):
+    """Every rank's flags -> their union on every rank, in place: ONE MAX all-reduce of one byte per segment (host-staged under gloo)."""
+    if _collective():
+        if _host_staged() and flags.is_cuda:
+            host = flags.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.MAX)
+            flags.copy_(host)
+        else:
+            dist.all_reduce(flags, op=dist.ReduceOp.MAX)
+    return flags
+
+
+def fuse_sharded(volume, stream_or_accum=None, *, merge="dense", segment=DEFAULT_SEGMENT):
     """Merge the per-rank fusions into the shared static-scene volume, on every rank, with TWO collectives:
     ONE reduce-scatter of the 5 accumulator planes (piece-major ``[world][5][chunk]``) -> every rank folds ITS 1 / W of the
     voxels (`accum_finalize_range`) -> ONE all-gather of the 3 result planes (``[world][3][chunk]``) -> the pieces are copied into
@@ -176,23 +283,43 @@ def fuse_sharded(volume, stream_or_accum=None):
     ``integrate`` (same kernel and cost as on one GPU); its volumes are converted to the sums
     ``[tsdf * w, w, r * w, g * w, b * w]`` straight into the piece-major buffer.  Otherwise: the accumulators of a
     ``DepthFusionStream(accumulate=True)`` or a raw accumulator tensor filled with ``accum_integrate`` (sums of the raw
-    observations, 40 B / voxel / frame)."""
+    observations, 40 B / voxel / frame).
+
+    ``merge``: ``"dense"`` (default) sends every voxel; ``"sparse"`` only the segments of ``segment`` consecutive voxels that some rank observed (module
+    docstring: the contract on unobserved voxels, and the parity -- bit for bit the dense merge's with one or two ranks): mark -> MAX all-reduce of the flags ->
+    segment list (its count is the one host read-back) -> pack -> ONE reduce-scatter -> fold -> ONE all-gather -> scatter; ``"auto"`` marks and unites, then takes
+    the mode ``merge_plan`` predicts to be faster.  With raw accumulators the volume must still hold its initial values where nothing was observed.  Afterwards
+    ``volume.merge_stats`` = {mode, segment, segments, active (None when the dense path never counted), bytes_reduce_scatter, bytes_all_gather (the buffers
+    this rank put through the two collectives), bytes_flags}.  ValueError for an unknown mode or a bad ``segment``, before any collective."""
+    _check_merge_args(merge, segment)
     # a volume whose context does not follow torch's current stream (the side stream of an overlapping DepthFusionStream, Context(stream="own"), an
     # explicit hipStream_t) has its kernels on THAT stream: the collectives and the torch buffers go there too, in order with them
     side = volume._ctx.torch_stream()
     if side is not None:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            _fuse_sharded(volume, stream_or_accum)
+            _fuse_sharded(volume, stream_or_accum, merge, segment)
         torch.cuda.current_stream().wait_stream(side)
         return volume
-    return _fuse_sharded(volume, stream_or_accum)
+    return _fuse_sharded(volume, stream_or_accum, merge, segment)
 
 
-def _fuse_sharded(volume, stream_or_accum):
+def _fuse_sharded(volume, stream_or_accum, merge, segment):
     n = volume.num_voxels
-    part = VoxelPartition(n)
     accum = getattr(stream_or_accum, "accum", stream_or_accum)
+    stats = {"mode": "dense", "segment": segment, "segments": -(-n // segment), "active": None, "bytes_flags": 0}
+    volume.merge_stats = stats
+    if merge != "dense":
+        from hive_amd import fusion
+        ctx = volume._ctx
+        flags = volume.mark_segments(segment) if accum is None else fusion.mark_segments(accum.view(5, n)[1], segment, ctx=ctx)
+        seg_list, n_active = fusion.segment_list(unite_segment_flags(flags), ctx=ctx)
+        stats.update(active=n_active, bytes_flags=flags.numel())
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        if merge == "sparse" or merge_plan(n, min(n, n_active * segment), world, segment=segment)["mode"] == "sparse":
+            return _fuse_sparse(volume, accum, seg_list, n_active, segment, stats)
+    part = VoxelPartition(n)
+    stats.update(bytes_reduce_scatter=4 * 5 * part.padded, bytes_all_gather=4 * 3 * part.padded)
     if accum is None:
         pieces = torch.empty((part.world, 5, part.chunk), dtype=torch.float32, device="cuda")
         volume.accum_from_volume_sharded(pieces, part.world, part.chunk)
@@ -206,6 +333,29 @@ def _fuse_sharded(volume, stream_or_accum):
     gathered = all_gather_pieces(share, part)  # [world, 3, chunk]
     for r in range(part.world):
         volume.set_volume_range(r * part.chunk, part.count_of(r), tsdf=gathered[r, 0], weight=gathered[r, 1], color=gathered[r, 2])
+    return volume
+
+
+def _fuse_sparse(volume, accum, seg_list, n_active, segment, stats):
+    """The dense merge's steps over the ``n_active`` united segments alone: a partition of n_active * L packed voxels in whole segments."""
+    from hive_amd import fusion
+    part = VoxelPartition(n_active * segment, align=segment)  # chunk = ceil(n_active / world) * L
+    per = part.chunk // segment
+    stats.update(mode="sparse", bytes_reduce_scatter=4 * 5 * part.padded, bytes_all_gather=4 * 3 * part.padded)
+    if n_active == 0:  # nothing observed on any rank (every rank sees the same count): the volume already is the merge
+        return volume
+    pieces = torch.empty((part.world, 5, part.chunk), dtype=torch.float32, device="cuda")
+    if accum is None:
+        volume.accum_from_volume_segments(pieces, seg_list, n_active, segment, part.world, per)
+    else:
+        fusion.accum_pack_segments(accum, pieces, seg_list, n_active, segment, part.world, per, ctx=volume._ctx)
+    mine = reduce_scatter_pieces(pieces, part)  # [5, per * L]
+    del pieces
+    share = torch.zeros((3, part.chunk), dtype=torch.float32, device="cuda")  # tsdf, weight, colour of this rank's segments
+    volume.accum_finalize_range(mine, part.chunk, part.count, [share[0], share[1], share[2]])
+    del mine
+    gathered = all_gather_pieces(share, part)  # [world, 3, per * L]
+    volume.set_volume_segments(gathered, seg_list, n_active, segment, part.world, per)
     return volume
 
 
@@ -224,14 +374,15 @@ def allreduce_bounds(vol_bnds):
     return np.stack([lo.cpu().numpy(), hi.cpu().numpy()], axis=1)
 
 
-def tsdf_fusion_fg_bg_sharded(dataset, options=None, num_frames=-1, frame_set=None, instance_id=0, chunk_frames=None):
+def tsdf_fusion_fg_bg_sharded(dataset, options=None, num_frames=-1, frame_set=None, instance_id=0, chunk_frames=None, merge="dense", segment=DEFAULT_SEGMENT):
     """BASELINE config 5's multi-GPU form: the dynamic path (background volume = depth with the dilated instance masks zeroed, foreground volume
     = the complement; ``hive_amd.fusion.tsdf_fusion_fg_bg``) with the frames sharded over the ranks.  Every rank decodes and fuses ITS contiguous
     block of the frame set into its own pair of volumes -- on the grid of the whole set: the ranks' scene bounds are all-reduced (min / max, exact)
     before the volumes are created -- and each of the two volumes is merged once with ``fuse_sharded`` (reduce-scatter of its sums, all-gather of
     the result).  Returns {"bg": TSDFVolume, "fg": TSDFVolume}, the merged volumes, on every rank.  Parity with one GPU: as ``fuse_sharded``
     (tsdf <= 1e-5, weights exact, colours +-2) -- for the dataset's OWN depth maps, which this driver reads from disk; depth maps estimated per rank by
-    the DPT network carry the batch-size caveat of this module's docstring on top."""
+    the DPT network carry the batch-size caveat of this module's docstring on top.  ``merge`` / ``segment``: the mode of both ``fuse_sharded`` calls."""
+    _check_merge_args(merge, segment)
     import numpy as np
     from hive_amd import fusion
     from hive_amd.options import BackgroundMeshOptions
@@ -248,7 +399,7 @@ def tsdf_fusion_fg_bg_sharded(dataset, options=None, num_frames=-1, frame_set=No
     vol_bnds = allreduce_bounds(local)
     volumes = fusion.tsdf_fusion_fg_bg(dataset, options, frame_set=mine, instance_id=instance_id, chunk_frames=chunk_frames, vol_bnds=vol_bnds)
     for vol in volumes.values():
-        fuse_sharded(vol)
+        fuse_sharded(vol, merge=merge, segment=segment)
     return volumes
 
 

@@ -278,6 +278,27 @@ class TSDFVolume:
             assert a is None or (a.numel() >= count and str(a.dtype) == "torch.float32" and a.is_contiguous())
         self._ctx.check(self._ctx.lib.hive_tsdf_set_volume_range(self._handle, int(first), int(count), ptr(tsdf), ptr(weight), ptr(color)))
 
+    # -- the sparse merge's passes (segments of L consecutive voxels: include/hive_mi355x.h, hive_amd.distributed.fuse_sharded) --
+    def mark_segments(self, segment):
+        """uint8 device tensor [ceil(N / segment)]: 1 where the segment holds a weight word whose bits are not those of +0.0f."""
+        import torch
+        self._ctx.follow_torch_stream()
+        flags = torch.empty(-(-self.num_voxels // int(segment)), dtype=torch.uint8, device=f"cuda:{self._ctx.device}")
+        self._ctx.check(self._ctx.lib.hive_tsdf_mark_segments(self._handle, int(segment), ptr(flags)))
+        return flags
+
+    def accum_from_volume_segments(self, out, seg_list, n_active, segment, world, per):
+        """The five sums of the ``n_active`` listed segments as float32 [world][5][per * segment]: the input of ONE reduce-scatter."""
+        self._ctx.follow_torch_stream()
+        _check_segment_buffers(out, seg_list, n_active, segment, world, per, 5)
+        self._ctx.check(self._ctx.lib.hive_tsdf_accum_from_volume_segments(self._handle, ptr(seg_list), int(n_active), int(segment), int(world), int(per), ptr(out)))
+
+    def set_volume_segments(self, pieces, seg_list, n_active, segment, world, per):
+        """Write float32 [world][3][per * segment] (tsdf, weight, colour: the all-gathered shares) into the listed segments' voxels."""
+        self._ctx.follow_torch_stream()
+        _check_segment_buffers(pieces, seg_list, n_active, segment, world, per, 3)
+        self._ctx.check(self._ctx.lib.hive_tsdf_set_volume_segments(self._handle, ptr(seg_list), int(n_active), int(segment), int(world), int(per), ptr(pieces)))
+
     def accum_finalize(self, accum):
         self._ctx.check(self._ctx.lib.hive_tsdf_accum_finalize(self._handle, ptr(accum)))
 
@@ -298,6 +319,42 @@ class TSDFVolume:
             self.close()
         except Exception:
             pass
+
+
+def _check_segment_buffers(buf, seg_list, n_active, segment, world, per, planes):
+    """The library cannot see the sizes of device buffers: refuse the ones its segment kernels would overrun."""
+    assert str(buf.dtype) == "torch.float32" and buf.is_contiguous() and buf.numel() >= int(world) * planes * int(per) * int(segment)
+    assert str(seg_list.dtype) == "torch.int32" and seg_list.is_contiguous() and seg_list.numel() >= int(n_active)
+
+
+def mark_segments(weight, segment, ctx=None):
+    """``TSDFVolume.mark_segments`` for a bare float32 device weight plane (plane 1 of raw accumulator planes): uint8 flags [ceil(N / segment)]."""
+    import torch
+    ctx = (ctx or _lib.default_context()).follow_torch_stream()
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.is_cuda
+    flags = torch.empty(-(-weight.numel() // int(segment)), dtype=torch.uint8, device=weight.device)
+    ctx.check(ctx.lib.hive_mark_segments(ctx.handle, ptr(weight), weight.numel(), int(segment), ptr(flags)))
+    return flags
+
+
+def segment_list(flags, ctx=None):
+    """(int32 device tensor [S] whose first A entries are the indices of the non-zero ``flags``, ascending; A).  Reading A back is one 8-byte copy, and
+    the only synchronisation of the sparse merge."""
+    import torch
+    ctx = (ctx or _lib.default_context()).follow_torch_stream()
+    assert flags.dtype == torch.uint8 and flags.is_contiguous() and flags.is_cuda
+    seg_list = torch.empty(flags.numel(), dtype=torch.int32, device=flags.device)
+    count = torch.empty(1, dtype=torch.int64, device=flags.device)
+    ctx.check(ctx.lib.hive_segment_list(ctx.handle, ptr(flags), flags.numel(), ptr(seg_list), ptr(count)))
+    return seg_list, int(count.item())
+
+
+def accum_pack_segments(accum, out, seg_list, n_active, segment, world, per, ctx=None):
+    """``TSDFVolume.accum_from_volume_segments`` for raw accumulator planes [5][N] (a plain gather of the listed segments)."""
+    ctx = (ctx or _lib.default_context()).follow_torch_stream()
+    assert str(accum.dtype) == "torch.float32" and accum.is_contiguous() and accum.numel() % 5 == 0
+    _check_segment_buffers(out, seg_list, n_active, segment, world, per, 5)
+    ctx.check(ctx.lib.hive_accum_pack_segments(ctx.handle, ptr(accum), accum.numel() // 5, ptr(seg_list), int(n_active), int(segment), int(world), int(per), ptr(out)))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 4
+#define HIVE_ABI_VERSION 5
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -203,6 +203,36 @@ int hive_tsdf_accum_finalize(hive_tsdf *vol, const float *d_accum);
  * planes; the three result arrays are then all-gathered (hive_amd.distributed.fuse_sharded). */
 int hive_tsdf_accum_finalize_to(hive_tsdf *vol, const float *d_accum, int64_t plane_stride, int64_t count, float *d_tsdf,
                                 float *d_weight, float *d_color);
+
+/* ---- Sparse merge: only the observed voxel SEGMENTS go through the collectives (hive_amd.distributed.fuse_sharded(merge="sparse")) ------
+ * A segment is a run of L consecutive voxels of the linear C-order index (z fastest): segment s = [s * L, min((s + 1) * L, N)),
+ * S = ceil(N / L) segments; L is a power of two in 64 .. 4096.  A segment is INACTIVE iff every weight word in it has the bit pattern of
+ * +0.0f (the bits decide, not w == 0: a -0.0f is active and goes through the same arithmetic as in the dense merge); everything else is active.
+ * Contract: a voxel of weight +0.0f holds the initial values (tsdf 1, colour 0).  That is true of every volume the integrate kernels produce,
+ * and it is what hive_tsdf_accum_finalize_to writes for w == 0, so leaving an inactive segment untouched equals what the dense merge writes there.
+ * All arrays are device memory; every offset is 64-bit. */
+/* d_flags u8 [S]: 1 for an active segment, 0 for an inactive one.  Reads the weight plane once (4 N bytes); one byte store per segment. */
+int hive_tsdf_mark_segments(hive_tsdf *vol, int L, uint8_t *d_flags);
+/* The same for a bare weight plane of n floats: plane 1 of raw accumulator planes [5][n] (d_accum + n). */
+int hive_mark_segments(hive_ctx *ctx, const float *d_weight, int64_t n, int L, uint8_t *d_flags);
+/* d_list i32 [S] (room for every segment): the indices of the segments whose flag is non-zero, ascending, at [0, *d_count); the rest of d_list
+ * is not written.  d_count is ONE int64 in device memory: the caller's 8-byte copy of it to the host is the only synchronisation the sparse
+ * merge adds. */
+int hive_segment_list(hive_ctx *ctx, const uint8_t *d_flags, int64_t n_segments, int32_t *d_list, int64_t *d_count);
+/* The five sums [tsdf * w, w, r * w, g * w, b * w] (the expressions of hive_tsdf_accum_from_volume_sharded) of the n_active listed segments
+ * laid out for ONE reduce-scatter over `world` ranks: d_out is float [world][5][per * L] with per >= ceil(n_active / world); list entry k goes
+ * to piece k / per, floats [(k % per) * L, (k % per + 1) * L) of each of that piece's planes, so piece r holds the active segments
+ * [r * per, min((r + 1) * per, n_active)).  Everything past n_active, and the lanes past N in the volume's last segment, are written as
+ * zeros.  Rank r's reduce-scatter output is its [5][per * L] share: the input of hive_tsdf_accum_finalize_to with plane_stride = per * L and
+ * count = (its number of segments) * L.  n_active == 0 returns HIVE_OK without a launch. */
+int hive_tsdf_accum_from_volume_segments(hive_tsdf *vol, const int32_t *d_list, int64_t n_active, int L, int world, int64_t per, float *d_out);
+/* The same layout from raw accumulator planes d_accum [5][n] (hive_tsdf_accum_integrate): a plain gather of the 5 planes. */
+int hive_accum_pack_segments(hive_ctx *ctx, const float *d_accum, int64_t n, const int32_t *d_list, int64_t n_active, int L, int world, int64_t per,
+                             float *d_out);
+/* The way back: d_in is float [world][3][per * L] (tsdf, weight, colour: the all-gathered shares, laid out as above with 3 planes per
+ * piece); the n_active listed segments are written into the volume's planes, never past N, and no other voxel is touched.  Drops the cached
+ * mesh and the volume's unit-weight fast path, as hive_tsdf_set_volume_range does.  n_active == 0 returns HIVE_OK without a launch. */
+int hive_tsdf_set_volume_segments(hive_tsdf *vol, const int32_t *d_list, int64_t n_active, int L, int world, int64_t per, const float *d_in);
 
 /* ---- fusion.get_view_frustum(depth_im, cam_intr, cam_pose) -- hive/fusion.py:59 ------ */
 /* out: float64 row-major [3][5] (apex + 4 corners at max(depth)), world coordinates */
