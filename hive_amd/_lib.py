@@ -18,7 +18,7 @@ OK, ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_EMPTY, ERR_STATE = 0, -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
 ROUND_HALF_EVEN, ROUND_HALF_AWAY = 0, 1
 F32, F16, BF16 = 0, 1, 2
-ABI_VERSION = 5  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments)
+ABI_VERSION = 6  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step
 
 c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 P = ctypes.POINTER
@@ -109,6 +109,10 @@ SIGNATURES = {
     "hive_render_shade": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p]),
     "hive_render_resolve": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hive_tsdf_raycast": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hive_frame_maps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hive_icp_step": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,
+                              P(c_int64), c_void_p]),
     "hive_similarity_ssim_psnr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_similarity_msssim_level": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_similarity_finish": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p]),

@@ -246,6 +246,35 @@ class TSDFVolume:
             return verts, faces, norms, colors, vvox
         return verts, faces, norms, colors
 
+    def raycast(self, cam_intr, cam_pose, size, z_near=0.0, z_far=0.0, step=0.5, return_vertex=False, return_normal=False, return_color=False):
+        """The volume seen from a camera, straight from the planes (``hive_tsdf_raycast``; the rules are in include/hive_mi355x.h): a preview, a held-out
+        view, and what ``hive_amd.tracking`` aligns a live frame against.
+
+        :param cam_intr: The camera intrinsics matrix of shape (3, 3).
+        :param cam_pose: The camera pose (camera-to-world) of shape (4, 4), as ``integrate`` takes it.
+        :param size: ``(H, W)`` of the picture.
+        :param z_near, z_far: the range of camera z that is searched; ``z_far <= 0`` = unbounded.
+        :param step: the march step as a share of the truncation distance.
+        :return: float32 depth (H, W) in metres, 0 where no surface was found, as a device tensor; with the ``return_`` flags a tuple with the world-frame
+            surface points (H, W, 3), the unit normals pointing into free space (H, W, 3; zeros where invalid) and the uint8 colours (H, W, 3) behind it.
+        """
+        import torch
+        self._ctx.follow_torch_stream()
+        h, w = (int(v) for v in size)
+        if h <= 0 or w <= 0:
+            raise ValueError(f"empty size {h} x {w}")
+        dev = f"cuda:{self._ctx.device}"
+        K = np.ascontiguousarray(cam_intr, dtype=np.float32).reshape(3, 3)
+        pose = np.ascontiguousarray(cam_pose, dtype=np.float64).reshape(4, 4)
+        depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+        vertex = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if return_vertex else None
+        normal = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if return_normal else None
+        color = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if return_color else None
+        self._ctx.check(self._ctx.lib.hive_tsdf_raycast(self._handle, h, w, ptr(K), ptr(pose), float(z_near), float(z_far), float(step), ptr(depth), ptr(vertex),
+                                                        ptr(normal), ptr(color)))
+        extra = tuple(x for x in (vertex, normal, color) if x is not None)
+        return (depth, *extra) if extra else depth
+
     def get_point_cloud(self):
         """Extract a point cloud from the voxel volume: (V, 6) [x, y, z, r, g, b]."""
         verts, _, _, colors = self.get_mesh()

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 5
+#define HIVE_ABI_VERSION 6
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -498,6 +498,57 @@ int hive_render_shade(hive_ctx *ctx, int64_t nv, const int32_t *d_faces, int64_t
  * background[3] (NULL = white); d_depth f32 [H][W] (may be NULL) the winner's depth, 0 where empty; d_face i32 [H][W] (may be NULL) its global face index, -1
  * where empty (an index of 2^31 or more does not fit: keep the total below 2^31 when the face plane is wanted). */
 int hive_render_resolve(hive_ctx *ctx, const uint64_t *d_key, int H, int W, const uint8_t background[3], uint8_t *d_color, float *d_depth, int32_t *d_face);
+
+/* ---- ray casting the volume and tracking the camera against it (KinectFusion-style frame-to-model ICP; no counterpart in the reference, which takes its
+ * poses from COLMAP or BundleFusion).  Float32 where stated, every operation rounded once (no fused multiply-add), in the order written here; pixel (u, v) =
+ * (column, row), pixel centres at integers.
+ *   ray        d = ((u - cx) / fx, (v - cy) / fy, 1); R, t = cam_pose (camera-to-world) rounded to float32 once; w_r = (R[r][0] d_0 + R[r][1] d_1) + R[r][2].
+ *              The ray parameter is camera z: P_r(z) = z w_r + t_r, and in voxel coordinates p_r(z) = (P_r(z) - origin_r) / voxel_size.
+ *   range      z_in = z_near, z_out = z_far (+inf for z_far <= 0); per axis r, with g0 = (t_r - origin_r) / voxel_size, gd = w_r / voxel_size and
+ *              hi = dim_r - 1 (the box of voxel centres): gd != 0: a = (0 - g0) / gd, b = (hi - g0) / gd, z_in = max(z_in, min(a, b)), z_out = min(z_out,
+ *              max(a, b)); gd == 0: no hit unless 0 <= g0 <= hi.  No hit unless z_in <= z_out.
+ *   sample     S(p): valid iff 0 <= p_r < dim_r - 1 on every axis and the eight corners floor(p) + {0, 1}^3 have weight > 0.  With f = p - floor(p) and T the
+ *              tsdf plane: c_xy = T[x][y][z0] + f_z (T[x][y][z1] - T[x][y][z0]); c_x = c_x0 + f_y (c_x1 - c_x0); S = c_0 + f_x (c_1 - c_0).
+ *   march      step = step_in_trunc * trunc; z_k = z_in + (float)k step for k = 0 .. min(floor((z_out - z_in) / step), 2^20).  The first k with S(z_{k-1})
+ *              valid and > 0 and S(z_k) valid and <= 0 is the hit: z* = z_{k-1} + (step S_{k-1}) / (S_{k-1} - S_k).  A valid pair going < 0 to > 0 (leaving a
+ *              surface from behind) ends the ray without a hit.  An invalid sample never pairs with a valid one.
+ *   outputs    depth = z* (0 without a hit: the convention of depth maps and of hive_render_resolve's depth plane); vertex = P(z*), world frame; normal =
+ *              g / sqrt((g_x g_x + g_y g_y) + g_z g_z) with g_r = S(p* + e_r) - S(p* - e_r), p* = p(z*): unit length, pointing into free space; (0, 0, 0) if
+ *              one of the six samples is invalid or the length is 0 (depth and vertex are still written); colour = the packed colour of voxel
+ *              clamp(floor(p* + 0.5), 0, dim - 1), unpacked r, g, b.  A pixel without a hit is all zeros in every plane.
+ * d_depth f32 [H][W], d_vertex f32 [H][W][3], d_normal f32 [H][W][3], d_color u8 [H][W][3]: device memory, any may be NULL.  K f32 3 x 3 and cam_pose f64 4 x 4
+ * are host arrays.  z_near >= 0; step_in_trunc > 0 (0.5 in the Python wrapper).  An x-slab volume is refused with HIVE_ERR_INVALID.  Nothing synchronises. */
+int hive_tsdf_raycast(hive_tsdf *vol, int H, int W, const float K[9], const double cam_pose[16], float z_near, float z_far, float step_in_trunc, float *d_depth,
+                      float *d_vertex, float *d_normal, uint8_t *d_color);
+/* The depth pyramid of a live frame with its vertex and normal maps (camera frame, float32).  d_depth f32 [H][W] metres, 0 = invalid (a sample counts when it
+ * is > 0).  Level 0 is the frame; level l + 1 has size (floor(H_l / 2), floor(W_l / 2)) and its pixel (u, v) comes from the samples (2v, 2u), (2v, 2u + 1),
+ * (2v + 1, 2u), (2v + 1, 2u + 1) of level l: m = the smallest valid one; sum and count, in that order, of the valid ones with d - m <= pyr_delta; the result
+ * is sum / count, or 0 for a block without a valid sample.  Level intrinsics: fx / 2, fy / 2, (cx - 0.5) / 2, (cy - 0.5) / 2 carried in float64 from level
+ * to level and rounded to float32 per level (level 0: K as given); K_levels (host, f32 [levels][9]) receives them.
+ *   vertex     V = ((d (u - cx)) / fx, (d (v - cy)) / fy, d); (0, 0, 0) where d is not valid
+ *   normal     a = V(u + 1, v) - V, b = V(u, v + 1) - V; c = a x b = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x); N = c / sqrt((c_x c_x + c_y c_y) +
+ *              c_z c_z), negated when (N_x V_x + N_y V_y) + N_z V_z > 0, so that it faces the camera like the ray cast's normals face free space.  (0, 0, 0)
+ *              on the last row and column, where one of the three depths is not valid, or where the length is 0 or not finite.
+ * The levels are packed back to back: d_depth_pyr f32 [sum H_l W_l], d_vertex_pyr and d_normal_pyr f32 [sum H_l W_l][3].  1 <= levels <= 8 and the last
+ * level must not be empty.  Nothing synchronises. */
+int hive_frame_maps(hive_ctx *ctx, const float *d_depth, int H, int W, const float K[9], int levels, float pyr_delta, float *d_depth_pyr, float *d_vertex_pyr,
+                    float *d_normal_pyr, float *K_levels);
+/* One Gauss-Newton step's sums of frame-to-model point-to-plane ICP at one pyramid level.  d_live_vertex / d_live_normal: the live frame's maps (camera frame,
+ * hive_frame_maps); d_model_vertex / d_model_normal: the volume ray cast at model_pose with this level's size and K (world frame, hive_tsdf_raycast).  A map
+ * pixel is valid iff its normal is not (0, 0, 0).  Per valid live pixel, in float64 from the float32 maps, with R, t = est_pose and M = model_pose^-1 =
+ * [R_m^T | -((R_m^T[r][0] t_0 + R_m^T[r][1] t_1) + R_m^T[r][2] t_2)] (both camera-to-world, host f64 4 x 4):
+ *   q_r = ((R[r][0] V_0 + R[r][1] V_1) + R[r][2] V_2) + t_r;  n_r = (R[r][0] N_0 + R[r][1] N_1) + R[r][2] N_2;  c = M q in q's order
+ *   kept iff c_z > 0; (pu, pv) = round(fx (c_x / c_z) + cx), round(fy (c_y / c_z) + cy) with the context's rounding mode lies inside the image; the model maps
+ *   are valid there; with d = V_m - q: sqrt((d_0 d_0 + d_1 d_1) + d_2 d_2) <= dist_thresh; (n_0 N_m0 + n_1 N_m1) + n_2 N_m2 >= cos_thresh
+ *   r = (N_m0 d_0 + N_m1 d_1) + N_m2 d_2;  J = [q x N_m, N_m] = (q_1 N_m2 - q_2 N_m1, q_2 N_m0 - q_0 N_m2, q_0 N_m1 - q_1 N_m0, N_m0, N_m1, N_m2)
+ * h_sums (host, 28): J_i J_j for i <= j row by row (21), J_i r (6), r r.  Minimising sum (r - J xi)^2 over xi = (omega, v) is A xi = b with A, b from these
+ * sums; the update is T <- [exp(omega) | v] T.  The sums are added in a fixed order -- pixel e = v W + u belongs to workgroup e / 256, thread e % 256; per
+ * workgroup the tree x[t] += x[t + off] for off = 128, 64 .. 1; then the workgroups' results in ascending order from 0.0 -- so every run gives the same bits
+ * (no floating-point atomic).  h_pairs (host): the number of kept pairs; without any, the sums are zeros.  d_pair_mask u8 [H][W] (device, may be NULL): 1
+ * where the live pixel was kept.  Synchronises the stream (one copy of 29 numbers). */
+int hive_icp_step(hive_ctx *ctx, int H, int W, const float K[9], const float *d_live_vertex, const float *d_live_normal, const float *d_model_vertex,
+                  const float *d_model_normal, const double model_pose[16], const double est_pose[16], float dist_thresh, float cos_thresh, double *h_sums,
+                  int64_t *h_pairs, uint8_t *d_pair_mask);
 
 /* ---- scoring a render against a held-out frame -- compare_images(ref_image, est_image), scripts/compare_image_pair.py:110-133, and ms_ssim as called at
  * scripts/experiments.py:1627-1635; the loops that use them are experiments.py:775-858 (LLFF) and :1554-1637 (HyperNeRF).  Pictures are u8 [N][H][W][3] in
