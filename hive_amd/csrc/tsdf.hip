@@ -44,6 +44,12 @@ struct FrameParams {
 // every buffer): depth f32 + colour u8x3 fused into one 8-byte texel, and max(depth) of the tile (the work list's per-row far cut,
 // below).  VEC: 4 pixels per lane (one 16-byte depth load, three 4-byte colour loads, two 16-byte stores -- needs W % 4 == 0, depth
 // 16-byte and colour 4-byte aligned); VEC = false is the scalar form for ragged / unaligned images.
+// A depth's key for the tile maximum: non-negative floats order like their bit patterns; zero and negative depths count as 0 (zero is
+// invalid, a negative depth can only update voxels nearer than the truncation margin, which every far cut keeps); a NaN depth counts as
+// +inf: it passes the contract's tests at EVERY camera depth (`depth != 0`, and `diff < -trunc` is false for a NaN diff), exactly as +inf does,
+// so no far cut may be taken from the finite depths around it.  (fmaxf would drop the NaN silently.)
+__device__ __forceinline__ unsigned depth_key(float d) { return d > 0.f ? __float_as_uint(d) : (d != d ? 0x7f800000u : 0u); }
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void prep_frame_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ color, int H, int W, int tile_shift,
                                                          int tiles_x, uint2 *__restrict__ out, unsigned *__restrict__ tile_max, int tile_stride,
@@ -59,7 +65,7 @@ __global__ __launch_bounds__(256) void prep_frame_kernel(const float *__restrict
     if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < zero_words) zero_next[threadIdx.x] = 0u;
     const int TS = 32 << tile_shift;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    // max over non-negative floats == max over their bit patterns; NaN / negatives are ignored (treated as 0)
+    // max over non-negative floats == max over their bit patterns (depth_key: negatives as 0, NaN as +inf)
     unsigned bits = 0;
     const int per_row = VEC ? TS / 4 : TS;
     for (int g = threadIdx.x; g < per_row * TS; g += 256) {
@@ -76,13 +82,12 @@ __global__ __launch_bounds__(256) void prep_frame_kernel(const float *__restrict
             uint4 *o = reinterpret_cast<uint4 *>(out + i);
             o[0] = make_uint4(__float_as_uint(d.x), p0, __float_as_uint(d.y), p1);
             o[1] = make_uint4(__float_as_uint(d.z), p2, __float_as_uint(d.w), p3);
-            const float m = fmaxf(fmaxf(d.x, d.y), fmaxf(d.z, d.w));
-            bits = max(bits, (m > 0.f) ? __float_as_uint(m) : 0u);
+            bits = max(max(bits, max(depth_key(d.x), depth_key(d.y))), max(depth_key(d.z), depth_key(d.w)));
         } else {
             const float d = depth[i];
             const unsigned rr = color[3 * (size_t)i + 0], gg = color[3 * (size_t)i + 1], bb = color[3 * (size_t)i + 2];
             out[i] = make_uint2(__float_as_uint(d), rr | (gg << 8) | (bb << 16));
-            bits = max(bits, (d > 0.f) ? __float_as_uint(d) : 0u);
+            bits = max(bits, depth_key(d));
         }
     }
     for (int off = 32; off > 0; off >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, off));

@@ -139,7 +139,12 @@ int hive_tsdf_device_ptrs(hive_tsdf *vol, float **d_tsdf, float **d_weight, floa
 /* TSDFVolume.integrate(color_im, depth_im, cam_intr, cam_pose, obs_weight) -- hive/fusion.py:124
  * color u8 [H][W][3] RGB, depth f32 [H][W] metres (0 = invalid), K f32 row-major 3x3,
  * cam_pose f64 row-major 4x4 camera-to-world.  n_updated (optional, host) receives the number
- * of voxels written by this call (forces a stream sync). */
+ * of voxels written by this call (forces a stream sync).
+ * Depths that are not positive finite numbers get no special treatment: a voxel in front of the camera that rounds to a pixel is
+ * updated unless `depth == 0` or `depth - cam_z < -trunc` -- the contract's tests, evaluated in float32 as the CPU oracle evaluates
+ * them.  So -0.0 is invalid like 0; a negative depth d updates the voxels with 0 < cam_z <= trunc + d (dist < 0);
+ * +inf and NaN update EVERY voxel in front of the camera that rounds to the pixel, with dist = 1 (`diff < -trunc` is false for a NaN, and
+ * fminf(1, NaN) = 1).  Callers that want such pixels ignored set them to 0 first. */
 int hive_tsdf_integrate(hive_tsdf *vol, const uint8_t *color, const float *depth, int H, int W,
                         const float K[9], const double cam_pose[16], float obs_weight,
                         int mem, uint64_t *n_updated);
