@@ -159,8 +159,9 @@ __global__ __launch_bounds__(256) void project_kernel(const double *__restrict__
 }
 
 // world2image + the visibility reduction of HiveDataset.select_key_frames (hive/io.py:1161-1175): project,
-// round (np.round), keep pixels inside [0, W) x [0, H), and reduce them to (min u, max u, min v, max v, count).
+// round as project_kernel<RM> does (RM 0: np.round), keep pixels inside [0, W) x [0, H), and reduce them to (min u, max u, min v, max v, count).
 // out[0..4] must be initialised to {INT_MAX, INT_MIN, INT_MAX, INT_MIN, 0}.
+template <int RM>
 __global__ __launch_bounds__(256) void project_bbox_kernel(const double *__restrict__ pts, long long n, ProjectParams p, int W, int H,
                                                            int *__restrict__ out) {
     int mn_u = 0x7fffffff, mx_u = (int)0x80000000, mn_v = 0x7fffffff, mx_v = (int)0x80000000, cnt = 0;
@@ -169,7 +170,8 @@ __global__ __launch_bounds__(256) void project_bbox_kernel(const double *__restr
         double cam[3], c[3];
         for (int r = 0; r < 3; ++r) cam[r] = p.R[3 * r + 0] * X[0] + p.R[3 * r + 1] * X[1] + p.R[3 * r + 2] * X[2] + p.t[r];
         for (int r = 0; r < 3; ++r) c[r] = p.K[3 * r + 0] * cam[0] + p.K[3 * r + 1] * cam[1] + p.K[3 * r + 2] * cam[2];
-        const int u = (int)rint(c[0] / c[2] / p.scale), v = (int)rint(c[1] / c[2] / p.scale);
+        const double uf = c[0] / c[2] / p.scale, vf = c[1] / c[2] / p.scale;
+        const int u = (int)(RM ? round(uf) : rint(uf)), v = (int)(RM ? round(vf) : rint(vf));
         if (u >= 0 && u < W && v >= 0 && v < H) {
             mn_u = min(mn_u, u);
             mx_u = max(mx_u, u);
@@ -723,7 +725,10 @@ int hive_project_bbox(hive_ctx *ctx, const double *points, int64_t n, const doub
     memcpy(p.t, t, sizeof(p.t));
     p.scale = 1.0;
     const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, (long long)ctx->num_cus * 4));
-    hipLaunchKernelGGL(project_bbox_kernel, grid, dim3(256), 0, ctx->stream, (const double *)d_pts, (long long)n, p, W, H, d_out);
+    if (ctx->round_mode)
+        hipLaunchKernelGGL(project_bbox_kernel<1>, grid, dim3(256), 0, ctx->stream, (const double *)d_pts, (long long)n, p, W, H, d_out);
+    else
+        hipLaunchKernelGGL(project_bbox_kernel<0>, grid, dim3(256), 0, ctx->stream, (const double *)d_pts, (long long)n, p, W, H, d_out);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     HIVE_CHECK_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
     HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -272,7 +272,7 @@ int hive_project(hive_ctx *ctx, const double *points, int64_t n, const double K[
                  int32_t *out_uv_i32, double *out_uv_f64, double *out_depth);
 
 /* world2image + the visibility reduction of HiveDataset.select_key_frames -- hive/io.py:1161-1175:
- * project points (f64 [n][3]), round half-to-even, keep pixels inside [0,W) x [0,H) and return
+ * project points (f64 [n][3]), rounded per the context's round mode (default half-even = np.round), keep pixels inside [0,W) x [0,H) and return
  * out = {min u, max u, min v, max v, count} (count == 0: the extrema are INT_MAX / INT_MIN). */
 int hive_project_bbox(hive_ctx *ctx, const double *points, int64_t n, const double K[9], const double R[9],
                       const double t[3], int W, int H, int mem, int32_t out[5]);
@@ -655,6 +655,7 @@ int hive_lpips_forward(hive_lpips *net, const uint8_t *d_ref_u8, const uint8_t *
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
  * (x 1/1000 as float32, > max_depth -> 0), optional mask (non-zero -> depth 0, fusion.py:121).
+ * Millimetres outside [0, 65535], where the reference's astype is undefined, saturate: negative -> 0, above -> 65535.
  * in: f32 or f16/bf16 depth in metres [H][W] on the device; out_mm (optional u16) and out_m (f32). */
 typedef enum hive_dtype { HIVE_F32 = 0, HIVE_F16 = 1, HIVE_BF16 = 2 } hive_dtype;
 int hive_depth_quantize(hive_ctx *ctx, const void *d_depth, int dtype, int H, int W,

@@ -300,12 +300,15 @@ void oracle_dilate_mask(const uint8_t *mask, int H, int W, int iterations, uint8
 }
 
 /* hive/dataset_adaptors.py:1432-1433 (x1000, astype(uint16) truncation) followed by the loader's
- * hive/io.py:1032-1039 (x depth_scale as float32, > max_depth -> 0) and fusion.py:121 (mask -> 0). */
+ * hive/io.py:1032-1039 (x depth_scale as float32, > max_depth -> 0) and fusion.py:121 (mask -> 0).
+ * astype(np.uint16) of a float outside [0, 65535] is undefined in the reference (C's conversion: numpy wraps it on x86 and saturates it on ARM, with a
+ * RuntimeWarning); DPT depth is <= 7.257 m and never gets there.  This library DEFINES it as saturation (negative -> 0, above -> 65535), here and in
+ * hive_depth_quantize: a 66 m depth must not come back as 0.464 m. */
 void oracle_depth_quantize(const float *depth_m, int64_t n, float depth_scale, float max_depth,
                            const uint8_t *mask, uint16_t *out_mm, float *out_m) {
     for (int64_t i = 0; i < n; ++i) {
         const float mm_f = depth_m[i] * 1000.0f;
-        const uint16_t mm = (uint16_t)(int32_t)mm_f; /* DPT depth <= 7.257 m: no overflow */
+        const uint16_t mm = (uint16_t)(int32_t)(mm_f < 0.0f ? 0.0f : mm_f > 65535.0f ? 65535.0f : mm_f); /* truncation inside the range */
         float m = depth_scale * (float)mm;
         if (m > max_depth) m = 0.0f;
         if (mask && mask[i]) m = 0.0f;
