@@ -789,8 +789,7 @@ extern "C" int hive_nhwc_conv_gn_apply(hive_ctx *ctx, const void *d_x, int dtype
     HIVE_REQUIRE(ctx, d_gamma && d_beta && d_scratch && fused, "nhwc_conv_gn_apply: NULL argument");
     *fused = 0;
     const long long hw = (long long)H_out * W_out;
-    // eligible: whole 256-channel tiles, a lane's 8 channels inside one group, a tile inside two samples
-    if (G <= 0 || C_out % 256 != 0 || C_out % G != 0 || (C_out / G) % 8 != 0 || hw < 256) return HIVE_OK;
+    if (!hive_conv_gn_two_pass_eligible(C_out, G, hw)) return HIVE_OK;
     const int64_t partial_floats = hive_nhwc_conv_gn_partial_floats((int64_t)N * hw, C_out);
     HIVE_REQUIRE(ctx, scratch_floats >= partial_floats + 2ll * N * G, "nhwc_conv_gn_apply: scratch holds %lld floats, %lld needed", (long long)scratch_floats,
                  (long long)(partial_floats + 2ll * N * G));
@@ -827,7 +826,7 @@ extern "C" int hive_nhwc_conv_gn_apply_gram(hive_ctx *ctx, const void *d_x, int 
     HIVE_REQUIRE(ctx, d_gamma && d_beta && d_scratch && d_tables && fused, "nhwc_conv_gn_apply_gram: NULL argument");
     *fused = 0;
     const long long hw = (long long)H_out * W_out;
-    if (G < 4 || 256 % G != 0 || G > 64 || C_out % 256 != 0 || C_out % G != 0 || (C_out / G) % 8 != 0 || hw < 256 || !(C_in == 64 || C_in == 128 || C_in == 256)) return HIVE_OK;
+    if (G < 4 || 256 % G != 0 || G > 64 || !hive_conv_gn_two_pass_eligible(C_out, G, hw) || !(C_in == 64 || C_in == 128 || C_in == 256)) return HIVE_OK;
     HIVE_REQUIRE(ctx, scratch_floats >= 2ll * N * G, "nhwc_conv_gn_apply_gram: scratch holds %lld floats, %lld needed", (long long)scratch_floats, 2ll * N * G);
     HIVE_REQUIRE(ctx, (long long)(H_out - 1) * stride < H && (long long)(W_out - 1) * stride < W, "nhwc_conv_gn_apply_gram: output %d x %d reaches outside the %d x %d input", H_out,
                  W_out, H, W);
@@ -845,6 +844,19 @@ extern "C" int hive_nhwc_conv_gn_apply_gram(hive_ctx *ctx, const void *d_x, int 
     if (rc) return rc;
     *fused = 1;
     return HIVE_OK;
+}
+
+// Which of the two a caller runs: the GroupNorm statistics from the input's Gram matrices where that is the cheaper way to them (csrc/gram.hip;
+// tools/probe_gram.py at the bench batch: the whole operation 651 -> 532 us at 64 -> 256 channels, 378 -> 317 at 128 -> 512, 499 -> 472 for the stride-2
+// 256 -> 512; 254 -> 262 at 256 -> 1024, which keeps the two-pass form) ... and only for large outputs: the three small kernels behind the Gram matrices cost
+// 40-60 us whatever the batch (break-even at ~32 frames for the 64- / 128-channel inputs, ~100 for the stride-2 one).  Never where the context is
+// deterministic (the choice depends on the batch size); HIVE_GN_GRAM=0 switches it off (read at every call).
+extern "C" int hive_gn_gram_preferred(int C_in, int C_out, int stride, int G, int N, int H_out, int W_out, int deterministic) {
+    const char *env = getenv("HIVE_GN_GRAM");
+    const long long hw = (long long)H_out * W_out;
+    if ((env && env[0] == '0') || deterministic || G != 32 || !hive_conv_gn_two_pass_eligible(C_out, G, hw)) return 0;
+    const long long out_elems = (long long)N * hw * C_out;
+    return ((C_in == 64 || C_in == 128) && out_elems >= 150000000ll) || (C_in == 256 && stride == 2 && out_elems >= 250000000ll);
 }
 
 extern "C" int hive_nhwc_conv(hive_ctx *ctx, const void *d_x, int dtype, int N, int H, int W, int C_in, int C_out, int kernel, int stride, int pad_top,

@@ -161,6 +161,12 @@ int hive_pinned_small(hive_ctx *ctx, void **out);
 int hive_upload(hive_ctx *ctx, void *dst, const void *src, size_t bytes);
 // dpt_ops.hip: (mean, rstd) per (sample, group) from the per-tile channel sums a GN convolution epilogue left (conv.hip)
 int hive_gn_finalize_tiles(hive_ctx *ctx, const float *d_partial, int N, int HW, int C, int G, int tile_rows, float eps, float *d_stats);
+// conv.hip: THE eligibility of the two-pass conv + GroupNorm, for its launchers hive_nhwc_conv_gn_apply and hive_nhwc_conv_gn_apply_gram (declared in
+// hive_mi355x.h; *fused = 0 otherwise), for hive_gn_gram_preferred and for the network object, which allocates the pair's intermediate where it fails:
+// whole 256-channel tiles, a lane's 8 channels inside one group, a tile inside two samples
+inline bool hive_conv_gn_two_pass_eligible(int C_out, int G, long long hw_out) {
+    return G > 0 && C_out % 256 == 0 && C_out % G == 0 && (C_out / G) % 8 == 0 && hw_out >= 256;
+}
 // split-K workspace of at least `bytes` and the (zeroed) arrival counters (HIVE_SPLITK_TILES of them)
 constexpr int HIVE_SPLITK_TILES = 4096;
 int hive_splitk_workspace(hive_ctx *ctx, size_t bytes, void **ws, unsigned **count);

@@ -26,6 +26,15 @@ def parameter_stamp(model):
     return tuple((p.data_ptr(), p._version, p.dtype) for p in model.parameters())
 
 
+def plan_arena(backbone, b, h, w, net_size=None):
+    """(bytes, layout hash) of the activation arena a forward of ``b`` frames of ``h`` x ``w`` needs (``hive_dpt_plan_arena``: the walk every forward sizes
+    its arena by).  ``backbone``: 0 = vitb_rn50_384, 1 = vitl16_384.  Host code only: needs the library, not a device."""
+    net_h, net_w = (h, w) if net_size is None else (int(net_size[0]), int(net_size[1]))
+    n, layout = ctypes.c_int64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.load().hive_dpt_plan_arena(int(backbone), int(b), int(h), int(w), net_h, net_w, ctypes.byref(n), ctypes.byref(layout)))
+    return int(n.value), int(layout.value)
+
+
 class NativeDPT:
     def __init__(self, model, ctx=None):
         """:param model: a ``hive_amd.dpt.models.DPTDepthModel`` (``vitb_rn50_384`` or ``vitl16_384``) whose parameters live on an MI355X."""
@@ -136,6 +145,10 @@ class NativeDPT:
         n = ctypes.c_int64(0)
         self.ctx.check(self.ctx.lib.hive_dpt_arena_bytes(self.handle, ctypes.byref(n)))
         return int(n.value)
+
+    def plan_arena(self, b, h, w, net_size=None):
+        """Bytes of the arena this network plans for ``b`` frames of ``h`` x ``w``: what ``arena_bytes()`` is after that forward on a fresh object."""
+        return plan_arena(0 if self.model.pretrained.hybrid else 1, b, h, w, net_size)[0]
 
     def close(self):
         if getattr(self, "handle", None) and _lib.alive():

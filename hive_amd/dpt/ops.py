@@ -5,8 +5,6 @@
 /root/reference/hive/dataset_adaptors.py:1394-1401) channels-last CUDA tensors; a layer the kernels do not cover raises
 ``HiveError`` -- there is no per-layer drop to a PyTorch operator.  ``engine="torch"`` is the plain PyTorch formulation: the
 float32 / CPU reference the numerics tests compare against (and ``estimate_depth_dpt(optimize=False)``'s float32 network)."""
-import os
-
 import torch
 import torch.nn.functional as F
 
@@ -197,8 +195,6 @@ def conv_gn_act(x, conv, norm, weight=None, same_pad=False, relu=True, residual=
     n, _, ih, iw = x.shape
     k, st, pt, pl, oh, ow = conv_geometry(conv, ih, iw, same_pad)
     cout, g = conv.out_channels, norm.num_groups
-    if cout % 256 or cout % g or (cout // g) % 8 or oh * ow < 256:
-        return None
     w = weight if weight is not None else _conv3x3_weight(conv)
     if not w.is_contiguous(memory_format=torch.channels_last):
         w = w.contiguous(memory_format=torch.channels_last)
@@ -207,12 +203,10 @@ def conv_gn_act(x, conv, norm, weight=None, same_pad=False, relu=True, residual=
     ctx = _lib.default_context(x.device.index or 0)
     scratch = torch.empty(int(ctx.lib.hive_nhwc_conv_gn_partial_floats(n * oh * ow, cout)) + 2 * n * g, dtype=torch.float32, device=x.device)
     fused = ctypes.c_int(0)
-    # 1 x 1 convolutions whose input is narrow enough: GroupNorm statistics from the input's Gram matrices (csrc/gram.hip) -- the rule of the network object
-    # (csrc/dpt_net.hip conv_norm), so that both orchestrations stay bit-identical; HIVE_GN_GRAM=0 switches it off
+    # 1 x 1 convolutions: GroupNorm statistics from the input's Gram matrices (csrc/gram.hip) where the library's rule prefers them -- the one the network
+    # object asks too (csrc/dpt_net.hip conv_norm), so that both orchestrations stay bit-identical
     cin = conv.in_channels
-    out_elems = n * oh * ow * cout
-    if k == 1 and os.environ.get("HIVE_GN_GRAM", "1") != "0" and not getattr(ctx, "deterministic", False) and g == 32 and ((cin in (64, 128) and out_elems >= 150_000_000) or
-                                                                               (cin == 256 and st == 2 and out_elems >= 250_000_000)):
+    if k == 1 and ctx.lib.hive_gn_gram_preferred(cin, cout, st, g, n, oh, ow, int(bool(getattr(ctx, "deterministic", False)))):
         def tables():
             t = torch.empty(int(ctx.lib.hive_gn_gram_table_floats(cin, g)), dtype=torch.float32, device=x.device)
             ctx.check(ctx.lib.hive_gn_gram_prepare(ctx.handle, w.data_ptr(), _code(x.dtype), cin, cout, g, t.data_ptr()))

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 6
+#define HIVE_ABI_VERSION 7
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -833,6 +833,13 @@ int hive_gn_gram_stats(hive_ctx *ctx, const void *d_x, int dtype, int N, int H, 
 int hive_nhwc_conv_gn_apply_gram(hive_ctx *ctx, const void *d_x, int dtype, int N, int H, int W, int C_in, int C_out, int stride, int H_out, int W_out,
                                  const void *d_w, const float *d_tables, int G, const void *d_gamma, const void *d_beta, float eps,
                                  const void *d_residual, int relu, void *d_out, void *d_scratch, int64_t scratch_floats, int *fused);
+/* 1 where the statistics from the Gram matrices are the cheaper way for this 1 x 1 convolution (hive_nhwc_conv_gn_apply_gram), 0 where the two-pass form is
+ * (hive_nhwc_conv_gn_apply): THE rule of the network object and of the Python orchestration, which stay bit-identical only while they share it.  1 needs
+ * all of: hive_nhwc_conv_gn_apply's conditions; G == 32; not deterministic (hive_ctx_set_deterministic: the choice depends on the batch size); the
+ * environment's HIVE_GN_GRAM not beginning with '0' (read at every call); and N * H_out * W_out * C_out >= 150 000 000 output elements with C_in 64 or
+ * 128, or >= 250 000 000 with C_in == 256 and stride == 2 (below that the Gram path's three small kernels cost more than the first pass they replace).  Pure host
+ * code: no context, no device. */
+int hive_gn_gram_preferred(int C_in, int C_out, int stride, int G, int N, int H_out, int W_out, int deterministic);
 
 /* DPT-Large (timm vit_large_patch16_384, `DPTDepthModel(backbone="vitl16_384")`) pieces that are not plain convolutions of
  * hive_nhwc_conv:
@@ -922,7 +929,15 @@ int hive_dpt_forward(hive_dpt *dpt, const uint8_t *d_rgb, int B, int H, int W, c
  * (net_h / 16)(net_w / 16) + 1.  With net == frame size this is hive_dpt_forward. */
 int hive_dpt_forward_frames(hive_dpt *dpt, const uint8_t *d_rgb, int B, int frame_h, int frame_w, int net_h, int net_w, const void *d_pos_embed,
                             float *d_depth, float max_depth, uint16_t *d_out_mm, float *d_out_m);
-/* Bytes of the activation arena (grown to the largest forward seen: the high-water mark of its maps, which are released behind
+/* The activation arena a forward of these shapes needs, without a device: every forward first PLANS -- walks the network's allocation sequence (each map
+ * allocated from shapes alone, released behind its last consumer, first fit over the freed blocks) -- reserves *bytes, the plan's high-water mark, and then
+ * launches over that memory repeating the same sequence.  A launch walk that asks for a block ending beyond the plan launches nothing with it: the forward
+ * returns HIVE_ERR_STATE, as it does when it ends with another size than planned.  hive_dpt_forward_frames sizes its arena through this very walk.
+ * backbone as hive_dpt_config; the argument checks of hive_dpt_forward_frames.  *layout_hash (may be NULL): 64-bit FNV-1a (basis 0xcbf29ce484222325, prime
+ * 0x100000001b3) over the (offset, bytes) of every allocation in order, each as 8 little-endian bytes: it fixes the layout, not only its size.  Pure host
+ * code: no context. */
+int hive_dpt_plan_arena(int backbone, int B, int frame_h, int frame_w, int net_h, int net_w, int64_t *bytes, uint64_t *layout_hash);
+/* Bytes of the activation arena (grown to the largest plan seen: the high-water mark of its maps, which are released behind
  * their last consumer -- ~10 GB for 96 frames of 480 x 640, where the maps total 38 GB). */
 int hive_dpt_arena_bytes(hive_dpt *dpt, int64_t *bytes);
 /* The table's tensors were overwritten in place: refresh what the object derived from them -- the ViT engine's folded LayerNorm weights (captured at

@@ -496,3 +496,20 @@ def test_native_network_object_dpt_large(gpu_ctx):
         assert float(d_c.max() - d_c.min()) > 0.5, "the seeded weights must give a depth range"
         assert torch.equal(d_c, d_py), f"depth differs by up to {float((d_c - d_py).abs().max()) * 1000:.3f} mm"
         assert torch.equal(mm_c, mm_py) and torch.equal(m_c, m_py)
+
+
+@pytest.mark.parametrize("backbone", ["vitb_rn50_384", "vitl16_384"])
+def test_network_object_sizes_its_arena_by_the_exported_plan(gpu_ctx, backbone):
+    """A fresh object's arena after one forward is exactly what ``hive_dpt_plan_arena`` answers for that shape (tests/test_dpt_plan_cpu.py pins those
+    answers to the recorded layouts): the forward sizes itself by the exported plan, and its launch walk ended at the planned size."""
+    from hive_amd.dpt.models import DPTDepthModel
+    from hive_amd.dpt.native import NativeDPT
+    model = DPTDepthModel(path=None, scale=SCALE, shift=SHIFT, invert=True, engine="hip", backbone=backbone).eval()
+    model = model.to(memory_format=torch.channels_last).to(torch.bfloat16).cuda()
+    nat = NativeDPT(model, ctx=gpu_ctx)
+    assert nat.arena_bytes() == 0
+    frames = torch.from_numpy(np.random.default_rng(9).integers(0, 256, (2, 96, 160, 3), dtype=np.uint8)).cuda()
+    depth, _, _ = nat.forward(frames, max_depth=10.0)
+    assert depth.shape == (2, 96, 160)
+    assert nat.arena_bytes() == nat.plan_arena(2, 96, 160) == {"vitb_rn50_384": 8421888, "vitl16_384": 8171520}[backbone]
+    nat.close()
