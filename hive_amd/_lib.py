@@ -18,7 +18,7 @@ OK, ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_EMPTY, ERR_STATE = 0, -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
 ROUND_HALF_EVEN, ROUND_HALF_AWAY = 0, 1
 F32, F16, BF16 = 0, 1, 2
-ABI_VERSION = 7  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step; 7 = hive_dpt_plan_arena, hive_gn_gram_preferred
+ABI_VERSION = 8  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step; 7 = hive_dpt_plan_arena, hive_gn_gram_preferred; 8 = hive_sift_*, hive_knn_match, hive_mifd
 
 c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 P = ctypes.POINTER
@@ -121,6 +121,14 @@ SIGNATURES = {
     "hive_lpips_destroy": (c_int, [c_void_p]),
     "hive_lpips_layer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hive_lpips_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hive_sift_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_int, P(c_void_p)]),
+    "hive_sift_destroy": (c_int, [c_void_p]),
+    "hive_sift_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "hive_sift_read_layer": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "hive_sift_read_candidates": (c_int, [c_void_p, c_int, c_void_p]),
+    "hive_sift_set_last_stage": (c_int, [c_void_p, c_int]),
+    "hive_knn_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "hive_mifd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_depth_apply_mask_se": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "hive_vit_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, P(c_void_p)]),
     "hive_vit_weights_modified": (c_int, [c_void_p]),

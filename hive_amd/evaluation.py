@@ -1,12 +1,15 @@
 """Score renders against held-out frames on the MI355X: the scoring half of the reference's experiment loops (/root/reference/scripts/experiments.py:775-858
 for LLFF, :1554-1637 for HyperNeRF) -- ``compare_images`` (scripts/compare_image_pair.py:110-133: cv2 gray, skimage SSIM and PSNR, LPIPS),
 ``pytorch_msssim.ms_ssim`` (:1627-1635), plain and with the frame whitened where the render shows background (:846-848) -- by the kernels of
-csrc/similarity.hip and csrc/lpips.hip.  Pictures stay on the device; the only copy back is the scores.
+csrc/similarity.hip and csrc/lpips.hip, and ``mifd`` (compare_image_pair.py:44-97) by the SIFT detector and the exact matcher of csrc/sift.hip
+(``hive_amd.features``).  Pictures stay on the device; the only copy back is the scores (and, for MIFD, the keypoint counts).
 
 The rules are stated in include/hive_mi355x.h above ``hive_similarity_ssim_psnr`` and ``hive_lpips_create`` and restated in tests/similarity_restatement.py and
 tests/lpips_restatement.py.  cv2, skimage, pytorch_msssim, lpips and torchvision cannot be run beside this code: the gray conversion is not pinned against cv2,
 SSIM and PSNR are not pinned against skimage, MS-SSIM is not pinned against pytorch_msssim, LPIPS is not pinned against lpips / torchvision.  LPIPS needs the
-AlexNet and linear-layer weights (``LPIPS.from_files``); without a model its slots hold nan.  MIFD (SIFT) is absent: its slot holds nan."""
+AlexNet and linear-layer weights (``LPIPS.from_files``); without a model its slots hold nan.  MIFD needs a ``features.SIFT`` object (``mifd=`` / ``sift=``);
+without one its slot holds nan.  Its SIFT is restated from recall of OpenCV 4.x and not pinned against cv2; its matcher is the exact nearest-neighbour search
+and not pinned against the reference's approximate FLANN matcher (include/hive_mi355x.h above ``hive_sift_create``, tests/sift_restatement.py)."""
 import json
 import warnings
 from dataclasses import dataclass
@@ -49,6 +52,9 @@ class SimilarityResult:
     gray_est: object = None
     lpips: np.ndarray = None  # with ``image_similarity(..., lpips=model)``
     lpips_masked: np.ndarray = None
+    mifd: np.ndarray = None  # with ``image_similarity(..., mifd=sift)``: float64 (N,), nan where a pair has no score
+    mifd_matches: np.ndarray = None  # int32 (N,): the ratio-test survivors behind ``mifd``
+    mifd_masked: np.ndarray = None
 
 
 def _checked_shapes(ref, est, ms_ssim, channel_order):
@@ -100,7 +106,7 @@ def ms_ssim_window():
     return np.ascontiguousarray(g / g.sum())
 
 
-def image_similarity(ref, est, *, ms_ssim=False, mask_background=False, channel_order="bgr", return_maps=False, ctx=None, lpips=None):
+def image_similarity(ref, est, *, ms_ssim=False, mask_background=False, channel_order="bgr", return_maps=False, ctx=None, lpips=None, mifd=None):
     """SSIM and PSNR of the gray pictures, as ``compare_images`` of scripts/compare_image_pair.py:110-133 computes them, and on request MS-SSIM of the colour
     pictures as experiments.py:1627-1635 does, for one pair or a batch, on the GPU.
 
@@ -113,7 +119,11 @@ def image_similarity(ref, est, *, ms_ssim=False, mask_background=False, channel_
     one grid dimension.  The only device-to-host copy is the scores.
 
     ``lpips``: an ``LPIPS`` model; the result then carries ``lpips`` and, with ``mask_background``, ``lpips_masked`` from the same device tensors (a second
-    copy back of scores).  A picture with a side below 31 has no LPIPS: the fields are nan and a warning says so."""
+    copy back of scores).  A picture with a side below 31 has no LPIPS: the fields are nan and a warning says so.
+
+    ``mifd``: a ``features.SIFT`` object; the result then carries ``mifd`` (``mifd(ref_gray, est_gray)`` of compare_image_pair.py:44-97 with its defaults),
+    ``mifd_matches`` and, with ``mask_background``, ``mifd_masked``, from the gray planes the SSIM kernel wrote, which never leave the device (the keypoint counts
+    and the scores are copied back).  A pair without a score is nan, with the reference's warning; so is a picture with a side below 6, which SIFT cannot handle."""
     n, h, w, batched = _checked_shapes(ref, est, ms_ssim, channel_order)
     import torch
     dev = next((a.device for a in (ref, est) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
@@ -132,8 +142,9 @@ def image_similarity(ref, est, *, ms_ssim=False, mask_background=False, channel_
     tiles = -(-(h - 6) // 32) * -(-(w - 6) // 32)
     partials = f64(vn, tiles)
     maps = f64(variants, n, h - 6, w - 6) if return_maps else None
-    gray_ref = torch.empty((variants, n, h, w), dtype=torch.uint8, device=dev) if return_maps else None
-    gray_est = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if return_maps else None
+    want_gray = return_maps or mifd is not None
+    gray_ref = torch.empty((variants, n, h, w), dtype=torch.uint8, device=dev) if want_gray else None
+    gray_est = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_gray else None
     ctx.check(lib.hive_similarity_ssim_psnr(handle, ptr(ref_d), ptr(est_d), n, h, w, int(channel_order == "rgb"), variants, ptr(partials), ptr(sse), ptr(maps),
                                             ptr(gray_ref), ptr(gray_est)))
     ctx.check(lib.hive_similarity_finish(handle, ptr(partials), vn, tiles, float((h - 6) * (w - 6)), ptr(results[vn:])))
@@ -172,6 +183,26 @@ def image_similarity(ref, est, *, ms_ssim=False, mask_background=False, channel_
         else:
             scored = lpips(ref_d, est_d, mask_background=mask_background, ctx=ctx)
             out.lpips, out.lpips_masked = scored.lpips, scored.lpips_masked
+    if mifd is not None:
+        from hive_amd import features
+        if min(h, w) < features.SIFT_MIN_SIDE:
+            warnings.warn(f"{h} x {w} is smaller than {features.SIFT_MIN_SIDE} x {features.SIFT_MIN_SIDE}: no SIFT, the MIFD scores are nan")
+            out.mifd, out.mifd_matches = np.full(n, NAN), np.zeros(n, dtype=np.int32)
+            out.mifd_masked = np.full(n, NAN) if mask_background else None
+        else:
+            # pictures [0, vn): the reference planes (plain, then masked), [vn, vn + n): the estimates; pair (variant, i) is picture variant * n + i against vn + i
+            found = mifd.detect_device(torch.cat([gray_ref.reshape(vn, h, w), gray_est]), None, ctx)
+            scored = [features.score_pairs(mifd, found, v * n, vn, n, ctx) for v in range(variants)]
+            counts = found[2].cpu().numpy()
+            mifd.check_counts(counts)
+            scores_h = np.stack([s[0].cpu().numpy() for s in scored])
+            matches_h = np.stack([s[1].cpu().numpy() for s in scored])
+            for v in range(variants):
+                for i in range(n):
+                    if np.isnan(scores_h[v, i]):
+                        features.warn_no_score(int(counts[v * n + i, 2]), int(counts[vn + i, 2]), int(matches_h[v, i]))
+            out.mifd, out.mifd_matches = scores_h[0], matches_h[0]
+            out.mifd_masked = scores_h[1] if mask_background else None
     return out
 
 
@@ -347,18 +378,19 @@ class LPIPS:
         return out
 
 
-def compare_images(ref_image, est_image, lpips_fn=None, return_mifd=False):
+def compare_images(ref_image, est_image, lpips_fn=None, return_mifd=False, sift=None):
     """``compare_images`` of scripts/compare_image_pair.py:110-133 for one pair of uint8 (H, W, 3) pictures: ``(ssim, psnr, lpips)``, with ``mifd`` behind it when
     ``return_mifd`` is set.  SSIM and PSNR come from ``image_similarity`` with the default channel order.  ``lpips_fn``: an ``LPIPS`` model of this module gives
     the third score (nan, with a warning, for a picture with a side below 31); anything else -- None, or the lpips package's own callable -- is ignored and the
-    score is nan.  MIFD needs SIFT, which does not exist here: nan."""
+    score is nan.  ``sift``: a ``features.SIFT`` object gives the fourth score, ``mifd(ref_gray, est_gray)`` on the gray planes of the SSIM (nan, with the
+    reference's warning, for a pair without enough descriptors or matches); without one the fourth value stays nan."""
     model = lpips_fn if isinstance(lpips_fn, LPIPS) else None
-    r = image_similarity(ref_image, est_image, lpips=model)
+    r = image_similarity(ref_image, est_image, lpips=model, mifd=sift if return_mifd else None)
     scores = (float(r.ssim[0]), float(r.psnr[0]), float(r.lpips[0]) if model is not None else NAN)
-    return (*scores, NAN) if return_mifd else scores
+    return (*scores, float(r.mifd[0]) if r.mifd is not None else NAN) if return_mifd else scores
 
 
-def compare_renders(camera_matrix, poses, frames, meshes, *, ms_ssim=False, size=None, names=None, lpips=None):
+def compare_renders(camera_matrix, poses, frames, meshes, *, ms_ssim=False, size=None, names=None, lpips=None, mifd=None):
     """The render-and-score loop of experiments.py:833-852 (and :1594-1614 with ``ms_ssim``): view i is ``render.render_mesh(camera_matrix, poses[i],
     *meshes_i)``, all views share one ``RenderBuffers``, the renders are stacked on the device and scored against ``frames`` (uint8 (N, H, W, 3), numpy or
     device) by one ``image_similarity(..., mask_background=True)`` call.
@@ -370,7 +402,8 @@ def compare_renders(camera_matrix, poses, frames, meshes, *, ms_ssim=False, size
     Returns ``(renders, rows)``: the uint8 (N, H, W, 3) device tensor and one dict per view with ``ssim``, ``psnr``, ``lpips``, ``ssim_masked``,
     ``psnr_masked``, ``lpips_masked`` behind the names; the two LPIPS scores come from ``lpips``, an ``LPIPS`` model, on the same device tensors, and are nan without
     one (or, with a warning, for pictures with a side below 31).  With ``ms_ssim`` rows also carry ``ms_ssim`` and ``ms_ssim_masked``, and the rule of
-    :1609-1610 applies: a masked result with infinite PSNR, an MS-SSIM of exactly 1.0 or (with a model) an LPIPS of exactly 0.0 becomes all nan."""
+    :1609-1610 applies: a masked result with infinite PSNR, an MS-SSIM of exactly 1.0 or (with a model) an LPIPS of exactly 0.0 becomes all nan.
+    ``mifd``: a ``features.SIFT`` object; rows then also carry ``mifd`` and ``mifd_masked`` (only then)."""
     import torch
     from hive_amd import render
     n = len(poses)
@@ -386,7 +419,7 @@ def compare_renders(camera_matrix, poses, frames, meshes, *, ms_ssim=False, size
     h, w = (int(v) for v in (size if size is not None else tuple(frames.shape[1:3])))
     buffers = render.RenderBuffers(h, w)
     renders = torch.stack([render.render_mesh(camera_matrix, poses[i], *(meshes[i] if per_view else meshes), size=(h, w), buffers=buffers) for i in range(n)])
-    r = image_similarity(frames, renders, ms_ssim=ms_ssim, mask_background=True, lpips=lpips)
+    r = image_similarity(frames, renders, ms_ssim=ms_ssim, mask_background=True, lpips=lpips, mifd=mifd)
     rows = []
     for i in range(n):
         name = names[i] if names is not None else {}
@@ -399,6 +432,8 @@ def compare_renders(camera_matrix, poses, frames, meshes, *, ms_ssim=False, size
             row.update(ms_ssim=float(r.ms_ssim[i]), ms_ssim_masked=float(r.ms_ssim_masked[i]))
             if np.isinf(row["psnr_masked"]) or row["ms_ssim_masked"] == 1.0 or row["lpips_masked"] == 0.0:
                 row.update(ssim_masked=NAN, psnr_masked=NAN, lpips_masked=NAN, ms_ssim_masked=NAN)
+        if mifd is not None:
+            row.update(mifd=float(r.mifd[i]), mifd_masked=float(r.mifd_masked[i]))
         rows.append(row)
     return renders, rows
 

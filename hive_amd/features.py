@@ -1,0 +1,300 @@
+"""SIFT keypoints and descriptors, the exact 2-nearest-neighbour matcher and MIFD on the MI355X (csrc/sift.hip): ``mifd`` of the reference's
+scripts/compare_image_pair.py:44-97, and the detector / matcher that hive/pose_optimisation.py:294, :426, :452 call through cv2.
+
+The rules are stated in include/hive_mi355x.h above ``hive_sift_create`` and restated in numpy float32 in tests/sift_restatement.py.  They are Lowe's SIFT with
+cv2.SIFT.create()'s parameters as recalled from OpenCV 4.x; cv2 cannot be run beside this code, so keypoints and descriptors are not pinned against cv2.  The
+reference matches with FLANN (an approximate randomised KD-tree search); the matcher here returns the exact nearest neighbours and is not pinned against FLANN."""
+import ctypes
+import warnings
+
+import numpy as np
+
+from hive_amd import _lib
+from hive_amd._lib import ptr
+
+NAN = float("nan")
+SIFT_MIN_SIDE = 6  # the doubled picture must reach past the 5-pixel border on both sides
+KEYPOINT_FIELDS = ("x", "y", "size", "angle", "response", "octave")
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def blur_sigmas(n_octave_layers=3, sigma=1.6):
+    """[0] the blur of the doubled base picture, [i] the blur from layer i - 1 to layer i of an octave (float64)."""
+    sig = [np.sqrt(max(sigma * sigma - 4 * 0.5 * 0.5, 0.01))]
+    k = 2.0 ** (1.0 / n_octave_layers)
+    for i in range(1, n_octave_layers + 3):
+        prev = sigma * k ** (i - 1)
+        total = prev * k
+        sig.append(np.sqrt(total * total - prev * prev))
+    return sig
+
+
+def gaussian_taps(sig):
+    """round(8 sig + 1) | 1 taps: exp(-(i - R)^2 / (2 sig^2)) in float64 over their sum, rounded to float32."""
+    n = int(np.rint(8 * sig + 1)) | 1
+    g = np.exp(-(np.arange(n, dtype=np.float64) - n // 2) ** 2 / (2 * sig * sig))
+    return np.ascontiguousarray((g / g.sum()).astype(np.float32))
+
+
+def octave_sizes(h, w):
+    """[(rows, cols)] of the octaves of an h x w picture (octave 0 is the doubled picture)."""
+    count = int(np.rint(np.log(float(2 * min(h, w))) / np.log(2.0) - 2.0)) + 1
+    sizes, rows, cols = [], 2 * h, 2 * w
+    for _ in range(max(count, 1)):
+        if rows < 1 or cols < 1:
+            break
+        sizes.append((rows, cols))
+        rows, cols = rows // 2, cols // 2
+    return sizes
+
+
+class SIFT:
+    """``cv2.SIFT.create(nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma)`` on the GPU.  ``capacity``: the most refined candidates and the most
+    keypoints one picture may have; a picture with more fails the call with an error that names the count (it is never cut).  One object serves any picture
+    size and batch: a native detector per (context, H, W) is made on first use and holds at most ``workspace_bytes`` of pyramids (larger batches run in chunks)."""
+
+    def __init__(self, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6, capacity=4096, ctx=None, workspace_bytes=4 << 30):
+        if not 1 <= int(nOctaveLayers) <= 5:
+            raise ValueError(f"nOctaveLayers: 1 .. 5, got {nOctaveLayers}")
+        if not 1 <= int(capacity) <= 65535:
+            raise ValueError(f"capacity: 1 .. 65535, got {capacity}")
+        if nfeatures < 0 or contrastThreshold < 0 or edgeThreshold <= 0 or sigma <= 0:
+            raise ValueError("nfeatures and contrastThreshold must not be negative, edgeThreshold and sigma must be positive")
+        self.nfeatures, self.nOctaveLayers, self.capacity = int(nfeatures), int(nOctaveLayers), int(capacity)
+        self.contrastThreshold, self.edgeThreshold, self.sigma = float(contrastThreshold), float(edgeThreshold), float(sigma)
+        self.ctx, self.workspace_bytes = ctx, int(workspace_bytes)
+        self.taps = [gaussian_taps(s) for s in blur_sigmas(self.nOctaveLayers, self.sigma)]
+        if max(len(t) for t in self.taps) > 33:
+            raise ValueError(f"sigma = {sigma} with {nOctaveLayers} layers needs a blur of {max(len(t) for t in self.taps)} taps; the kernel holds 33")
+        self._native = {}  # (id(ctx), H, W) -> [ctx, handle, max_images]
+        self._last = None  # (ctx, handle, pictures) of the most recent launch, for the stage readers
+
+    # ---- the native detector ----
+    def _chunk(self, h, w, n):
+        # float32: the doubled base, nOctaveLayers + 3 layers of octaves that sum to at most 4 / 3 of it, 20 words a candidate / keypoint slot
+        per_image = 4 * (4 * h * w) * (1 + -(-(self.nOctaveLayers + 3) * 4 // 3)) + self.capacity * 20 * 4
+        return int(max(1, min(n, self.workspace_bytes // per_image, 8192)))
+
+    def _handle(self, ctx, h, w, images):
+        key = (id(ctx), h, w)
+        entry = self._native.get(key)
+        if entry is not None and entry[2] < images:
+            ctx.check(ctx.lib.hive_sift_destroy(entry[1]))
+            entry = None
+        if entry is None:
+            count = len(self.taps)
+            taps = (ctypes.c_void_p * count)(*(t.ctypes.data for t in self.taps))
+            counts = (ctypes.c_int * count)(*(len(t) for t in self.taps))
+            handle = ctypes.c_void_p()
+            ctx.check(ctx.lib.hive_sift_create(ctx.handle, h, w, images, self.nfeatures, self.nOctaveLayers, self.contrastThreshold, self.edgeThreshold, self.sigma,
+                                               taps, counts, self.capacity, ctypes.byref(handle)))
+            entry = self._native[key] = [ctx, handle, images]
+        return entry[1]
+
+    def close(self):
+        for ctx, handle, _ in self._native.values():
+            if _lib.alive() and getattr(ctx, "handle", None):
+                ctx.lib.hive_sift_destroy(handle)
+        self._native, self._last = {}, None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _context(self, dev):
+        return (self.ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+
+    def detect_device(self, gray, mask=None, ctx=None, out=None, first=0):
+        """The launches alone, nothing synchronises: ``gray`` (and ``mask``) contiguous uint8 device tensors (N, H, W) -> device tensors ``(keypoints float32
+        (N, capacity, 6), descriptors uint8 (N, capacity, 128), counts int32 (N, 3))``; rows past a picture's count are undefined.  ``out``: such a triple of a
+        larger batch, filled from picture ``first`` on.  Hand the counts to ``check_counts`` once they are on the host."""
+        import torch
+        n, h, w = (int(v) for v in gray.shape)
+        if min(h, w) < SIFT_MIN_SIDE:
+            raise ValueError(f"{h} x {w} is smaller than {SIFT_MIN_SIDE} x {SIFT_MIN_SIDE}, the smallest picture SIFT can handle")
+        ctx = ctx or self._context(gray.device)
+        if out is None:
+            out = (torch.empty((n, self.capacity, 6), dtype=torch.float32, device=gray.device),
+                   torch.empty((n, self.capacity, 128), dtype=torch.uint8, device=gray.device), torch.empty((n, 3), dtype=torch.int32, device=gray.device))
+        kps, desc, counts = out
+        chunk = self._chunk(h, w, n)
+        handle = self._handle(ctx, h, w, chunk)
+        for at in range(0, n, chunk):
+            m = min(chunk, n - at)
+            ctx.check(ctx.lib.hive_sift_detect(handle, ptr(gray[at:at + m]), ptr(mask[at:at + m]) if mask is not None else None, m, ptr(kps[first + at:]),
+                                               ptr(desc[first + at:]), ptr(counts[first + at:])))
+            self._last = (ctx, handle, m, h, w, gray.device)
+        return out
+
+    def check_counts(self, counts):
+        """``counts``: host (N, 3).  Raises when a picture had more candidates or keypoints than the capacity."""
+        counts = np.asarray(counts)
+        for i, (cand, raw, _) in enumerate(counts):
+            if max(cand, raw) > self.capacity:
+                what, count = ("refined candidates", cand) if cand > self.capacity else ("keypoints", raw)
+                raise _lib.HiveError(_lib.ERR_INVALID, f"SIFT: picture {i} has {int(count)} {what}, more than the capacity {self.capacity}; make the SIFT with a larger capacity")
+
+    def _pictures(self, gray, mask):
+        import torch
+        batched = len(gray.shape) == 3
+        if len(gray.shape) not in (2, 3):
+            raise ValueError(f"gray pictures are (H, W) or (N, H, W), got {tuple(gray.shape)}")
+        dev = next((a.device for a in (gray, mask) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+
+        def device(a, name):
+            if str(a.dtype).replace("torch.", "") != "uint8":
+                raise ValueError(f"{name}: uint8, got {a.dtype}")
+            if not _is_torch(a):
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore", UserWarning)
+                    a = torch.from_numpy(np.ascontiguousarray(a))
+            a = a.to(dev)
+            return (a if batched else a[None]).contiguous()
+        g = device(gray, "gray")
+        m = None
+        if mask is not None:
+            if tuple(mask.shape) != tuple(gray.shape):
+                raise ValueError(f"mask: shape {tuple(mask.shape)}, the pictures have {tuple(gray.shape)}")
+            m = device(mask, "mask")
+        return g, m, batched
+
+    def detect_and_compute(self, gray, mask=None):
+        """``gray``: one uint8 (H, W) picture or a batch (N, H, W), a numpy array or a device tensor; ``mask`` likewise (a keypoint whose rounded position has
+        mask 0 is dropped).  Returns ``(keypoints, descriptors)``, float32 (K, 6) in the order of ``KEYPOINT_FIELDS`` and uint8 (K, 128), numpy arrays; for a batch
+        a list of such pairs.  The float32 view of the descriptor bytes is what cv2 returns."""
+        g, m, batched = self._pictures(gray, mask)
+        kps, desc, counts = self.detect_device(g, m)
+        counts_h = counts.cpu().numpy()
+        self.check_counts(counts_h)
+        kps_h, desc_h = kps.cpu().numpy(), desc.cpu().numpy()
+        out = [(kps_h[i, :k].copy(), desc_h[i, :k].copy()) for i, k in enumerate(counts_h[:, 2])]
+        return out if batched else out[0]
+
+    # ---- stages of the most recent launch (tests) ----
+    def read_layer(self, octave, layer):
+        """Gaussian layer ``layer`` of octave ``octave`` of the pictures of the most recent launch: a float32 device tensor (N, rows, cols)."""
+        import torch
+        ctx, handle, n, h, w, dev = self._last
+        rows, cols = octave_sizes(h, w)[octave]
+        out = torch.empty((n, rows, cols), dtype=torch.float32, device=dev)
+        ctx.check(ctx.lib.hive_sift_read_layer(handle, octave, layer, n, ptr(out)))
+        return out
+
+    def read_candidates(self):
+        """The refined candidates of the most recent launch in append order: a device tensor (N, capacity, 8) of 32-bit words (int32 view; the first four are
+        float32 bits): x, y, size, response, packed octave, layer, r, c."""
+        import torch
+        ctx, handle, n, _, _, dev = self._last
+        out = torch.empty((n, self.capacity, 8), dtype=torch.int32, device=dev)
+        ctx.check(ctx.lib.hive_sift_read_candidates(handle, n, ptr(out)))
+        return out
+
+
+def knn_match(query, train, ctx=None):
+    """The two nearest ``train`` descriptors of every ``query`` descriptor (uint8 (Q, 128) and (T, 128), numpy arrays or device tensors) by exact squared L2
+    distance, ties to the lower train index: ``(indices int32 (Q, 2), distances float32 (Q, 2))``, of the kind ``query`` is.  With fewer than two train descriptors
+    the missing entries are -1 and inf.  This is the exact answer: not pinned against the reference's approximate FLANN search."""
+    import torch
+    as_numpy = not _is_torch(query)
+    dev = next((a.device for a in (query, train) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+
+    def device(a, name):
+        if str(a.dtype).replace("torch.", "") != "uint8" or len(a.shape) != 2 or a.shape[1] != 128:
+            raise ValueError(f"{name}: uint8 (K, 128) descriptors, got {a.dtype} {tuple(a.shape)}")
+        if not _is_torch(a):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(dev).contiguous()
+    q, t = device(query, "query"), device(train, "train")
+    nq, nt = int(q.shape[0]), int(t.shape[0])
+    idx = torch.full((nq, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((nq, 2), float("inf"), dtype=torch.float32, device=dev)
+    if nq and nt:
+        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx.check(ctx.lib.hive_knn_match(ctx.handle, ptr(q), nq, ptr(t), nt, ptr(idx), ptr(dist)))
+    return (idx.cpu().numpy(), dist.cpu().numpy()) if as_numpy else (idx, dist)
+
+
+def warn_no_score(n_query, n_train, matches, k=2, min_matches=1):
+    """The reference's warnings (compare_image_pair.py:63-87) for a pair without a score; True when one was given."""
+    if n_query == 0 or n_train == 0:
+        warnings.warn("Could not extract any features for at least one image in the pair.")
+    elif n_query < k or n_train < k:
+        warnings.warn(f"Not enough descriptors for k={k:d}, only got {n_query:,d} and {n_train:,d}.")
+    elif matches < min_matches or matches == 0:
+        warnings.warn(f"Not enough matches for `min_matches={min_matches}`, only got {matches}.")
+    else:
+        return False
+    return True
+
+
+def score_pairs(sift, features, query_first, train_first, pairs, ctx, ratio_threshold=0.7, min_matches=1):
+    """MIFD of ``pairs`` pairs of pictures of one ``SIFT.detect_device`` result, picture ``query_first + p`` against ``train_first + p``: device tensors
+    ``(scores float64 (pairs,), matches int32 (pairs,), indices int32 (pairs, capacity, 2), distances float32 (pairs, capacity, 2))``.  Nothing synchronises."""
+    import torch
+    kps, desc, counts = features
+    dev, cap = kps.device, sift.capacity
+    scores = torch.empty(pairs, dtype=torch.float64, device=dev)
+    matches = torch.empty(pairs, dtype=torch.int32, device=dev)
+    idx = torch.empty((pairs, cap, 2), dtype=torch.int32, device=dev)
+    dist = torch.empty((pairs, cap, 2), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.hive_mifd(ctx.handle, ptr(kps), ptr(desc), ptr(counts), cap, query_first, train_first, pairs, float(ratio_threshold), int(min_matches), ptr(idx),
+                                ptr(dist), ptr(scores), ptr(matches)))
+    return scores, matches, idx, dist
+
+
+def mifd(label, output, ratio_threshold=0.7, k=2, min_matches=1, log_residual=False, sift=None, return_matches=False):
+    """``mifd`` of compare_image_pair.py:44-97 on two gray uint8 pictures (numpy arrays or device tensors): SIFT on both, the two nearest ``output`` descriptors
+    of every ``label`` descriptor, Lowe's ratio test, the mean distance between the matched positions; nan, with the reference's warnings, with fewer than ``k``
+    descriptors on a side or fewer than ``min_matches`` matches.  ``k`` must be 2 (ValueError otherwise).  ``sift``: a ``SIFT`` to use (default parameters
+    otherwise).  ``log_residual``: the distances are taken between the float32 log10 of the positions; that variant is finished on the host from the device's
+    matches.  ``return_matches``: ``(score, matches)``."""
+    import torch
+    if k != 2:
+        raise ValueError(f"mifd: k = 2 only (the ratio test needs exactly the two nearest), got {k}")
+    own = sift is None
+    sift = sift or SIFT()
+    try:
+        a, _, _ = sift._pictures(label, None)
+        b, _, _ = sift._pictures(output, None)
+        if a.shape[0] != 1 or b.shape[0] != 1:
+            raise ValueError("mifd: one (H, W) picture on each side")
+        dev, cap = a.device, sift.capacity
+        ctx = sift._context(dev)
+        if min(a.shape[1:]) < SIFT_MIN_SIDE or min(b.shape[1:]) < SIFT_MIN_SIDE:
+            warnings.warn("Could not extract any features for at least one image in the pair.")
+            return (NAN, 0) if return_matches else NAN
+        features = (torch.empty((2, cap, 6), dtype=torch.float32, device=dev), torch.empty((2, cap, 128), dtype=torch.uint8, device=dev),
+                    torch.empty((2, 3), dtype=torch.int32, device=dev))
+        if a.shape == b.shape:
+            sift.detect_device(torch.cat([a, b]), None, ctx, out=features)
+        else:
+            sift.detect_device(a, None, ctx, out=features, first=0)
+            sift.detect_device(b, None, ctx, out=features, first=1)
+        scores, matches, idx, dist = score_pairs(sift, features, 0, 1, 1, ctx, ratio_threshold, min_matches)
+        counts = features[2].cpu().numpy()
+        sift.check_counts(counts)
+        nq, nt = int(counts[0, 2]), int(counts[1, 2])
+        kept = int(matches.cpu().numpy()[0]) if nq >= k and nt >= k else 0
+        if warn_no_score(nq, nt, kept, k, min_matches):
+            score = NAN
+        elif log_residual:
+            kps = features[0].cpu().numpy()
+            idx_h, dist_h = idx[0, :nq].cpu().numpy(), dist[0, :nq].cpu().numpy()
+            keep = dist_h[:, 0] < np.float32(ratio_threshold) * dist_h[:, 1]
+            with np.errstate(all="ignore"):
+                res = (np.log10(kps[0, :nq][keep][:, :2]) - np.log10(kps[1][idx_h[keep, 0]][:, :2])).astype(np.float64)
+            total = 0.0
+            for dx, dy in res:
+                total = total + np.sqrt(dx * dx + dy * dy)
+            score = float(total / kept)
+        else:
+            score = float(scores.cpu().numpy()[0])
+        return (score, kept) if return_matches else score
+    finally:
+        if own:
+            sift.close()

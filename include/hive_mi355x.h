@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 7
+#define HIVE_ABI_VERSION 8
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -590,7 +590,7 @@ int hive_icp_step(hive_ctx *ctx, int H, int W, const float K[9], const float *d_
  *              divided by 4, avg_pool2d's count_include_pad=True).  The score is the mean over the channels of the product of value ^ weight.  The smaller
  *              side must exceed 160 (the original asserts).  Sums over a map: a workgroup owns 16 x 32 values (p = 32 r + c, thread t adds p = t, t + 256) and
  *              reduces as above; hive_similarity_finish then gives the mean.
- * LPIPS is restated below, above hive_lpips_create; MIFD (SIFT) is not restated.  Nothing synchronises; every call is ordered on the context's stream. */
+ * LPIPS is restated below, above hive_lpips_create; MIFD (SIFT keypoints, the exact matcher) below that, above hive_sift_create.  Nothing synchronises; every call is ordered on the context's stream. */
 /* compare_images' SSIM and PSNR sums (compare_image_pair.py:120-124) for N pairs and `variants` (1: plain; 2: plain, then masked) at once.  H, W >= 7, N >= 1,
  * variants * N <= 65535.  d_partials f64 [variants][N][ceil((H - 6) / 32) * ceil((W - 6) / 32)]: the tile sums of S, for hive_similarity_finish with the divisor
  * (H - 6)(W - 6).  d_sse i64 [variants][N]: zeroed here, then the sum of squared gray differences.  Optional (NULL = not stored): d_map f64 [variants][N][H - 6][W - 6],
@@ -651,6 +651,88 @@ int hive_lpips_layer(hive_lpips *net, int layer, const float *d_in, int N, int h
  * d_dist[l] f64 [variants][N][h_l][w_l], the maps d.  Any N: the pairs are run in chunks over one workspace. */
 int hive_lpips_forward(hive_lpips *net, const uint8_t *d_ref_u8, const uint8_t *d_est_u8, int N, int H, int W, int variants, double *d_scores,
                        double *d_layer_scores, float *const d_features[5], double *const d_dist[5]);
+
+/* ---- SIFT, the exact matcher and MIFD: the fourth score of a render -- mifd() of scripts/compare_image_pair.py:44-97 (cv2.SIFT.create(), a 2-nearest-neighbour
+ * descriptor match, Lowe's ratio test, the mean distance between matched keypoint positions); the detector is also what hive/pose_optimisation.py:294, :426, :452
+ * call.  cv2 is absent: the rules below are Lowe's SIFT with the parameters and rules of cv2.SIFT.create() as recalled from OpenCV 4.x, and the result is not
+ * pinned against cv2.  The reference matches with FLANN, an approximate randomised KD-tree search; the matcher here is the exact answer and is not pinned against
+ * FLANN.  tests/sift_restatement.py states the same rules in numpy float32.  All arithmetic is float32 with one rounding per operation (no fused multiply-add),
+ * sqrt and / correctly rounded, sums evaluated left to right; rint is round-half-even.
+ *   exp        E(x), x clamped to >= -87: n = rint(x * f(1.4426950408889634)); r = x - n * 0.693145751953125; r = r - n * f(1.42860682030941723212e-6);
+ *              p = f(1/5040); p = p r + f(1/720); p = p r + f(1/120); p = p r + f(1/24); p = p r + f(1/6); p = p r + 0.5; p = p r + 1; p = p r + 1;
+ *              E = ldexp(p, n).  f(.) rounds a float64 constant to float32.  Relative error below 2^-21 for -87 <= x <= 10.
+ *   atan2      A(y, x) in degrees (cv2's fastAtan2 form): ax = |x|, ay = |y|, e = f(2.220446049250313e-16), p1 = f(0.9997878412794807 * 57.29577951308232),
+ *              p3 = f(-0.3258083974640975 * 57.29577951308232), p5 = f(0.1555786518463281 * 57.29577951308232), p7 = f(-0.04432655554792128 * 57.29577951308232);
+ *              if ax >= ay: c = ay / (ax + e), a = (((p7 c^2 + p5) c^2 + p3) c^2 + p1) c; else c = ax / (ay + e), a = 90 - (that polynomial);
+ *              x < 0: a = 180 - a; y < 0: a = 360 - a.  Within 0.3 degrees of atan2 (cv2's stated accuracy; the polynomial's own error is near 0.01).
+ *   sin, cos   of a degrees in [0, 360]: q = rint(a * f(1/90)); t = (a - q * 90) * f(pi / 180); u = t t;
+ *              s = ((((f(1/362880) u + f(-1/5040)) u + f(1/120)) u + f(-1/6)) u + 1) t;  c = ((((f(-1/3628800) u + f(1/40320)) u + f(-1/720)) u + f(1/24)) u - 0.5) u + 1;
+ *              (cos, sin) = (c, s), (-s, c), (-c, -s), (s, -c) for q mod 4 = 0, 1, 2, 3.
+ *   base       gray u8 -> float32; x2 bilinear with INTER_LINEAR's geometry, source coordinate (d + 0.5) / 2 - 0.5, edge samples replicated (the weights are 0.25
+ *              and 0.75: exact); then a blur by sqrt(max(sigma^2 - 4 * 0.5^2, 0.01)).  The first octave is -1.
+ *   octaves    round(log2(min(2H, 2W)) - 2) + 1 of them, each nOctaveLayers + 3 layers; layer i is layer i - 1 blurred by sig[i] = sqrt((sigma k^i)^2 -
+ *              (sigma k^(i-1))^2), k = 2^(1 / nOctaveLayers); the next octave's layer 0 is layer nOctaveLayers at every second row and column, (rows / 2, cols / 2)
+ *              rounded down.
+ *   blur       separable, border reflect-101 folded as often as the radius needs (a 3 x 4 octave meets 25 taps); round(8 sig + 1) | 1 taps, exp(-(i - R)^2 /
+ *              (2 sig^2)) in float64 over their sum, rounded to float32, GIVEN BY THE CALLER (as the MS-SSIM window is) so that one set of bits serves the device
+ *              and a restatement; at most 33.  Along the row first, then along the column: out = t[0] v[0], then + t[k] v[k] for k = 1 .. ascending.
+ *   extrema    DoG i = layer i + 1 - layer i.  threshold = floor(0.5 * contrastThreshold / nOctaveLayers * 255) (contrastThreshold as float32); border 5; a
+ *              candidate of DoG 1 .. nOctaveLayers has |v| > threshold and is >= all 26 neighbours (v > 0) or <= all of them (v < 0).
+ *   refine     up to 5 steps: with s = f(1/255), first derivatives (difference) * (s * 0.5), second (sum - 2 v) * s, mixed (a - b - c + d) * (s * 0.25) in cv2's
+ *              operand order; solve H X = dD by elimination on the 3 x 4 matrix with partial pivoting (largest |a| in the column, lowest row on a tie; a zero
+ *              pivot rejects), back substitution X2 = a23 / a22, X1 = (a13 - a12 X2) / a11, X0 = (a03 - a01 X1 - a02 X2) / a00; offset = -X.  All |offset| < 0.5
+ *              ends the loop; an offset that is not <= 2^29 in magnitude rejects; else c, r, layer move by rint(offset) and leaving layers 1 .. nOctaveLayers or
+ *              the border rejects; five steps without the end reject.  contr = v s + (dD . offset) * 0.5 (the dot as d0 xc + d1 xr + d2 xi); reject on |contr| *
+ *              nOctaveLayers < contrastThreshold, on det = dxx dyy - dxy dxy <= 0, on tr^2 edge >= (edge + 1)(edge + 1) det.  Then x = (c + xc) 2^o, y likewise,
+ *              octave = o + (layer << 8) + (rint((xi + 0.5) * 255) << 16), size = sigma * E(((layer + xi) / nOctaveLayers) * f(ln 2)) * 2^o * 2, response = |contr|.
+ *   mask       a candidate is dropped when mask[(int)(y * 0.5 + 0.5)][(int)(x * 0.5 + 0.5)] (clamped into the picture) is 0: before orientation.
+ *   nfeatures  > 0: before orientation a candidate stays when fewer than nfeatures candidates of its picture have a larger response (the nfeatures largest and
+ *              everything equal to the last of them).
+ *   orient     scl = size * 0.5 / 2^o; radius rint(4.5 scl); weight E((i^2 + j^2) * (-1 / (2 (1.5 scl)^2))); samples p = (i + radius)(2 radius + 1) + (j + radius)
+ *              of the window whose pixel lies strictly inside the layer: dx = right - left, dy = up - down, bin = rint(f(0.1) * A(dy, dx)) mod 36, value weight *
+ *              sqrt(dx dx + dy dy).  Lane p mod 64 adds its samples in ascending p to a private histogram; bin totals are 0 + lane 0 + lane 1 + ... + lane 63.
+ *              Smoothed h[b] = (t[b-2] + t[b+2]) / 16 + (t[b-1] + t[b+1]) * 0.25 + t[b] * 0.375.  Every b with h[b] > both neighbours and >= 0.8 max h gives a
+ *              keypoint: bin = b + 0.5 (h[l] - h[r]) / (h[l] - 2 h[b] + h[r]) wrapped into [0, 36), angle = 360 - 10 bin, 0 when within FLT_EPSILON of 360.
+ *   keypoint   (x * 0.5, y * 0.5, size * 0.5, angle, response, octave) with the octave byte (o - 1) & 255: six float32 (the packed octave is below 2^24).  Sorted by
+ *              that tuple, exact duplicates removed.
+ *   descriptor 4 x 4 x 8, on the keypoint's layer at its octave: point rint(x 2^-octave), rint(y 2^-octave); ori = 360 - angle (0 when within FLT_EPSILON of 360);
+ *              hist_width = 3 (size 2^-octave 0.5); radius = min(rint(hist_width * f(sqrt 2) * 5 * 0.5), (int)sqrt(rows^2 + cols^2)); cos and sin of ori divided by
+ *              hist_width; per window sample p as above: c_rot = j cos - i sin, r_rot = j sin + i cos, rbin = r_rot + 2 - 0.5, cbin likewise, kept when both lie
+ *              in (-1, 4) and the pixel strictly inside; weight E((c_rot^2 + r_rot^2) * (-1 / 8)); obin = (A(dy, dx) - ori) * f(8 / 360); trilinear split in cv2's
+ *              order (v_r1 = mag rbin, v_r0 = mag - v_r1, ...) into the eight bins (r0 + 0/1, c0 + 0/1, o0 / o0 + 1 mod 8), in the order 000 001 010 011 100 101 110
+ *              111; rows and columns outside 0 .. 3 take nothing.  Lane-private histograms and the lane-order sum as for the orientation.  Then nrm2 = sum of
+ *              squares ascending; clip at sqrt(nrm2) * 0.2; nrm2 again; scale 512 / max(sqrt(nrm2), FLT_EPSILON); rint, saturated to 0 .. 255, stored as bytes.
+ *   knn        squared L2 distance of byte descriptors: an exact integer (at most 128 * 255^2 < 2^24); the two nearest, a tie to the lower train index; distance
+ *              = float32 sqrt of the integer; index -1 and +inf where the train set has fewer than two.
+ *   MIFD       a query q survives when d0 < ratio * d1 in float32; its residual is (x_q - x_t, y_q - y_t) in float32, its length sqrt(dx dx + dy dy) in float64;
+ *              the score is the float64 sum over the survivors in query order divided by their number; nan with fewer than 2 descriptors on either side or fewer
+ *              than min_matches (or no) survivors.
+ * Every stage has the same bits on every run, in every batch and at every place in it: no floating-point atomic exists; the appends are integer atomics and the
+ * sort removes their order.  Nothing synchronises; every call is ordered on the context's stream.  A picture with more candidates or keypoints than `capacity` is
+ * never cut silently: d_counts holds the true counts, and the caller fails the call when one exceeds the capacity (hive_amd.features does, naming the count). */
+typedef struct hive_sift hive_sift;
+/* A detector for pictures of H x W (>= 6 x 6), up to max_images (<= 8192) a call, `capacity` (<= 65535) candidates and keypoints a picture.  nOctaveLayers 1 .. 5.
+ * taps[i] / tap_counts[i], i = 0 .. nOctaveLayers + 2: host float32 blur taps, [0] the base blur, [i] the blur from layer i - 1 to layer i (rule `blur`). */
+int hive_sift_create(hive_ctx *ctx, int H, int W, int max_images, int nfeatures, int n_octave_layers, double contrast_threshold, double edge_threshold, double sigma,
+                     const float *const *taps, const int *tap_counts, int capacity, hive_sift **out);
+/* Frees the detector (after the stream has drained). */
+int hive_sift_destroy(hive_sift *sift);
+/* d_gray u8 [N][H][W]; d_mask u8 [N][H][W] or NULL -> d_keypoints f32 [N][capacity][6], d_descriptors u8 [N][capacity][128] (4-byte aligned), d_counts i32 [N][3]:
+ * refined candidates, keypoints before the duplicates left, keypoints.  Rows past a count are undefined.  1 <= N <= max_images. */
+int hive_sift_detect(hive_sift *sift, const uint8_t *d_gray, const uint8_t *d_mask, int N, float *d_keypoints, uint8_t *d_descriptors, int32_t *d_counts);
+/* Stages of the most recent hive_sift_detect, for the tests: a Gaussian layer f32 [N][rows][cols] of an octave (octave 0 is 2H x 2W, each next one halved, rounded
+ * down); the refined candidates [N][capacity][8] 32-bit words in append order: x, y, size, response (f32, before the halving), packed octave, layer, r, c (i32). */
+int hive_sift_read_layer(hive_sift *sift, int octave, int layer, int N, float *d_out);
+int hive_sift_read_candidates(hive_sift *sift, int N, void *d_out);
+/* For tools/probe_sift.py, which times the stages by difference: hive_sift_detect stops after the pyramid (stage 1: the counts stay 0) or after the sorted
+ * keypoints (stage 2: no descriptors); 0, the default, runs everything. */
+int hive_sift_set_last_stage(hive_sift *sift, int stage);
+/* The two nearest of T train descriptors for each of Q query descriptors (u8 [.][128], 4-byte aligned): d_indices i32 [Q][2], d_distances f32 [Q][2] (rule `knn`). */
+int hive_knn_match(hive_ctx *ctx, const uint8_t *d_query, int Q, const uint8_t *d_train, int T, int32_t *d_indices, float *d_distances);
+/* MIFD of `pairs` pairs from hive_sift_detect's outputs over pictures [.][capacity]: pair p matches picture query_first + p against picture train_first + p.
+ * d_indices i32 and d_distances f32 [pairs][capacity][2] receive the matches, d_scores f64 [pairs] the score, d_matches i32 [pairs] the survivors. */
+int hive_mifd(hive_ctx *ctx, const float *d_keypoints, const uint8_t *d_descriptors, const int32_t *d_counts, int capacity, int query_first, int train_first, int pairs,
+              float ratio_threshold, int min_matches, int32_t *d_indices, float *d_distances, double *d_scores, int32_t *d_matches);
 
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
