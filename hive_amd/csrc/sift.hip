@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "hive_internal.hpp"
+#include "knn_core.hpp"
 
 namespace {
 
@@ -38,7 +39,6 @@ constexpr int SF_ORI_BINS = 36;
 constexpr int SF_D = 4, SF_N = 8, SF_DESC = SF_D * SF_D * SF_N;
 constexpr int SF_CAND_WORDS = 8;  // x, y, size, response (f32); packed octave, layer, r, c (i32)
 constexpr int SF_KP_WORDS = 6;    // x, y, size, angle, response, octave (all f32)
-constexpr int KNN_TILE = 64;
 
 struct SfTaps {
     float g[SF_MAX_TAPS];
@@ -479,49 +479,18 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SfPyramid pyr, const 
     for (int k = 0; k < SF_DESC; ++k) out[k] = (uint8_t)fminf(fmaxf(rintf(dst[k] * s), 0.0f), 255.0f);
 }
 
-// sum over the four bytes of a[i] * b[i], added to acc
-__device__ __forceinline__ unsigned knn_dot4(unsigned a, unsigned b, unsigned acc) {
-#if __has_builtin(__builtin_amdgcn_udot4)
-    return __builtin_amdgcn_udot4(a, b, acc, false);
-#else
-    return acc + (a & 255u) * (b & 255u) + ((a >> 8) & 255u) * ((b >> 8) & 255u) + ((a >> 16) & 255u) * ((b >> 16) & 255u) + (a >> 24) * (b >> 24);
-#endif
-}
-
 // The two nearest train descriptors of every query descriptor; one thread per query, grid (ceil(max Q / 64), pairs).  Pair p: queries of picture q_base + p,
 // trains of picture t_base + p, `stride` descriptors a picture; their numbers from counts[3 * picture + 2] when counts is given, else Q and T.
 __global__ __launch_bounds__(KNN_TILE) void knn_kernel(const uint8_t *__restrict__ query, const uint8_t *__restrict__ train, const unsigned *__restrict__ counts,
                                                        int q_base, int t_base, int stride, int Q, int T, int32_t *__restrict__ idx, float *__restrict__ dist) {
-    __shared__ unsigned tile[KNN_TILE][SF_DESC / 4 + 1];
-    const int p = blockIdx.y, t = threadIdx.x, q = blockIdx.x * KNN_TILE + t;
+    __shared__ unsigned tile[KNN_TILE][KNN_WORDS + 1];
+    const int p = blockIdx.y, q = blockIdx.x * KNN_TILE + threadIdx.x;
     if (counts) Q = (int)min(counts[3 * (q_base + p) + 2], (unsigned)stride), T = (int)min(counts[3 * (t_base + p) + 2], (unsigned)stride);
     if ((int)blockIdx.x * KNN_TILE >= Q) return;
     const unsigned *qd = (const unsigned *)(query + (size_t)(q_base + p) * stride * SF_DESC), *td = (const unsigned *)(train + (size_t)(t_base + p) * stride * SF_DESC);
-    unsigned mine[SF_DESC / 4], nq = 0;
-#pragma unroll
-    for (int k = 0; k < SF_DESC / 4; ++k) {
-        mine[k] = q < Q ? qd[(size_t)q * (SF_DESC / 4) + k] : 0u;
-        nq = knn_dot4(mine[k], mine[k], nq);
-    }
-    unsigned b0 = 0xffffffffu, b1 = 0xffffffffu;
-    int i0 = -1, i1 = -1;
-    for (int t0 = 0; t0 < T; t0 += KNN_TILE) {
-        const int rows = min(KNN_TILE, T - t0);
-        __syncthreads();
-        for (int e = t; e < rows * (SF_DESC / 4); e += KNN_TILE) tile[e / (SF_DESC / 4)][e % (SF_DESC / 4)] = td[(size_t)t0 * (SF_DESC / 4) + e];
-        __syncthreads();
-        for (int d = 0; d < rows; ++d) {
-            unsigned dot = 0, nt = 0;
-#pragma unroll
-            for (int k = 0; k < SF_DESC / 4; ++k) {
-                const unsigned v = tile[d][k];
-                dot = knn_dot4(mine[k], v, dot), nt = knn_dot4(v, v, nt);
-            }
-            const unsigned d2 = nq + nt - 2u * dot;  // the exact squared distance, at most 128 * 255^2
-            if (d2 < b0) b1 = b0, i1 = i0, b0 = d2, i0 = t0 + d;
-            else if (d2 < b1) b1 = d2, i1 = t0 + d;
-        }
-    }
+    unsigned b0, b1;
+    int i0, i1;
+    knn_two_nearest(qd, td, Q, T, q, tile, b0, b1, i0, i1);  // knn_core.hpp
     if (q >= Q) return;
     const size_t at = ((size_t)p * stride + q) * 2;
     idx[at] = i0, idx[at + 1] = i1;

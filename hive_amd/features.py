@@ -3,7 +3,10 @@ scripts/compare_image_pair.py:44-97, and the detector / matcher that hive/pose_o
 
 The rules are stated in include/hive_mi355x.h above ``hive_sift_create`` and restated in numpy float32 in tests/sift_restatement.py.  They are Lowe's SIFT with
 cv2.SIFT.create()'s parameters as recalled from OpenCV 4.x; cv2 cannot be run beside this code, so keypoints and descriptors are not pinned against cv2.  The
-reference matches with FLANN (an approximate randomised KD-tree search); the matcher here returns the exact nearest neighbours and is not pinned against FLANN."""
+reference matches with FLANN (an approximate randomised KD-tree search); the matcher here returns the exact nearest neighbours and is not pinned against FLANN.
+
+``match_pairs``, ``ransac_homography`` / ``find_homography`` and ``compact_pairs`` (csrc/pairs.hip) are the stages of the reference's ``FeatureExtractor`` behind the
+detector (hive/pose_optimisation.py:437-578); the homography RANSAC is a stated rule of its own, not pinned against cv2's randomised USAC_MAGSAC."""
 import ctypes
 import warnings
 
@@ -298,3 +301,117 @@ def mifd(label, output, ratio_threshold=0.7, k=2, min_matches=1, log_residual=Fa
     finally:
         if own:
             sift.close()
+
+
+# ---- feature pairs for pose optimisation: the pair matcher, its filter and the homography RANSAC (csrc/pairs.hip) ----
+ROW_WORDS = 8  # a survivor: x_i, y_i, x_j, y_j, depth_i, depth_j (float32), query index, train index (int32 bits)
+
+
+def match_pairs(features, pairs, depth, ratio=0.7, min_features=2, return_table=False, ctx=None):
+    """The stage before the RANSAC of the reference's ``FeatureExtractor`` (hive/pose_optimisation.py:449-455, :518-539) for a list of picture pairs of one
+    ``SIFT.detect_device`` result: the exact two nearest ``pairs[p][1]`` descriptors of every ``pairs[p][0]`` descriptor, then the filter -- both pictures have
+    ``max(min_features, 2)`` keypoints, ``not float(d0) > ratio * float(d1)`` in float64, and the depth at both rounded keypoint positions is not 0 -- with the
+    survivors kept in query order.  ``features``: the device triple; ``pairs``: (P, 2) picture indices, a list, an array or an int32 device tensor; ``depth``:
+    float32 device tensor (N, H, W).  Returns device tensors ``(rows float32 (P, capacity, 8), counts int32 (P, 2))``: a row is x_i, y_i, x_j, y_j, depth_i,
+    depth_j and, as int32 bits, the query and the train index; ``counts[p]`` the ratio survivors and the survivors (rows past them are undefined).  With
+    ``return_table`` also ``(indices int32, distances float32)`` (P, capacity, 2), the raw 2-NN table.  Nothing synchronises.  The matcher is the exact answer:
+    not pinned against the reference's approximate FLANN search."""
+    import torch
+    kps, desc, counts = features
+    dev, cap, n = kps.device, int(kps.shape[1]), int(kps.shape[0])
+    if not _is_torch(pairs):
+        host = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        if len(host) and (host.min() < 0 or host.max() >= n):
+            raise ValueError(f"pairs name pictures {int(host.min())} .. {int(host.max())}; the features hold {n}")
+        pairs = torch.from_numpy(host.astype(np.int32)).to(dev)
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs: int32 (P, 2), got {pairs.dtype} {tuple(pairs.shape)}")
+    if depth.dtype != torch.float32 or depth.dim() != 3 or int(depth.shape[0]) != n:
+        raise ValueError(f"depth: float32 (N, H, W) with N = {n}, got {depth.dtype} {tuple(depth.shape)}")
+    pairs, depth, p = pairs.contiguous(), depth.contiguous(), int(pairs.shape[0])
+    rows = torch.empty((p, cap, ROW_WORDS), dtype=torch.float32, device=dev)
+    pair_counts = torch.zeros((p, 2), dtype=torch.int32, device=dev)
+    idx = torch.empty((p, cap, 2), dtype=torch.int32, device=dev) if return_table else None
+    dist = torch.empty((p, cap, 2), dtype=torch.float32, device=dev) if return_table else None
+    if p:
+        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx.check(ctx.lib.hive_pairs_match(ctx.handle, ptr(kps), ptr(desc), ptr(counts), cap, n, ptr(pairs), p, ptr(depth), int(depth.shape[1]), int(depth.shape[2]),
+                                           float(ratio), int(min_features), ptr(rows), ptr(pair_counts), ptr(idx), ptr(dist)))
+    return (rows, pair_counts, idx, dist) if return_table else (rows, pair_counts)
+
+
+def ransac_homography(rows, counts, keys, threshold=3.0, trials=2000, seed=0, min_count=0, ctx=None):
+    """The homography RANSAC of include/hive_mi355x.h (rules ``normalise`` .. ``H``) for P pairs at once.  ``rows``: float32 device tensor (P, stride, W >= 4)
+    whose first four words are x_i, y_i, x_j, y_j (``match_pairs``'s rows, or plain (P, stride, 4) points); ``counts``: int32 device tensor (P,), or a column
+    such as ``match_pairs``'s ``counts[:, 1]``; ``keys``: (P, 2) the frame pairs that seed the draws.  Returns device tensors ``(H float64 (P, 3, 3), mask uint8
+    (P, stride), result int32 (P, 3))``: per pair the winning trial (-1 without a model, -2 for a count outside 0 .. stride), the winner's count and the final
+    count; a pair with fewer than ``max(min_count, 4)`` correspondences has no model.  A function of its inputs alone: all ``trials`` trials run.  It stands where the reference calls ``cv2.findHomography(..., cv2.USAC_MAGSAC)``
+    (:562) and is not pinned against cv2.  Nothing synchronises."""
+    import torch
+    if rows.dtype != torch.float32 or rows.dim() != 3 or int(rows.shape[2]) < 4 or not rows.is_contiguous():
+        raise ValueError(f"rows: contiguous float32 (P, stride, >= 4), got {rows.dtype} {tuple(rows.shape)}")
+    dev, p, stride, words = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(rows.shape[2])
+    if counts.dtype != torch.int32 or counts.dim() != 1 or int(counts.shape[0]) != p:
+        raise ValueError(f"counts: int32 (P,) with P = {p}, got {counts.dtype} {tuple(counts.shape)}")
+    if not _is_torch(keys):
+        keys = torch.from_numpy(np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1, 2).astype(np.int32))).to(dev)
+    if keys.dtype != torch.int32 or tuple(keys.shape) != (p, 2):
+        raise ValueError(f"keys: int32 (P, 2) with P = {p}, got {keys.dtype} {tuple(keys.shape)}")
+    keys = keys.contiguous()
+    H = torch.empty((p, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((p, max(stride, 1)), dtype=torch.uint8, device=dev)[:, :stride]
+    result = torch.empty((p, 3), dtype=torch.int32, device=dev)
+    if p and stride:
+        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx.check(ctx.lib.hive_ransac_homography(ctx.handle, ptr(rows), words, ptr(counts), int(counts.stride(0)), ptr(keys), p, stride, float(threshold), int(trials),
+                                                 int(seed) & 0xFFFFFFFF, int(min_count), ptr(H), ptr(mask), ptr(result)))
+    elif p:
+        H.fill_(NAN)
+        result.copy_(torch.tensor([-1, 0, 0], dtype=torch.int32, device=dev))
+    return H, mask, result
+
+
+def find_homography(points_i, points_j, threshold=3.0, trials=2000, seed=0, pair_key=(0, 0), return_stats=False, ctx=None):
+    """The part of ``cv2.findHomography(points_i, points_j, cv2.USAC_MAGSAC)`` (hive/pose_optimisation.py:562) for one pair: (M, 2) points, numpy arrays or
+    device tensors -> ``(H, mask)``, H float64 (3, 3) with h33 = 1 mapping ``points_i`` onto ``points_j`` (None without a model: fewer than four points, all
+    points of a side equal, or every sample degenerate) and the inlier mask uint8 (M,), of the kind ``points_i`` is.  ``threshold`` in pixels of ``points_j`` and
+    ``trials`` are cv2's defaults (ransacReprojThreshold 3, maxIters 2000, from recall).  The draws depend on ``seed`` and ``pair_key`` alone, so the result is a
+    function of the arguments.  ``return_stats``: also ``(winning trial, the winner's count, the final count)``.  Not pinned against cv2: USAC_MAGSAC is randomised."""
+    import torch
+    as_numpy = not _is_torch(points_i)
+    dev = next((a.device for a in (points_i, points_j) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+
+    def device(a, name):
+        if not _is_torch(a):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 2)))
+        if a.dim() != 2 or a.shape[1] != 2:
+            raise ValueError(f"{name}: (M, 2) points, got {tuple(a.shape)}")
+        return a.to(dev, torch.float32)
+    a, b = device(points_i, "points_i"), device(points_j, "points_j")
+    if a.shape != b.shape:
+        raise ValueError(f"points_i {tuple(a.shape)} and points_j {tuple(b.shape)} differ")
+    m = int(a.shape[0])
+    rows = torch.cat([a, b], dim=1).reshape(1, m, 4).contiguous()
+    H, mask, result = ransac_homography(rows, torch.tensor([m], dtype=torch.int32, device=dev), [pair_key], threshold, trials, seed, ctx=ctx)
+    stats = tuple(int(v) for v in result[0].cpu().numpy())
+    found = stats[0] >= 0
+    if as_numpy:
+        out = (H[0].cpu().numpy() if found else None, mask[0].cpu().numpy())
+    else:
+        out = (H[0] if found else None, mask[0])
+    return out + (stats,) if return_stats else out
+
+
+def compact_pairs(rows, counts, mask, result, min_features, ctx=None):
+    """The second compaction (:465-468): the inlier rows of every pair with ``min_features`` survivors and ``min_features`` inliers, pair after pair, inliers in
+    row order.  Device tensors ``(out float32 (P * stride, 8), kept int32 (P,), offsets int64 (P + 1,))``: ``out[offsets[p]:offsets[p + 1]]`` are pair p's rows,
+    ``kept[p]`` their number (0: the pair is dropped), ``offsets[P]`` all rows.  Nothing synchronises."""
+    import torch
+    dev, p, stride = rows.device, int(rows.shape[0]), int(rows.shape[1])
+    out = torch.empty((p * stride, ROW_WORDS), dtype=torch.float32, device=dev)
+    kept = torch.zeros(p, dtype=torch.int32, device=dev)
+    offsets = torch.zeros(p + 1, dtype=torch.int64, device=dev)
+    if p:
+        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx.check(ctx.lib.hive_pairs_compact(ctx.handle, ptr(rows), ptr(counts), ptr(mask), ptr(result), p, stride, int(min_features), ptr(out), ptr(kept), ptr(offsets)))
+    return out, kept, offsets

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HIVE_ABI_VERSION 8
+#define HIVE_ABI_VERSION 9
 
 typedef enum hive_status {
     HIVE_OK = 0,
@@ -733,6 +733,56 @@ int hive_knn_match(hive_ctx *ctx, const uint8_t *d_query, int Q, const uint8_t *
  * d_indices i32 and d_distances f32 [pairs][capacity][2] receive the matches, d_scores f64 [pairs] the score, d_matches i32 [pairs] the survivors. */
 int hive_mifd(hive_ctx *ctx, const float *d_keypoints, const uint8_t *d_descriptors, const int32_t *d_counts, int capacity, int query_first, int train_first, int pairs,
               float ratio_threshold, int min_matches, int32_t *d_indices, float *d_distances, double *d_scores, int32_t *d_matches);
+
+/* ---- Feature pairs for pose optimisation: FeatureExtractor of hive/pose_optimisation.py:437-578 behind hive_sift_detect -- the 2-nearest-neighbour match of an
+ * arbitrary list of picture pairs, the ratio-and-depth filter (:518-539), a homography RANSAC where the reference calls cv2.findHomography(..., cv2.USAC_MAGSAC)
+ * (:562) and the compaction by its inlier mask.  cv2 is absent and USAC_MAGSAC is randomised: the RANSAC below is an exact rule of its own and is not pinned
+ * against cv2 (as the keypoints are not pinned against cv2's SIFT and the matcher is not pinned against FLANN).  tests/ransac_restatement.py states the same
+ * rules in numpy.  The RANSAC's arithmetic is float64 with one rounding per operation (no fused multiply-add), sqrt and / correctly rounded; parentheses below
+ * give the order.
+ *   match      rule `knn` above between picture pairs[p][0] (queries) and picture pairs[p][1] (trains).
+ *   filter     a pair whose pictures do not both have max(min_features, 2) keypoints has no rows.  Query q survives when NOT (double) d0 > ratio * (double) d1
+ *              (the float32 distances widened, the product in float64: the reference's Python arithmetic, not MIFD's float32 <), and depth_i[r(y_q)][r(x_q)] != 0
+ *              and depth_j[r(y_t)][r(x_t)] != 0, r(v) = rint(v) on the float32 coordinate (half-even) clamped into the picture.  Survivors keep the order of q:
+ *              a row is x_q, y_q, x_t, y_t, depth_i, depth_j (float32), q, t (int32).  Counts per pair: ratio survivors, survivors.
+ *   M < 4      M correspondences (x, y) -> (u, v) a pair, float32 widened.  M < 4: no model (mask 0, H NaN, winning trial -1, counts 0).  A count outside
+ *              0 .. stride is refused, never cut: no model, winning trial -2.
+ *   lane sum   L(v) over items k = 0 .. M - 1: lane l = 0 .. 63 adds v[l], v[l + 64], ... in ascending order to 0.0; L = 0.0 + lane 0 + lane 1 + ... + lane 63.
+ *   normalise  per side: cx = L(x) / M, cy = L(y) / M, m = L(sqrt((x - cx)(x - cx) + (y - cy)(y - cy))) / M, s = 1.4142135623730951 / m; NOT m > 0 on either
+ *              side: no model.  X = (x - cx_i) s_i, Y = (y - cy_i) s_i, U = (u - cx_j) s_j, V = (v - cy_j) s_j.
+ *   draw       mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (lowbias32, uint32).  base = mix(mix(mix(seed) ^ frame_i) ^
+ *              frame_j), the pair key (frame_i, frame_j) from the caller (the frames, not the place in the batch); h = mix(base ^ t) for trial t; draw k = 0 .. 3:
+ *              r_k = mulhi(mix(h ^ k), M - k), taken as the r_k-th index not yet chosen, in ascending order.  The sample keeps the order drawn.
+ *   solve      sample point k gives rows 2k: [X, Y, 1, 0, 0, 0, -(U X), -(U Y) | U] and 2k + 1: [0, 0, 0, X, Y, 1, -(V X), -(V Y) | V] (h33 = 1).  Elimination on
+ *              the 8 x 9 matrix, column c = 0 .. 7: pivot = the largest |a[r][c]|, r >= c, the lowest row on a tie; |pivot| <= eps = 2^-40 rejects the trial
+ *              (a degenerate sample; normalised coordinates are of order 1); rows exchanged; for r > c: f = a[r][c] / a[c][c], a[r][k] = a[r][k] - f a[c][k] for
+ *              k > c.  Back substitution r = 7 .. 0: acc = a[r][8]; acc = acc - a[r][k] h[k] for k = r + 1 .. 7 ascending; h[r] = acc / a[r][r].
+ *   score      w = (h6 X + h7 Y) + 1; pu = (h0 X + h1 Y) + h2; pv = (h3 X + h4 Y) + h5; du = pu / w - U; dv = pv / w - V; e2 = du du + dv dv; an inlier has
+ *              w > 0 and e2 <= thr thr, thr = threshold s_j: `threshold` target pixels, the target normalisation being a similarity.  The score is the integer
+ *              count.  All `trials` trials run (no early stop).  The winner has the largest count, the lower t on a tie: one 64-bit integer atomic maximum a pair
+ *              of count << 32 | (0xFFFFFFFF - t).  All trials rejected: no model.
+ *   refit      once, over the winner's inliers: G[a][b] (a <= b) and g[a] are lane sums over the inliers (a lane's items ascending; per item first
+ *              + r1[a] r1[b], then + r2[a] r2[b]; g with the right-hand sides), r1 and r2 the two rows above; G mirrored, the same elimination.  Re-scored; the
+ *              refit's h and mask are kept when it solved and counts at least the winner's, else the winner's.
+ *   H          A = h T_i: A[r][0] = h[r][0] s_i, A[r][1] = h[r][1] s_i, A[r][2] = (h[r][2] - A[r][0] cx_i) - A[r][1] cy_i; B = T_j^-1 A: B[0][c] = A[0][c] / s_j +
+ *              cx_j A[2][c], B[1][c] = A[1][c] / s_j + cy_j A[2][c], B[2][c] = A[2][c]; H = B / B[2][2].
+ *   compact    a pair is kept when it has min_features survivors and min_features inliers (:457-468); the kept pairs' inlier rows follow each other in pair order,
+ *              inliers in row order.
+ * No floating-point atomic; the same bits on every run, in every batch and at every place in it.  Nothing synchronises. */
+/* hive_sift_detect's outputs over N pictures [.][capacity], d_pairs i32 [P][2] picture indices (a pair naming a picture outside 0 .. N - 1 has no rows),
+ * d_depth f32 [N][H][W] -> d_rows [P][capacity][8] 32-bit words (16-byte aligned; rows past a pair's count are undefined), d_pair_counts i32 [P][2].  Optional
+ * (both or neither): the raw table d_indices i32 and d_distances f32 [P][capacity][2].  1 <= P <= 65535. */
+int hive_pairs_match(hive_ctx *ctx, const float *d_keypoints, const uint8_t *d_descriptors, const int32_t *d_counts, int capacity, int N, const int32_t *d_pairs, int P,
+                     const float *d_depth, int H, int W, double ratio, int min_features, float *d_rows, int32_t *d_pair_counts, int32_t *d_indices, float *d_distances);
+/* P pairs of correspondences: pair p has d_counts[p * count_stride] rows of row_words 32-bit words (the first four: x, y, u, v float32) from d_rows + p * stride *
+ * row_words on; d_keys i32 [P][2] the pair keys -> d_H f64 [P][9], d_mask u8 [P][stride] (0 past the count), d_result i32 [P][3]: the winning trial (-1: no
+ * model, -2: count outside 0 .. stride), the winner's count, the final count.  A pair with fewer than max(min_count, 4) correspondences has no model (:457-460). */
+int hive_ransac_homography(hive_ctx *ctx, const float *d_rows, int row_words, const int32_t *d_counts, int count_stride, const int32_t *d_keys, int P, int stride,
+                           double threshold, int trials, unsigned seed, int min_count, double *d_H, uint8_t *d_mask, int32_t *d_result);
+/* hive_pairs_match's rows and counts, hive_ransac_homography's mask and result -> d_out [.][8] (room for P * stride rows, 16-byte aligned), d_kept i32 [P] the rows
+ * of every pair (0: dropped), d_offsets i64 [P + 1] the rows before every pair and, last, all rows. */
+int hive_pairs_compact(hive_ctx *ctx, const float *d_rows, const int32_t *d_pair_counts, const uint8_t *d_mask, const int32_t *d_result, int P, int stride,
+                       int min_features, float *d_out, int32_t *d_kept, int64_t *d_offsets);
 
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
