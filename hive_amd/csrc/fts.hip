@@ -24,6 +24,7 @@
 // take elements lane, lane + 64, .. in order, then the butterfly), gradients and update.  The state (14 N doubles of moments, 10 N of per-frame terms) is global
 // memory that stays in L2.
 #include "hive_internal.hpp"
+#include "pose_math.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -108,47 +109,7 @@ struct FtsArgs {
     double lr, beta1, beta2, eps, weight_decay;
 };
 
-struct Vec3 {
-    double x, y, z;
-};
-__device__ __forceinline__ Vec3 operator+(Vec3 a, Vec3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ Vec3 operator-(Vec3 a, Vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec3 operator*(double s, Vec3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ Vec3 cross(Vec3 a, Vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ Vec3 load3(const double *p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ void store3(double *p, Vec3 a) {
-    p[0] = a.x;
-    p[1] = a.y;
-    p[2] = a.z;
-}
-
-struct Pose {
-    Vec3 a;      // vector part of the unit quaternion
-    double s;    // its scalar part
-    double norm; // |q|
-    Vec3 t;
-};
-
-__device__ __forceinline__ Pose load_pose(const double *p) {
-    Pose o;
-    const double n = sqrt(((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]) + p[3] * p[3]);
-    o.a = {p[0] / n, p[1] / n, p[2] / n};
-    o.s = p[3] / n;
-    o.norm = n;
-    o.t = load3(p + 4);
-    return o;
-}
-
-// conj(u) (v, 0) u
-__device__ __forceinline__ Vec3 rotate_inverse(const Pose &u, Vec3 v) {
-    return ((u.s * u.s - dot(u.a, u.a)) * v + (2.0 * dot(u.a, v)) * u.a) - (2.0 * u.s) * cross(u.a, v);
-}
-
-// u (g, 0) conj(u)
-__device__ __forceinline__ Vec3 rotate_forward(const Pose &u, Vec3 g) {
-    return ((u.s * u.s - dot(u.a, u.a)) * g + (2.0 * dot(u.a, g)) * u.a) + (2.0 * u.s) * cross(u.a, g);
-}
+using namespace hive_pose;  // Vec3, Pose, load_pose, rotate_inverse, rotate_forward
 
 __device__ __forceinline__ double wave_sum(double s) {
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);

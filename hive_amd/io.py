@@ -180,6 +180,10 @@ class HiveDataset:
         return self.metadata.num_frames
 
     @property
+    def fps(self) -> float:
+        return self.metadata.fps
+
+    @property
     def frame_width(self) -> int:
         return self.metadata.width
 

@@ -1,8 +1,21 @@
-"""Feature pairs for pose optimisation (``FeatureExtractor`` of hive/pose_optimisation.py:224-656, at the end of this file) and foreground trajectory smoothing
-(``--fts_num_epochs N``): ``ForegroundPoseOptimiser`` of hive/pose_optimisation.py:1618-1711 on the MI355X.
+"""Pose optimisation on the MI355X: the feature pairs (``FeatureExtractor`` of hive/pose_optimisation.py:224-656), the ``PoseOptimiser`` that consumes them
+(:659-1615) and the foreground trajectory smoothing (``--fts_num_epochs N``: ``ForegroundPoseOptimiser``, :1618-1711).
 
-An Adam loop over the camera poses that damps the jitter of the dynamic objects: the centroid of every frame's object pixels is put into world space with the
-initial poses, and the poses are then moved so that those world-space centroids stay where they were while the camera path gets smoother.
+``PoseOptimiser`` / ``optimise_poses``: the reference's Adam loop over the camera poses as ONE native loop (``hive_pose_optimise``, csrc/poseopt.hip): hand-derived
+gradients gathered per frame without floating-point atomics, the learning-rate scheduler and the early stop on the device, two launches an epoch and one
+read-back per ``check_every`` epochs.  Deliberate deviations from the reference, none of them pinned against the reference's run:
+
+  * PROJECTED ADAM.  The reference assigns a new ``torch.nn.Parameter`` for the normalised quaternions (and, with ``clip_distance``, the clipped positions) every
+    epoch while its optimiser keeps the old objects, whose ``.grad`` stays None: its ``step()`` moves nothing, the loss never changes and early stopping ends the
+    run after 76 epochs.  Built here is the intent: every epoch normalises the quaternions and clips the positions IN PLACE, as projections of the live
+    parameters, and Adam steps those same parameters with its moments and step count carried through.
+  * float64 parameters (the reference: float32); the start values are the reference's float32 values, widened; ``scale`` and ``shift`` come back as float64 numpy.
+  * ``OptimisationOptions.copy()`` carries ``clip_distance``; ``OptimisationOptions`` validates ``steps``.
+  * ``AlignmentType.Deformable`` raises NotImplementedError.
+
+Foreground trajectory smoothing: an Adam loop over the camera poses that damps the jitter of the dynamic objects: the centroid of every frame's object pixels is
+put into world space with the initial poses, and the poses are then moved so that those world-space centroids stay where they were while the camera path gets
+smoother.
 
   ``centroids``                 per-frame mean of ``point_cloud_from_depth(depth, mask > 0, K)`` and its point count (``hive_fg_centroids``)
   ``dataset_centroids``         the same for every frame of a dataset, uploaded in chunks
@@ -13,6 +26,7 @@ initial poses, and the poses are then moved so that those world-space centroids 
 Deviation from the reference, on purpose: the parameters are float64 here (the reference keeps them in float32 and promotes inside the loss); the start values
 are the reference's float32 ``dataset.camera_trajectory.tensor()``, widened.  tests/test_fts_gpu.py bounds the difference by the reference's own rounding.
 """
+import ctypes
 import enum
 import logging
 
@@ -406,3 +420,466 @@ class FeatureExtractor:
             chunks += 1 if frame_index in covered and not inside else 0
             inside = frame_index in covered
         logging.info(f"Found {chunks} group(s) of consecutive frames.")
+
+
+# ---- the pose optimiser: AlignmentType .. PoseOptimiser of hive/pose_optimisation.py:659-1615, its Adam loop as hive_pose_optimise (csrc/poseopt.hip) ----
+class AlignmentType(enum.Enum):
+    """How depth maps are scaled and shifted (if at all) during pose optimisation (:659-669)."""
+    Rigid = enum.auto()       # the camera pose alone
+    Affine = enum.auto()      # the camera pose and one scale and shift per depth map
+    Deformable = enum.auto()  # a 3 x 3 field of scales and shifts per depth map: NOT built here (``optimise_poses`` raises NotImplementedError)
+
+
+class ResidualType(enum.Enum):
+    """How residuals are calculated (:829-842)."""
+    World3D = enum.auto()  # both sides of a correspondence in world space: the distance in 3-D
+    Image2D = enum.auto()  # side i projected into frame j: the distance in pixels
+
+
+class OptimisationStep(enum.Enum):
+    """Steps of the pose optimisation pipeline (:846-868)."""
+    PairWise3D = enum.auto()
+    Global3D = enum.auto()
+    PairWise2D = enum.auto()
+    Global2D = enum.auto()
+
+
+class EarlyStopping:
+    """Whether training has stagnated (:790-825): ``step(loss)`` sets ``should_stop`` once more than ``patience`` calls in a row failed to lower the best loss by
+    more than ``min_difference``.  hive_pose_optimise runs the same rule on the device."""
+
+    def __init__(self, patience=10, min_difference=0.0):
+        self.patience = patience
+        self.min_difference = min_difference
+        self.best_loss = float('inf')
+        self.calls_since_last_best = 0
+        self.should_stop = False
+
+    def step(self, loss) -> bool:
+        loss = float(loss)
+        if loss < self.best_loss and abs(loss - self.best_loss) > self.min_difference:
+            self.best_loss = loss
+            self.calls_since_last_best = 0
+        else:
+            self.calls_since_last_best += 1
+        if self.calls_since_last_best > self.patience:
+            self.should_stop = True
+        return self.should_stop
+
+
+def _check_number(value, name, kind, positive, nullable=False):
+    """The reference's ``check_domain``: ``kind`` int or float (a float option takes an int too), positive or non-negative, None where ``nullable``."""
+    if value is None and nullable:
+        return
+    ok = isinstance(value, kind if kind is int else (int, float)) and not isinstance(value, bool)
+    if not ok or not (value > 0 if positive else value >= 0) or value != value:
+        raise ValueError(f"`{name}` must be a {'positive' if positive else 'non-negative'} {kind.__name__}{' or None' if nullable else ''}, but got {value!r}.")
+
+
+class OptimisationOptions:
+    """Configuration of the ``PoseOptimiser`` (:871-964), the reference's names and defaults.  Two deliberate deviations: ``copy()`` carries ``clip_distance``
+    (the reference drops it, harmlessly there), and ``steps`` is validated -- a non-empty tuple or list of ``OptimisationStep`` (the reference's check can never
+    reject a wrong element)."""
+
+    default_pipeline = (OptimisationStep.PairWise3D, OptimisationStep.Global3D)
+
+    def __init__(self, num_epochs=4000, learning_rate=1e-2, l2_regularisation=0.5, min_loss_delta=1e-4, lr_scheduler_patience=50, early_stopping_patience=75,
+                 alignment_type=AlignmentType.Rigid, steps=default_pipeline, position_only=False, fine_tune=True, pose_t_reg=0.5, pose_r_reg=1.0,
+                 trajectory_smoothing=None, clip_distance=1.0):
+        _check_number(num_epochs, 'num_epochs', int, True)
+        _check_number(learning_rate, 'learning_rate', float, True)
+        _check_number(l2_regularisation, 'l2_regularisation', float, False)
+        _check_number(min_loss_delta, 'min_loss_delta', float, True)
+        _check_number(lr_scheduler_patience, 'lr_scheduler_patience', int, True)
+        _check_number(early_stopping_patience, 'early_stopping_patience', int, True)
+        _check_number(pose_t_reg, 'pose_t_reg', float, False)
+        _check_number(pose_r_reg, 'pose_r_reg', float, False)
+        _check_number(trajectory_smoothing, 'trajectory_smoothing', float, False, nullable=True)
+        _check_number(clip_distance, 'clip_distance', float, False, nullable=True)
+        if not isinstance(alignment_type, AlignmentType):
+            raise ValueError(f"alignment_type must be an {AlignmentType}, but got {alignment_type!r}.")
+        if not isinstance(steps, (tuple, list)) or len(steps) == 0:
+            raise ValueError(f"steps must a tuple or list with at least one element, got {type(steps)} instead.")
+        for step in steps:
+            if not isinstance(step, OptimisationStep):
+                raise ValueError(f"steps must only contain values of type {OptimisationStep}, but found a value of type {type(step)}")
+        self.num_epochs = num_epochs
+        self.learning_rate = learning_rate
+        self.l2_regularisation = l2_regularisation
+        self.min_loss_delta = min_loss_delta
+        self.lr_scheduler_patience = lr_scheduler_patience
+        self.early_stopping_patience = early_stopping_patience
+        self.alignment_type = alignment_type
+        self.steps = steps
+        self.position_only = position_only
+        self.pose_t_reg = pose_t_reg
+        self.pose_r_reg = pose_r_reg
+        self.fine_tune = fine_tune
+        self.trajectory_smoothing = trajectory_smoothing
+        self.clip_distance = clip_distance
+
+    _FIELDS = ("num_epochs", "learning_rate", "l2_regularisation", "min_loss_delta", "lr_scheduler_patience", "early_stopping_patience", "alignment_type", "steps",
+               "position_only", "pose_t_reg", "pose_r_reg", "fine_tune", "trajectory_smoothing", "clip_distance")
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(" + ", ".join(f"{name}={getattr(self, name)}" for name in self._FIELDS) + ")"
+
+    def copy(self) -> 'OptimisationOptions':
+        return OptimisationOptions(**{name: getattr(self, name) for name in self._FIELDS})
+
+
+class OptimisationParameters:
+    """The parameters subject to optimisation (:672-787): a plain holder of float64 arrays -- ``rotation_quaternions`` (N, 4) scalar last, ``translation_vectors``
+    (N, 3), and per frame ``scale`` / ``shift`` (N,), empty for Rigid alignment.  The reference's is a torch.nn.Module of float32 Parameters."""
+
+    def __init__(self, initial_camera_poses, alignment_type, scale_parameters=None, shift_parameters=None, dtype=np.float64):
+        poses = np.asarray(initial_camera_poses.values if isinstance(initial_camera_poses, Trajectory) else initial_camera_poses)
+        if poses.ndim != 2 or poses.shape[1] != 7:
+            raise ValueError(f"initial_camera_poses must be (N, 7), but got {poses.shape}")
+        self.rotation_quaternions = np.array(poses[:, :4], dtype=dtype)
+        self.translation_vectors = np.array(poses[:, 4:], dtype=dtype)
+        self.alignment_type = alignment_type
+        n = len(poses)
+        if alignment_type == AlignmentType.Rigid:
+            scale_parameters, shift_parameters = np.empty(0), np.empty(0)
+        elif alignment_type == AlignmentType.Affine:
+            scale_parameters = np.ones(n) if scale_parameters is None or np.size(scale_parameters) == 0 else scale_parameters
+            shift_parameters = np.zeros(n) if shift_parameters is None or np.size(shift_parameters) == 0 else shift_parameters
+        elif alignment_type == AlignmentType.Deformable:
+            raise NotImplementedError("AlignmentType.Deformable (a 3 x 3 field of scales and shifts per frame) is not built; Rigid and Affine are.")
+        else:
+            raise RuntimeError(f"Unsupported alignment type {alignment_type}.")
+        self.scale = np.array(scale_parameters, dtype=dtype)
+        self.shift = np.array(shift_parameters, dtype=dtype)
+
+    @property
+    def dtype(self):
+        return self.rotation_quaternions.dtype
+
+    @property
+    def num_frames(self):
+        return len(self.rotation_quaternions)
+
+    def __len__(self) -> int:
+        """The number of optimisation parameters."""
+        return int(self.rotation_quaternions.size + self.translation_vectors.size + self.scale.size + self.shift.size)
+
+    def poses(self):
+        """(N, 7) rows [raw quaternion, translation]."""
+        return np.hstack((self.rotation_quaternions, self.translation_vectors))
+
+    def normalise_rotations(self):
+        """Scale the rotation quaternions to unit vectors, in place."""
+        self.rotation_quaternions /= np.linalg.norm(self.rotation_quaternions, ord=2, axis=1).reshape((-1, 1))
+
+    def get_trajectory(self) -> Trajectory:
+        r = self.rotation_quaternions / np.linalg.norm(self.rotation_quaternions, ord=2, axis=1).reshape((-1, 1))
+        return Trajectory(np.hstack((r, self.translation_vectors)))
+
+    def sample_at(self, frame_indices) -> 'OptimisationParameters':
+        frame_indices = list(frame_indices)
+        has = self.scale.size > 0
+        return OptimisationParameters(self.poses()[frame_indices], self.alignment_type, self.scale[frame_indices] if has else None,
+                                      self.shift[frame_indices] if has else None, self.dtype)
+
+    def clone(self) -> 'OptimisationParameters':
+        return OptimisationParameters(self.poses(), self.alignment_type, self.scale.copy(), self.shift.copy(), self.dtype)
+
+
+class _PoseOptions(ctypes.Structure):
+    """``hive_pose_options`` of include/hive_mi355x.h."""
+    _fields_ = [("num_epochs", ctypes.c_int32), ("lr_scheduler_patience", ctypes.c_int32), ("early_stopping_patience", ctypes.c_int32),
+                ("alignment_type", ctypes.c_int32), ("residual_type", ctypes.c_int32), ("smooth_trajectory", ctypes.c_int32), ("position_only", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("learning_rate", ctypes.c_double), ("l2_regularisation", ctypes.c_double), ("min_loss_delta", ctypes.c_double),
+                ("pose_t_reg", ctypes.c_double), ("pose_r_reg", ctypes.c_double)]
+
+
+DEFAULT_CHECK_EVERY = 64  # epochs enqueued between two reads of the device-side stop flag: ~1 ms of queued launches, one read in 64 epochs
+
+
+def project_poses(poses, max_frame_distance=None, ctx=None):
+    """One epoch's projection alone (``hive_pose_project``): quaternions normalised, positions clipped to ``max_frame_distance`` between adjacent frames (None: no
+    clip), in the order include/hive_mi355x.h states.  ``poses`` (N, 7); returns a float64 copy."""
+    ctx = ctx or _lib.default_context()
+    p = np.array(poses, dtype=np.float64, order="C")
+    assert p.ndim == 2 and p.shape[1] == 7, "poses (N, 7)"
+    ctx.check(ctx.lib.hive_pose_project(ctx.handle, ptr(p), len(p), -1.0 if max_frame_distance is None else float(max_frame_distance)))
+    return p
+
+
+def optimise_poses(feature_set, parameters, options=None, residual_type=ResidualType.World3D, smooth_trajectory=True, fps=None, check_every=DEFAULT_CHECK_EVERY,
+                   return_gradient=False, num_epochs=None, ctx=None):
+    """The loop of ``PoseOptimiser._optimisation_loop`` (:1256-1338) as ``hive_pose_optimise``: projected Adam with hand-derived gradients, the scheduler and the
+    early stop on the device (rule and deviations: module docstring, include/hive_mi355x.h).  ``feature_set``: a ``FeatureSet`` on the device; ``parameters``: an
+    ``OptimisationParameters`` (left untouched); ``options``: ``OptimisationOptions`` -- its ``clip_distance`` (metres a second) needs ``fps``; ``num_epochs``
+    overrides the options' (0: evaluate only).  Returns (parameters, losses (epochs_run,), learning rates (epochs_run,), epochs_run): the RAW parameters after the
+    last step, the loss of every epoch before its step, the learning rate after the scheduler saw it.  With ``return_gradient`` also the loss at the returned
+    parameters and its gradient (N, 9) = d/d(quaternion, translation, scale, shift), pins applied."""
+    import torch
+    options = options or OptimisationOptions()
+    alignment = parameters.alignment_type
+    if alignment == AlignmentType.Deformable or options.alignment_type == AlignmentType.Deformable:
+        raise NotImplementedError("AlignmentType.Deformable (a 3 x 3 field of scales and shifts per frame) is not built; Rigid and Affine are.")
+    if not isinstance(residual_type, ResidualType):
+        raise RuntimeError(f"optimise_poses got given an unsupported residuals type {residual_type}.")
+    if options.clip_distance is not None and fps is None:
+        raise ValueError("options.clip_distance is metres a second: pass the dataset's fps (or clip_distance=None)")
+    if len(feature_set) == 0:
+        raise ValueError("the feature set holds no correspondence")
+    if feature_set.frame_i.index.device.type != "cuda":
+        raise ValueError("the feature set must be on the device (FeatureSet.to('cuda')): hive_amd has no CPU fallback")
+    ctx = ctx or _lib.default_context(feature_set.frame_i.index.device.index or 0)
+    ctx.follow_torch_stream()
+    epochs = int(options.num_epochs if num_epochs is None else num_epochs)
+    affine = alignment == AlignmentType.Affine
+    K = feature_set.camera_matrix.detach().cpu().numpy().astype(np.float64)
+    sides = [(s.index.contiguous(), s.points.contiguous(), s.depth.contiguous()) for s in (feature_set.frame_i, feature_set.frame_j)]
+    assert all(i.dtype == torch.long and p.dtype == torch.float32 and d.dtype == torch.float32 for i, p, d in sides)
+    n = parameters.num_frames
+    p = np.array(parameters.poses(), dtype=np.float64, order="C")
+    scale = np.array(parameters.scale, dtype=np.float64) if affine else None
+    shift = np.array(parameters.shift, dtype=np.float64) if affine else None
+    o = _PoseOptions(num_epochs=epochs, lr_scheduler_patience=int(options.lr_scheduler_patience), early_stopping_patience=int(options.early_stopping_patience),
+                     alignment_type=1 if affine else 0, residual_type=0 if residual_type == ResidualType.World3D else 1, smooth_trajectory=int(bool(smooth_trajectory)),
+                     position_only=int(bool(options.position_only)), reserved=0, learning_rate=float(options.learning_rate),
+                     l2_regularisation=float(options.l2_regularisation), min_loss_delta=float(options.min_loss_delta), pose_t_reg=float(options.pose_t_reg),
+                     pose_r_reg=float(options.pose_r_reg))
+    losses, rates = np.zeros(max(epochs, 1), np.float64), np.zeros(max(epochs, 1), np.float64)
+    ran, final = ctypes.c_int(0), np.zeros(1, np.float64)
+    grad = np.zeros((n, 9), np.float64) if return_gradient else None
+    max_distance = -1.0 if options.clip_distance is None else float(options.clip_distance) * (1.0 / float(fps))
+    ctx.check(ctx.lib.hive_pose_optimise(ctx.handle, ptr(p), ptr(scale), ptr(shift), n, K[0, 0], K[1, 1], K[0, 2], K[1, 2], ptr(sides[0][0]), ptr(sides[0][1]),
+                                         ptr(sides[0][2]), ptr(sides[1][0]), ptr(sides[1][1]), ptr(sides[1][2]), len(feature_set), ctypes.addressof(o), max_distance,
+                                         int(check_every), ptr(losses), ptr(rates), ctypes.byref(ran), ptr(final) if return_gradient else None, ptr(grad)))
+    out = OptimisationParameters(p, alignment, scale, shift)
+    result = (out, losses[:ran.value].copy(), rates[:ran.value].copy(), int(ran.value))
+    return result + (float(final[0]), grad) if return_gradient else result
+
+
+class PoseOptimiser:
+    """The reference's ``PoseOptimiser`` (:967-1615): ``PoseOptimiser(dataset, frame_sampling, feature_extraction_options, optimisation_options, debug)
+    .run(num_frames) -> (Trajectory, scale, shift)``; ``scale`` / ``shift`` float64 numpy.  Features by ``FeatureExtractor``, every optimisation loop by
+    ``optimise_poses`` (projected Adam -- the deliberate deviation the module docstring states), the host-side steps in numpy / scipy as the reference has
+    them.  The dataset's stored trajectory is not touched.  A loop over a feature set without a single correspondence (the offset run of a two-frame sequence)
+    returns its parameters as they are, with a log line; the reference takes a mean over nothing there.  The match visualisations are not written."""
+
+    DEBUG_FOLDER = 'pose_optim'
+
+    def __init__(self, dataset, frame_sampling=FrameSamplingMode.Hierarchical, feature_extraction_options=None, optimisation_options=None, debug=True,
+                 check_every=DEFAULT_CHECK_EVERY):
+        self.dataset = dataset
+        self.frame_sampling = frame_sampling
+        self.feature_extraction_options = feature_extraction_options or FeatureExtractionOptions()
+        self.optimisation_options = optimisation_options or OptimisationOptions()
+        self.debug = debug
+        self.debug_path = None
+        self.check_every = check_every
+        self.history = []  # after run(): per loop (label, losses, learning rates, epochs run)
+
+    def run(self, num_frames=-1):
+        if num_frames == -1:
+            num_frames = self.dataset.num_frames
+        # the reference's float32 start values, widened
+        start = np.asarray(self.dataset.camera_trajectory[:num_frames]).astype(np.float32).astype(np.float64)
+        self.history = []
+        self._setup_debug_folder()
+        frame_pairs = self._sample_frame_pairs(self.frame_sampling)
+        fixed_parameters = self._extract_feature_points(frame_pairs, self.feature_extraction_options)
+        optimisation_parameters = OptimisationParameters(start, alignment_type=self.optimisation_options.alignment_type)
+        optimised_parameters = self._optimise_pose(fixed_parameters, optimisation_parameters, optimisation_options=self.optimisation_options, num_frames=num_frames)
+        trajectory = self._interpolate_poses_without_matches(fixed_parameters, optimised_parameters.get_trajectory())
+        if self.optimisation_options.trajectory_smoothing:
+            trajectory = self._smooth_trajectory(trajectory=trajectory, weight=self.optimisation_options.trajectory_smoothing)
+        scale, shift = optimised_parameters.scale.copy(), optimised_parameters.shift.copy()
+        if self.debug:
+            import os
+            trajectory.save(os.path.join(self.debug_path, 'optimised_camera_trajectory.txt'))
+            np.savetxt(os.path.join(self.debug_path, 'scale.txt'), scale)
+            np.savetxt(os.path.join(self.debug_path, 'shift.txt'), shift)
+        return trajectory, scale, shift
+
+    def _setup_debug_folder(self):
+        if self.debug:
+            import os
+            self.debug_path = os.path.join(self.dataset.base_path, self.DEBUG_FOLDER)
+            os.makedirs(self.debug_path, exist_ok=True)
+
+    def _sample_frame_pairs(self, frame_sampling_mode, num_frames=-1):
+        return sample_frame_pairs(frame_sampling_mode, self.dataset.num_frames if num_frames == -1 else num_frames)
+
+    def _extract_feature_points(self, frame_pairs, feature_extraction_options=None) -> FeatureSet:
+        extractor = FeatureExtractor(self.dataset, frame_pairs, feature_extraction_options or FeatureExtractionOptions(), debug_path=self.debug_path)
+        return extractor.extract_feature_points().subset_from(frame_pairs)
+
+    def _optimise_pose(self, fixed_parameters, optimisation_parameters, optimisation_options=None, num_frames=-1) -> OptimisationParameters:
+        """The step pipeline plus the fine-tune step (:1110-1183)."""
+        options = optimisation_options or self.optimisation_options
+        if num_frames == -1:
+            num_frames = self.dataset.num_frames
+        if num_frames != self.dataset.num_frames:
+            fixed_parameters = fixed_parameters.sample_at(range(num_frames))
+            optimisation_parameters = optimisation_parameters.sample_at(list(range(num_frames)))
+        if fixed_parameters.frame_i.index.device.type != "cuda":
+            fixed_parameters = fixed_parameters.to("cuda")
+        num_steps = len(self.optimisation_options.steps) + (1 if self.optimisation_options.fine_tune else 0)
+        if self.debug:
+            self.visualise_solution(optimisation_parameters, label="initial_trajectory")
+        for i, step in enumerate(self.optimisation_options.steps):
+            logging.info(f"Step {i + 1}/{num_steps}: {step.name} Alignment...")
+            if step in (OptimisationStep.PairWise2D, OptimisationStep.PairWise3D):
+                residual_type = ResidualType.Image2D if step == OptimisationStep.PairWise2D else ResidualType.World3D
+                optimisation_parameters = self._optimise_pairwise(fixed_parameters, optimisation_parameters, options, residual_type, num_frames)
+            elif step in (OptimisationStep.Global2D, OptimisationStep.Global3D):
+                residual_type = ResidualType.Image2D if step == OptimisationStep.Global2D else ResidualType.World3D
+                optimisation_parameters = self._optimisation_loop(fixed_parameters, optimisation_parameters, options, residual_type, label=step.name)
+            else:
+                raise RuntimeError(f"Unsupported optimisation step: {step}.")
+            if self.debug:
+                self.visualise_solution(optimisation_parameters, f"{i}_{step.name}")
+        if self.optimisation_options.fine_tune:
+            logging.info(f"Step {num_steps}/{num_steps}: Fine tuning...")
+            optimisation_parameters = self._optimisation_loop(fixed_parameters, optimisation_parameters, options, ResidualType.World3D, smooth_trajectory=False,
+                                                              label="FineTune")
+            if self.debug:
+                self.visualise_solution(optimisation_parameters, f"{num_steps}_FineTune")
+        return optimisation_parameters
+
+    def _optimise_pairwise(self, fixed_parameters, optimisation_parameters, optimisation_options=None, residual_type=ResidualType.World3D, num_frames=-1):
+        """Poses over the consecutive pairs (0, 1), (2, 3), .. and then (1, 2), (3, 4), .. in isolation, Rigid whatever the options say, chained from the
+        identity pose by the relative pose of every pair (:1185-1254)."""
+        from hive_amd.geometric import add_pose, get_identity_pose, subtract_pose
+        if num_frames == -1:
+            num_frames = self.dataset.num_frames
+        options = (optimisation_options or self.optimisation_options).copy()
+        options.alignment_type = AlignmentType.Rigid
+        rigid = OptimisationParameters(optimisation_parameters.poses(), AlignmentType.Rigid)
+        pose_data = dict()
+        for mode in (FrameSamplingMode.ConsecutiveNoOverlap, FrameSamplingMode.ConsecutiveNoOverlapOffset):
+            frame_pairs = self._sample_frame_pairs(mode, num_frames)
+            feature_set = fixed_parameters.subset_from(frame_pairs)
+            trajectory = self._optimisation_loop(feature_set, rigid, options, residual_type=residual_type, label=f"PairWise/{mode.name}").get_trajectory()
+            for i, j in frame_pairs:
+                pose_data[(i, j)] = trajectory[[i, j]]
+        merged = [get_identity_pose()]
+        for i, j in sorted(pose_data.keys()):
+            pose_i, pose_j = pose_data[i, j]
+            merged.append(add_pose(merged[-1], subtract_pose(pose_i, pose_j)))
+        return OptimisationParameters(np.asarray(merged), optimisation_parameters.alignment_type, optimisation_parameters.scale, optimisation_parameters.shift,
+                                      optimisation_parameters.dtype)
+
+    def _optimisation_loop(self, fixed_parameters, optimisation_parameters, optimisation_options=None, residual_type=ResidualType.World3D, smooth_trajectory=True,
+                           label=None) -> OptimisationParameters:
+        options = optimisation_options or self.optimisation_options
+        if len(fixed_parameters) == 0:
+            logging.info("Pose optimisation: no correspondence for this step, parameters left as they are.")
+            return optimisation_parameters.clone()
+        if options.alignment_type != optimisation_parameters.alignment_type:  # the pair-wise runs force Rigid
+            optimisation_parameters = OptimisationParameters(optimisation_parameters.poses(), options.alignment_type)
+        out, losses, rates, ran = optimise_poses(fixed_parameters, optimisation_parameters, options, residual_type, smooth_trajectory,
+                                                 fps=self.dataset.fps if options.clip_distance is not None else None, check_every=self.check_every)
+        self.history.append((label, losses, rates, ran))
+        if ran:
+            logging.info(f"{label or 'Optimisation'}: {ran} epochs, loss {losses[0]:.4f} -> {losses[-1]:.4f}, LR {rates[-1]:,.2e}")
+        return out
+
+    @staticmethod
+    def _interpolate_poses_without_matches(feature_set, optimised_camera_trajectory) -> Trajectory:
+        """Poses of the frames in no matched pair, by Slerp / linear interpolation between the nearest frames that are (:1521-1569)."""
+        import torch
+        from scipy.interpolate import interp1d
+        from scipy.spatial.transform import Rotation, Slerp
+        num_frames = len(optimised_camera_trajectory)
+        matched = set(i for i in torch.unique(torch.cat((feature_set.frame_i.index, feature_set.frame_j.index))).tolist() if i < num_frames)
+        chunks, chunk = [], []
+        for frame_index in range(num_frames):
+            if frame_index not in matched:
+                chunk.append(frame_index)
+            elif chunk:
+                chunks.append(chunk)
+                chunk = []
+        if chunk:
+            chunks.append(chunk)
+        out = optimised_camera_trajectory.copy()
+        for chunk in chunks:
+            start, end = max(0, chunk[0] - 1), min(chunk[-1] + 1, num_frames - 1)
+            if end == start:
+                continue
+            times = np.linspace(0, 1, num=end - start + 1)
+            slerp = Slerp([0, 1], Rotation.from_quat([optimised_camera_trajectory[start, :4], optimised_camera_trajectory[end, :4]]))
+            lerp = interp1d([0, 1], [optimised_camera_trajectory[start, 4:], optimised_camera_trajectory[end, 4:]], axis=0)
+            out[start:end + 1, 4:] = lerp(times)
+            out[start:end + 1, :4] = slerp(times).as_quat()
+        return out
+
+    @staticmethod
+    def _smooth_trajectory(trajectory, weight=0.9) -> Trajectory:
+        """Exponential moving average of the positions (:1571-1588)."""
+        out = trajectory.copy()
+        for i in range(1, len(out)):
+            out.positions[i] = weight * trajectory.positions[i] + (1 - weight) * out.positions[i - 1]
+        return out
+
+    def visualise_solution(self, solution, label):
+        """The trajectory on the XY and XZ planes as ``<label>.png`` in the debug folder (:1590-1615), when matplotlib imports."""
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+        except ImportError:
+            return
+        import os
+        positions = solution.get_trajectory().positions
+        figure, axes = plt.subplots(1, 2, figsize=(12.8, 4.8))
+        for axis, (name, column) in zip(axes, (("y", 1), ("z", 2))):
+            axis.plot(positions[:, 0], positions[:, column], '-', color="black", label="trajectory")
+            axis.legend()
+            axis.set_xlabel("x [m]")
+            axis.set_ylabel(f"{name} [m]")
+            axis.set_title(f"Trajectory on X{name.upper()} Plane")
+        plt.tight_layout()
+        plt.savefig(os.path.join(self.debug_path, f"{label}.png"), dpi=90)
+        plt.close(figure)
+
+
+def main(argv=None):
+    """The reference's command line (:1714-1763): optimise a dataset's poses and, in debug mode, fuse a mesh before and after."""
+    import argparse
+    import os
+
+    from hive_amd.io import HiveDataset
+    parser = argparse.ArgumentParser()
+    parser.add_argument('dataset_path', type=str, help='Path to the VTM formatted dataset.')
+    parser.add_argument('--num_frames', type=int, default=-1, help='Number of frames to optimise. If set to -1 (default), use all frames.')
+    parser.add_argument('--fine_tune', action='store_true', help='Whether to perform an additional fine tuning step.')
+    parser.add_argument('--params_init', type=str, choices=['gt', 'random'], default='gt', help='How to initialise the camera trajectory.')
+    parser.add_argument('--random_seed', type=int, default=None, help='Random seed to use when initialising camera trajectory with random data.')
+    args = parser.parse_args(argv)
+    if not HiveDataset.is_valid_folder_structure(args.dataset_path):
+        raise RuntimeError(f"The path {args.dataset_path} does not point to a valid dataset.")
+    dataset = HiveDataset(args.dataset_path)
+    num_frames = args.num_frames
+    if num_frames == -1:
+        num_frames = dataset.num_frames
+    elif num_frames < 2:
+        raise RuntimeError(f"--num_frames must at least 2, but got {num_frames}.")
+    if args.params_init == 'random':
+        from scipy.spatial.transform import Rotation
+        rng = np.random.default_rng(args.random_seed)
+        dataset.camera_trajectory[:, :4] = Rotation.random(len(dataset), random_state=args.random_seed).as_quat()
+        dataset.camera_trajectory[:, 4:] = rng.normal(loc=0., scale=.1, size=(len(dataset), 3))
+    optimiser = PoseOptimiser(dataset, feature_extraction_options=FeatureExtractionOptions(min_features=40, max_features=2048),
+                              optimisation_options=OptimisationOptions(num_epochs=20000, learning_rate=1e-2, lr_scheduler_patience=50))
+    camera_trajectory, _, _ = optimiser.run(num_frames)
+    if optimiser.debug_path:
+        from hive_amd.fusion import tsdf_fusion
+        from hive_amd.options import BackgroundMeshOptions, MeshReconstructionMethod
+        reconstruction_options = BackgroundMeshOptions(reconstruction_method=MeshReconstructionMethod.TSDFFusion, sdf_max_voxels=80000000)
+        logging.info("Running TSDFFusion on initial pose data...")
+        tsdf_fusion(dataset, options=reconstruction_options, num_frames=num_frames).export(os.path.join(optimiser.debug_path, 'before.ply'))
+        dataset.camera_trajectory = camera_trajectory
+        logging.info("Running TSDFFusion on final pose data..")
+        tsdf_fusion(dataset, options=reconstruction_options, num_frames=num_frames).export(os.path.join(optimiser.debug_path, 'after.ply'))
+
+
+if __name__ == '__main__':
+    main()

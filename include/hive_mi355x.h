@@ -387,6 +387,56 @@ int hive_fg_centroids(hive_ctx *ctx, const float *d_depth, const uint8_t *d_mask
 int hive_fts_optimise(hive_ctx *ctx, double *params, const double *gt_params, const double *centroids, int n_frames, const int32_t *chunk_start,
                       const int32_t *chunk_len, int n_chunks, double learning_rate, int num_epochs, double *losses, double *gradient);
 
+/* ---- PoseOptimiser._optimisation_loop (hive/pose_optimisation.py:1256-1519) as PROJECTED Adam -- csrc/poseopt.hip */
+typedef enum hive_pose_alignment { HIVE_POSE_RIGID = 0, HIVE_POSE_AFFINE = 1, HIVE_POSE_DEFORMABLE = 2 } hive_pose_alignment;
+typedef enum hive_pose_residual { HIVE_POSE_WORLD3D = 0, HIVE_POSE_IMAGE2D = 1 } hive_pose_residual;
+typedef struct hive_pose_options {
+    int32_t num_epochs, lr_scheduler_patience, early_stopping_patience;
+    int32_t alignment_type, residual_type; /* hive_pose_alignment, hive_pose_residual */
+    int32_t smooth_trajectory, position_only;
+    int32_t reserved;
+    double learning_rate, l2_regularisation, min_loss_delta, pose_t_reg, pose_r_reg;
+} hive_pose_options;
+/* The Adam loop over the camera poses p_f = (q_f scalar-last, t_f), world-to-camera, and -- Affine -- a depth scale and shift per frame, against the M
+ * correspondences of a FeatureSet.  DELIBERATE DEVIATION, not pinned against the reference's run: the reference assigns new Parameter objects for the normalised
+ * quaternions and the clipped positions every epoch while its optimiser keeps the old ones, so its step() moves nothing; this is the intent, projected Adam --
+ * every epoch normalises the quaternions and clips the positions IN PLACE and Adam then steps those same parameters, moments and step count carried through.
+ * Float64 parameters and arithmetic (the reference: float32), no contraction, every sum in an order fixed by the problem: bit-identical from run to run and for
+ * every check_every.
+ *   params f64 [n][7] in / out (host): raw, the returned ones as the last step left them (not normalised).  scale, shift f64 [n] in / out (host; Affine, else NULL).
+ *   d_index_{i,j} i64 [M], d_points_{i,j} f32 [M][2] (u, v), d_depth_{i,j} f32 [M]: DEVICE arrays, the tensors of a FeatureSet.
+ * One epoch e, with lr_e decided after the loss of epoch e - 1 (lr_0 = learning_rate):
+ *   1. q_f := q_f / sqrt(((x^2 + y^2) + z^2) + w^2), component by component.
+ *   2. if max_frame_distance >= 0 (= clip_distance / fps; negative: no clip): d_f = t_f - t_{f-1} of the positions as they are; |d_f| = sqrt((dx^2 + dy^2) + dz^2); where
+ *      |d_f| > max_frame_distance, d_f := (max_frame_distance / |d_f|) d_f; frames before the first such f stay as they are, from it on t_f := t_{f-1} + d_f, frame after
+ *      frame (shifting all later frames by a correction, as the reference does, leaves later differences untouched).
+ *   3. loss = (sum_f share_f) -- the shares added thread k taking frames k, k + 256, .., lane butterfly xor 32 .. 1, four waves in order -- where share_f =
+ *      (sum over the correspondences with index_i = f of |r_k|) / M + the regulariser terms whose FIRST frame is f, and, per correspondence, with u = q / |q|:
+ *        camera point c = (((u - c_x) * depth) / f_x, ((v - c_y) * depth) / f_y, depth) -- Rigid: computed once; Affine: depth = 1 / (scale_f (1 / depth) + shift_f);
+ *        World3D: r = p - q, p = conj(u_i) (c_i - t_i) u_i, q likewise on side j;   Image2D: x = u_j p conj(u_j) + t_j, r = (u_j, v_j) - ((f_x x + c_x z) / z,
+ *        (f_y y + c_y z) / z), no guard on z;
+ *      smooth_trajectory: + pose_t_reg (mean_a |t_a - t_{a+1}|^2 + mean_a |D2_a|^2 + mean_a |D2_a - D2_{a+1}|^2), D2_a = (t_a - 2 t_{a+1}) + t_{a+2}, + pose_r_reg
+ *      mean_a (1 - (q_a . q_{a+1})^2) on the raw quaternions; a mean over no rows (n < 4) is 0, not NaN;   Affine: + l2 mean_f (1 / scale_f - 1)^2 + 2 l2 mean_f shift_f^2.
+ *   4. the gradient by hand (formulas at the top of poseopt.hip; 0 where |r_k| = 0, as torch.norm's): per frame the sum over its incidence list -- every (k, side)
+ *      with index_side[k] = f, ascending in k, side i before j -- thread j taking entries j, j + 256, .., lane butterfly, waves in order; then the regularisers; then
+ *      frame 0's pose gradient := 0 and, position_only, every quaternion gradient := 0.
+ *   5. torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, no weight decay): m += (1 - b1) (g - m), v = b2 v + (1 - b2) g g, p -= lr_e / (1 - b1^k) * m / (sqrt(v) /
+ *      sqrt(1 - b2^k) + eps), b^k by repeated multiplication.
+ *   6. ReduceLROnPlateau(mode min, threshold_mode abs, threshold min_loss_delta, patience lr_scheduler_patience, factor 0.1, cooldown 0, min_lr 0, eps 1e-8) on the
+ *      loss: better if loss < best - threshold; more than patience bad epochs: lr := 0.1 lr if that lowers it by more than 1e-8, bad count := 0.  Then the
+ *      reference's EarlyStopping: improved if loss < best and |loss - best| > min_loss_delta; stop once the calls since the last best exceed
+ *      early_stopping_patience.  Both run ON THE DEVICE; after a stop every queued launch is a no-op.  The host enqueues check_every epochs and then reads the state.
+ * losses, learning_rates f64 [num_epochs] (host): entries [0, *epochs_run) are written -- the loss of each epoch's projected parameters before its step, and the
+ * learning rate after the scheduler saw that loss (what the next epoch uses).  *final_loss, gradient f64 [n][9] (both optional): the loss and d/d(q, t, scale, shift)
+ * with the pins applied at the RETURNED parameters, no projection -- with num_epochs = 0, at the input.  Refused with a message: n < 2, M < 1, an index outside
+ * [0, n), a depth or focal length that is not positive and finite, Deformable; a loss that is not finite ends the call with an error naming the epoch. */
+int hive_pose_optimise(hive_ctx *ctx, double *params, double *scale, double *shift, int n_frames, double fx, double fy, double cx, double cy,
+                       const int64_t *d_index_i, const float *d_points_i, const float *d_depth_i, const int64_t *d_index_j, const float *d_points_j,
+                       const float *d_depth_j, int64_t n_matches, const hive_pose_options *options, double max_frame_distance, int check_every, double *losses,
+                       double *learning_rates, int *epochs_run, double *final_loss, double *gradient);
+/* Steps 1 and 2 of an epoch of hive_pose_optimise alone, on params f64 [n][7] in / out (host), n >= 1: what the tests hold against the stated order. */
+int hive_pose_project(hive_ctx *ctx, double *params, int n_frames, double max_frame_distance);
+
 /* ---- dilate_mask(mask, MaskDilationOptions(num_iterations)) -- hive/image_processing.py:30-45 */
 /* 3x3 rectangular structuring element applied `iterations` times == one (2*it+1)^2 box max
  * (cv2.dilate border = no contribution from outside).  mask/out u8 [H][W], non-zero = set; out is written as 0 / 1 and must not
