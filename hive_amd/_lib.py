@@ -18,7 +18,7 @@ OK, ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_EMPTY, ERR_STATE = 0, -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
 ROUND_HALF_EVEN, ROUND_HALF_AWAY = 0, 1
 F32, F16, BF16 = 0, 1, 2
-ABI_VERSION = 9  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step; 7 = hive_dpt_plan_arena, hive_gn_gram_preferred; 8 = hive_sift_*, hive_knn_match, hive_mifd; 9 = hive_pairs_match, hive_ransac_homography, hive_pairs_compact (hive_pose_optimise and hive_pose_project joined without a new number: additions only, and a library without them fails to load by name)
+ABI_VERSION = 9  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step; 7 = hive_dpt_plan_arena, hive_gn_gram_preferred; 8 = hive_sift_*, hive_knn_match, hive_mifd; 9 = hive_pairs_match, hive_ransac_homography, hive_pairs_compact (hive_pose_optimise and hive_pose_project joined without a new number: additions only, and a library without them fails to load by name; hive_gltf_layout and hive_gltf_pack likewise)
 
 c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 P = ctypes.POINTER
@@ -136,6 +136,8 @@ SIGNATURES = {
                          c_void_p]),
     "hive_ransac_homography": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_int, ctypes.c_uint, c_int, c_void_p, c_void_p, c_void_p]),
     "hive_pairs_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "hive_gltf_layout": (c_int, [c_void_p, c_int, c_int, c_void_p, P(c_int64)]),
+    "hive_gltf_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "hive_depth_apply_mask_se": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "hive_vit_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, P(c_void_p)]),
     "hive_vit_weights_modified": (c_int, [c_void_p]),
@@ -193,6 +195,21 @@ SIGNATURES = {
     "hive_dpt_destroy": (c_int, [c_void_p]),
     "hive_depth_quantize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
 }
+
+GLTF_POSITION, GLTF_TEXCOORD, GLTF_COLOR, GLTF_INDICES = 0, 1, 2, 3  # hive_gltf_kind: the columns of hive_gltf_layout's views
+GLTF_F32, GLTF_F64, GLTF_I32, GLTF_I64 = 0, 1, 0, 1
+
+
+class GltfMesh(ctypes.Structure):
+    """``hive_gltf_mesh``: one mesh of hive_gltf_layout / hive_gltf_pack (device pointers as integers)."""
+    _fields_ = [("vertices", c_void_p), ("faces", c_void_p), ("uv", c_void_p), ("colors", c_void_p), ("n_vertices", c_int64), ("n_faces", c_int64),
+                ("vertex_dtype", ctypes.c_int32), ("face_dtype", ctypes.c_int32), ("color_channels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class GltfView(ctypes.Structure):
+    """``hive_gltf_view``: byte offset and length of one buffer view ({0, 0}: absent)."""
+    _fields_ = [("offset", c_int64), ("length", c_int64)]
+
 
 _lib = None
 _lock = threading.Lock()

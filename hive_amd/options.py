@@ -438,11 +438,13 @@ class PipelineOptions(Options):
               _Flag('billboard', 'billboard', bool, False, 'flat billboards instead of meshes for the foreground objects'),
               _Flag('disable_scaling', 'disable_scaling', bool, False, 'keep the input resolution instead of rescaling to 640x480'),
               _Flag('disable_coverage_constraint', 'disable_coverage_constraint', bool, False, 'keep foreground objects that cover under 1 %% of the frame'),
-              _Flag('log_file', 'log_file', str, 'logs.log', 'path of the log file'))
+              _Flag('log_file', 'log_file', str, 'logs.log', 'path of the log file'),
+              _Flag('export_gltf', 'export_gltf', bool, False, 'centre the scenes and write mesh/fg.glb, mesh/bg.glb and metadata.json, then export them to --webxr_path'))
 
     def __init__(self, num_frames=-1, frame_step=15, estimate_pose=False, estimate_depth=False, background_only=False, static_camera=False,
                  align_scene=False, inpainting_mode=InpaintingMode.Off, billboard=False, disable_scaling=False, disable_coverage_constraint=False,
-                 log_file='logs.log'):
+                 log_file='logs.log', export_gltf=False):
+        self.export_gltf = export_gltf
         self.disable_scaling = disable_scaling
         self.disable_coverage_constraint = disable_coverage_constraint
         self.num_frames = num_frames

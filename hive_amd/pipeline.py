@@ -2,18 +2,23 @@
 (/root/reference/hive/pipeline.py:258-286, 871-901), then the per-frame foreground meshes (``_create_scene``, :309-497) with the
 connected-component clean-up and, on request, decimation, billboards and trajectory smoothing.
 
-glTF export, draco compression, scene centring and the WebXR viewer of the reference's ``Pipeline`` are outside the scope of this
-build; meshes are written as PLY.
+Meshes are written as PLY.  On request (``run(export_gltf=True)`` / ``--export_gltf``) the reference's last stages follow (:213-237, :902-1158): the two
+scenes are centred (``_center_scenes``), written as ``mesh/fg.glb`` and ``mesh/bg.glb`` (hive_amd/gltf.py: packed on the device, csrc/gltf.hip) with
+``mesh/metadata.json``, and copied to the player's folder (``_export_video_webxr``).  Where the reference compresses with draco_transcoder the files are
+written quantised (KHR_mesh_quantization).  Draco itself and the WebXR server of the reference's ``Pipeline`` stay outside the scope of this build
+(SURVEY.md §2 row 10), as do the oriented bounds of ``align_scene`` (trimesh's).
 """
 import argparse
 import json
 import logging
 import os
+import shutil
+from pathlib import Path
 from typing import Optional
 
 import numpy as np
 
-from hive_amd import foreground, fusion
+from hive_amd import foreground, fusion, gltf
 from hive_amd.dataset_adaptors import get_dataset
 from hive_amd.io import HiveDataset
 from hive_amd.options import (BackgroundMeshOptions, COLMAPOptions, ForegroundTrajectorySmoothingOptions, MaskDilationOptions, MeshDecimationOptions,
@@ -61,8 +66,8 @@ def write_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None, *,
 class Pipeline:
     """The reference's ``Pipeline`` (/root/reference/hive/pipeline.py:59-262) for the part this build serves: dataset -> key frames
     -> TSDF fusion -> background mesh -> per-frame foreground meshes.  Constructor, ``from_command_line`` and ``run`` take the reference's
-    arguments; the foreground path does what the reference's does short of export: the stages behind the remaining option groups (glTF / draco export, WebXR)
-    are outside this build's scope."""
+    arguments; the foreground path does what the reference's does, and with ``export_gltf`` the scenes are centred, written as glTF and exported to the player's
+    folder (``_center_scenes`` .. ``_export_video_webxr`` below); draco and the WebXR server are outside this build's scope."""
     mesh_folder = "mesh"
     bundle_fusion_folder = "bundle_fusion"
 
@@ -132,13 +137,14 @@ class Pipeline:
         logging.info(f"Creating background mesh from {len(frame_set)} key frames...")
         return fusion.tsdf_fusion(dataset, options, num_frames=num_frames, frame_set=frame_set)
 
-    def create_foreground_meshes(self, dataset: HiveDataset, num_frames: int, folder: str):
+    def create_foreground_meshes(self, dataset: HiveDataset, num_frames: int, folder: str, scene: Optional[gltf.Scene] = None):
         """``_create_foreground_scene`` / ``_create_scene`` (pipeline.py:288-497) for the dynamic objects of frames 0 .. num_frames - 1: every frame through
         ``foreground.process_frame`` with the connected-component clean-up on; a frame with a surviving object gives ``<folder>/%06d.ply`` (vertices in the frame of
         bg.ply, atlas uv) and ``<folder>/%06d.png`` (its texture atlas).  With ``decimation_options.enabled`` (``--enable_decimation``; off by default) every object is
         decimated before the clean-up and ``mesh_decimation`` profiling counts are recorded; with ``options.billboard`` (``--billboard``) every object is flattened to
         its median depth before texturing; with ``fts_options.num_epochs > 0`` (``--fts_num_epochs``) the meshes are built with the poses ``ForegroundPoseOptimiser``
-        returns (:297-303) -- the dataset's stored trajectory, and with it bg.ply, stay as they are (the reference's ``temporary_trajectory``)."""
+        returns (:297-303) -- the dataset's stored trajectory, and with it bg.ply, stay as they are (the reference's ``temporary_trajectory``).  With a ``scene`` every
+        frame's mesh joins it as it is made, on the device, under the node name ``%06d`` (:487)."""
         from PIL import Image
         not_applied = []
         decimation = self.decimation_options if self.decimation_options.enabled else None
@@ -173,14 +179,133 @@ class Pipeline:
             Image.fromarray(mesh["texture"].cpu().numpy()).save(os.path.join(folder, name))
             write_ply(os.path.join(folder, f"{i:06d}.ply"), mesh["vertices"].cpu().numpy(), mesh["faces"].cpu().numpy(),
                       vertex_uv=mesh["uv"].cpu().numpy(), texture_file=name)
+            if scene is not None:
+                scene.add_geometry({key: mesh[key] for key in ("vertices", "faces", "uv", "texture")}, node_name=f"{i:06d}")
 
-    def run(self, dataset=None, adaptor=None, compress=True, *, estimate_depth=None):
+    # ------------------------------------------------------------------------------------------------ glTF export (pipeline.py:213-237, 902-1158)
+    @staticmethod
+    def _create_empty_scene(dataset: HiveDataset) -> gltf.Scene:
+        """pipeline.py:636-648: an empty scene with the dataset's camera (resolution and focal lengths)."""
+        K = np.asarray(dataset.camera_matrix)
+        return gltf.Scene(camera=dict(resolution=(dataset.frame_width, dataset.frame_height), focal=(float(K[0, 0]), float(K[1, 1]))))
+
+    def _create_background_scene(self, dataset: HiveDataset, static_mesh=None):
+        """pipeline.py:258-286 for TSDFFusion: the static mesh under the node ``000000``.  Where the reference rewrites the vertex colours with
+        ``(255 * (c / 255) ** 2.2).astype(int)`` (:281-282) the mesh stays as it is and the same table is returned as the ``lut`` the packer applies on the
+        device.  Returns (scene, lut)."""
+        if self.background_mesh_options.reconstruction_method != MeshReconstructionMethod.TSDFFusion:
+            raise NotImplementedError(f"{self.background_mesh_options.reconstruction_method.name}: only TSDFFusion is part of the dense-compute path")
+        scene = self._create_empty_scene(dataset)
+        if static_mesh is None:
+            static_mesh = self.create_static_mesh(dataset, num_frames=self.num_frames, options=self.background_mesh_options)
+        lut = (255 * np.power(np.arange(256) / 255, 2.2)).astype(np.uint8)
+        scene.add_geometry(static_mesh, node_name="000000")
+        return scene, lut
+
+    def _create_foreground_scene(self, dataset: HiveDataset, num_frames: Optional[int] = None, folder: Optional[str] = None) -> gltf.Scene:
+        """pipeline.py:288-307: an empty scene for ``background_only``, else every frame's mesh (``create_foreground_meshes``, which smooths the trajectory
+        first when asked to); the PLY and PNG files go to ``folder`` (default ``<mesh_path>/fg``) as in a run without export."""
+        scene = self._create_empty_scene(dataset)
+        if not self.options.background_only:
+            n = dataset.num_frames if num_frames is None else num_frames
+            self.create_foreground_meshes(dataset, n, folder or os.path.join(self.mesh_path, "fg"), scene=scene)
+        return scene
+
+    @staticmethod
+    def _get_scene_bounds(foreground_scene, background_scene):
+        """pipeline.py:1084-1104: the joint (2, 3) bounds; a foreground scene without meshes has no bounds and contributes none."""
+        fg_bounds, bg_bounds = foreground_scene.bounds, background_scene.bounds
+        if fg_bounds is None:
+            return bg_bounds
+        return np.vstack([np.min(np.vstack((fg_bounds[0], bg_bounds[0])), axis=0), np.max(np.vstack((fg_bounds[1], bg_bounds[1])), axis=0)])
+
+    def _center_scenes(self, dataset, foreground_scene, background_scene):
+        """pipeline.py:982-1031 on copies of the scenes: turn them the right way up, then move them so that the joint bounds are centred in x and sit on y = 0 and
+        z = 0.  Two stated choices: the turn by 180 degrees about z is exactly diag(-1, -1, 1, 1) (scipy's ``Rotation.from_euler('xyz', [0, 0, 180])`` has
+        1.2e-16 where this has 0), and the offset is rounded to float32 as the reference's ``np.eye(4, dtype=np.float32)`` does.  ``align_scene`` needs trimesh's
+        oriented bounds (:1006-1017) and raises."""
+        if self.options.align_scene:
+            raise NotImplementedError("align_scene: the oriented bounds of the background scene are trimesh's (trimesh.bounds.oriented_bounds), which this build does not have")
+        foreground_scene, background_scene = foreground_scene.copy(), background_scene.copy()
+        rotate_right_way_up = np.diag([-1.0, -1.0, 1.0, 1.0])
+        foreground_scene.apply_transform(rotate_right_way_up)
+        background_scene.apply_transform(rotate_right_way_up)
+        scene_bounds = self._get_scene_bounds(foreground_scene, background_scene)
+        scene_centroid = np.mean(scene_bounds, axis=0)
+        translation = np.eye(4, dtype=np.float32)
+        translation[:3, 3] = np.array([-scene_centroid[0], -scene_bounds[0, 1], -scene_bounds[0, 2]])
+        foreground_scene.apply_transform(translation)
+        background_scene.apply_transform(translation)
+        return foreground_scene, background_scene
+
+    @classmethod
+    def _write_meshes_to_disk(cls, mesh_path: str, foreground_scene, background_scene, overwrite_ok=False, quantize=False, background_lut=None):
+        """pipeline.py:902-919 -> (path of fg.glb, path of bg.glb).  (The folder already holds this run's PLY files, so unlike the reference's it is made with
+        ``exist_ok=True``; ``overwrite_ok`` guards the export folder, ``_export_video_webxr``.)"""
+        os.makedirs(mesh_path, exist_ok=True)
+        return (cls._write_mesh_to_disk(mesh_path, "fg", foreground_scene, quantize=quantize),
+                cls._write_mesh_to_disk(mesh_path, "bg", background_scene, quantize=quantize, lut=background_lut))
+
+    @classmethod
+    def _write_mesh_to_disk(cls, base_folder: str, scene_name: str, scene, quantize=False, lut=None) -> str:
+        """pipeline.py:921-936: ``<base_folder>/<scene_name>.glb`` through ``gltf.write_glb``."""
+        output_path = os.path.join(base_folder, f"{scene_name}.glb")
+        sizes = gltf.write_glb(output_path, scene, quantize=quantize, lut=lut)
+        logging.info(f"Wrote mesh data to {output_path} ({sizes['total']} bytes)")
+        return output_path
+
+    def _compress_with_quantisation(self, path_to_glb: str, scene, lut=None):
+        """Where the reference runs draco_transcoder over the file (:938-980): the scene is written again with KHR_mesh_quantization, the plain file is
+        replaced, and ``profiling['mesh_compression'][foreground | background]`` gets the reference's four keys from the two file sizes."""
+        src_path = Path(path_to_glb)
+        tmp_path = src_path.with_name(f"{src_path.stem}_tmp{src_path.suffix}")
+        gltf.write_glb(str(tmp_path), scene, quantize=True, lut=lut)
+        size_before, size_after = os.path.getsize(src_path), os.path.getsize(tmp_path)
+        shutil.move(str(tmp_path), str(src_path))
+        name = {"fg": "foreground", "bg": "background"}.get(src_path.stem, src_path.stem)
+        set_key_path(self.profiling, ["mesh_compression", name], {
+            "uncompressed_file_size": size_before,
+            "compressed_file_size": size_after,
+            "data_saving": 1 - size_after / size_before,
+            "compression_ratio": size_before / size_after,
+        })
+
+    @staticmethod
+    def _get_dataset_name(dataset: HiveDataset) -> str:
+        """pipeline.py:1106-1109: the dataset's folder name."""
+        return Path(dataset.base_path).name
+
+    def _get_webxr_metadata(self, dataset: HiveDataset, num_frames: Optional[int] = None) -> dict:
+        """pipeline.py:1111-1125: the six keys of the player's metadata.json."""
+        fy = float(np.asarray(dataset.camera_matrix)[1, 1])
+        fov_y = float(np.rad2deg(2 * np.arctan2(dataset.frame_height, 2 * fy)))  # io.py:1025-1027
+        return dict(fps=dataset.fps, fov_y=int(fov_y), num_frames=self.num_frames if num_frames is None else num_frames,
+                    use_vertex_colour_for_bg=self.background_mesh_options.reconstruction_method != MeshReconstructionMethod.RGBD,
+                    add_ground_plane=self.webxr_options.webxr_add_ground_plane, add_sky_box=self.webxr_options.webxr_add_sky_box)
+
+    def _export_video_webxr(self, mesh_path: str, fg_scene_name: str, bg_scene_name: str, metadata: dict, export_name: str) -> str:
+        """pipeline.py:1127-1158: metadata.json beside the meshes, then the three files copied to ``<webxr_path>/<export_name>``; an export folder that exists
+        raises FileExistsError unless ``storage_options.overwrite_ok``."""
+        webxr_output_path = os.path.join(self.webxr_options.webxr_path, export_name)
+        os.makedirs(webxr_output_path, exist_ok=bool(self.storage_options and self.storage_options.overwrite_ok))
+        with open(os.path.join(mesh_path, "metadata.json"), "w") as f:
+            json.dump(metadata, f)
+        for filename in ("metadata.json", f"{fg_scene_name}.glb", f"{bg_scene_name}.glb"):
+            shutil.copy(os.path.join(mesh_path, filename), os.path.join(webxr_output_path, filename))
+        logging.info(f"Exported mesh data to: {webxr_output_path}")
+        return webxr_output_path
+
+    def run(self, dataset=None, adaptor=None, compress=True, *, estimate_depth=None, export_gltf=None):
         """pipeline.py:172-262: load (or convert) the dataset, fuse the static scene, write ``<output>/mesh/bg.ply`` (vertex colours in sRGB as
         pipeline.py:281-282), then -- unless ``background_only`` -- the foreground meshes of every frame (``create_foreground_meshes``: ``mesh/fg/``),
         and ``profiling.json``; returns the background mesh.
 
         Reference form: ``run(dataset: Optional[HiveDataset] = None, adaptor: Optional[DatasetAdaptor] = None, compress=True)`` with the
-        paths in ``storage_options``.  Shorthand of earlier rounds: ``run(dataset_path, output_path, estimate_depth=False)``."""
+        paths in ``storage_options``.  Shorthand of earlier rounds: ``run(dataset_path, output_path, estimate_depth=False)``.
+
+        ``export_gltf`` (default: ``options.export_gltf``, off): after the PLY files the scenes are centred and ``mesh/fg.glb``, ``mesh/bg.glb`` and
+        ``mesh/metadata.json`` are written and copied to ``webxr_options.webxr_path/<dataset name>`` (:213-237); with ``compress`` the files are written
+        quantised.  Off, a run writes nothing new."""
         if isinstance(dataset, (str, os.PathLike)):  # shorthand: run(dataset_path, output_path)
             self.storage_options = StorageOptions(dataset_path=str(dataset), output_path=str(adaptor))
             dataset = adaptor = None
@@ -206,12 +331,40 @@ class Pipeline:
         os.makedirs(out, exist_ok=True)
         with timed_block("Wrote mesh data in", self.profiling, ("timing", "mesh_export")):
             write_ply(os.path.join(out, "bg.ply"), mesh.vertices, mesh.faces, colors, mesh.vertex_normals)
+        export_gltf = bool(self.options.export_gltf if export_gltf is None else export_gltf)
+        foreground_scene = self._create_empty_scene(dataset) if export_gltf else None
         if not self.options.background_only:
             with timed_block("Created foreground meshes in", self.profiling, ("timing", "foreground_reconstruction", "total")):
-                self.create_foreground_meshes(dataset, n, os.path.join(out, "fg"))
+                self.create_foreground_meshes(dataset, n, os.path.join(out, "fg"), scene=foreground_scene)
+        if export_gltf:
+            self._export_gltf(dataset, n, out, mesh, foreground_scene, compress)
         with open(os.path.join(dataset.base_path, "profiling.json"), "w") as f:  # pipeline.py:251
             json.dump(self.profiling, f, indent=2)
         return mesh
+
+
+    def _export_gltf(self, dataset, num_frames, mesh_path, static_mesh, foreground_scene, compress):
+        """The reference's last four stages (pipeline.py:213-237) under its timing keys (``mesh_export`` is the sum of the PLY and the glTF writing)."""
+        if self.storage_options is None:
+            self.storage_options = StorageOptions(dataset_path=dataset.base_path, output_path=os.path.dirname(mesh_path))
+        background_scene, lut = self._create_background_scene(dataset, static_mesh)
+        with timed_block("Centred the scenes in", self.profiling, ("timing", "scene_centering")):
+            foreground_scene, background_scene = self._center_scenes(dataset, foreground_scene, background_scene)
+        ply_seconds = self.profiling.get("timing", {}).get("mesh_export", 0.0)
+        with timed_block("Wrote glTF data in", self.profiling, ("timing", "mesh_export")):
+            fg_path, bg_path = self._write_meshes_to_disk(mesh_path, foreground_scene, background_scene, overwrite_ok=self.storage_options.overwrite_ok,
+                                                          background_lut=lut)
+        self.profiling["timing"]["mesh_export"] += ply_seconds
+        with timed_block("Compressed mesh data in", self.profiling, ("timing", "mesh_compression", "total")):
+            with timed_block("Quantised the foreground scene in", self.profiling, ("timing", "mesh_compression", "foreground")):
+                if compress:
+                    self._compress_with_quantisation(fg_path, foreground_scene)
+            with timed_block("Quantised the background scene in", self.profiling, ("timing", "mesh_compression", "background")):
+                if compress:
+                    self._compress_with_quantisation(bg_path, background_scene, lut)
+        with timed_block("Exported mesh data in", self.profiling, ("timing", "webxr_export")):
+            self._export_video_webxr(mesh_path, fg_scene_name="fg", bg_scene_name="bg", metadata=self._get_webxr_metadata(dataset, num_frames),
+                                     export_name=self._get_dataset_name(dataset))
 
 
 def main(argv=None):

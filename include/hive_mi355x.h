@@ -834,6 +834,45 @@ int hive_ransac_homography(hive_ctx *ctx, const float *d_rows, int row_words, co
 int hive_pairs_compact(hive_ctx *ctx, const float *d_rows, const int32_t *d_pair_counts, const uint8_t *d_mask, const int32_t *d_result, int P, int stride,
                        int min_features, float *d_out, int32_t *d_kept, int64_t *d_offsets);
 
+/* ---- glTF 2.0 export: the meshes of a scene packed into the binary buffer of a .glb -- what Pipeline._write_mesh_to_disk (hive/pipeline.py:921-936) hands to
+ * trimesh's exporter and Pipeline._compress_with_draco (:938-980) to draco_transcoder -- csrc/gltf.hip.  trimesh, pygltflib and draco_transcoder are absent: the
+ * bytes below are stated from the glTF 2.0 specification and KHR_mesh_quantization and are not pinned against trimesh's exporter or against three.js's loader.
+ * tests/gltf_restatement.py states the same rules in numpy.  Float64 arithmetic with one rounding per operation, / correctly rounded, rint = round half to even.
+ *   views      one binary buffer; mesh after mesh, within a mesh POSITION, TEXCOORD_0 (with uv), COLOR_0 (with colours), indices.  Every view starts at the next
+ *              multiple of 4 after the view before it, the bytes between are 0, and the buffer ends on a multiple of 4.
+ *   bounds     per mesh and axis lo = min, hi = max over the vertices (float32 input widened).  A vertex that is not finite fails the call.
+ *   quantize 0 POSITION 3 x float32: the round-to-nearest-even cast of the input.  TEXCOORD_0 2 x float32 of (u, 1.0 - v), the subtraction in float64 (the atlas
+ *              coordinates of pack_textures_row have their origin bottom-left, glTF's top-left).  COLOR_0 4 x uint8 normalised: r, g, b (each through lut[.] when
+ *              a table is given), a (255 when the input has three channels; never through the table).  Indices uint32.
+ *   quantize 1 KHR_mesh_quantization.  s = (hi - lo) / 65535.0 per axis, s = 1.0 when hi == lo.  POSITION 3 x uint16, not normalised, in an 8-byte stride whose
+ *              last two bytes are 0: q = min(65535, rint((x - lo) / s)); the mesh's node carries scale s and translation lo.  TEXCOORD_0 2 x uint16 normalised:
+ *              rint(min(max(c, 0.0), 1.0) * 65535.0) of c = u and c = 1.0 - v.  COLOR_0 as above.  Indices uint16 when V <= 65535, else uint32.
+ *   indices    an index outside [0, V) fails the call.  A mesh without faces (or without vertices) is rejected: leave its node out.
+ * Failures name the first mesh they concern.  No floating-point atomic; the same bytes on every run, for a mesh alone or inside a batch. */
+typedef enum hive_gltf_kind { HIVE_GLTF_POSITION = 0, HIVE_GLTF_TEXCOORD = 1, HIVE_GLTF_COLOR = 2, HIVE_GLTF_INDICES = 3 } hive_gltf_kind;
+typedef enum hive_gltf_dtype { HIVE_GLTF_F32 = 0, HIVE_GLTF_F64 = 1, HIVE_GLTF_I32 = 0, HIVE_GLTF_I64 = 1 } hive_gltf_dtype;
+typedef struct hive_gltf_mesh {
+    const void *vertices;   /* device [V][3], vertex_dtype */
+    const void *faces;      /* device [F][3], face_dtype */
+    const double *uv;       /* device [V][2] or NULL */
+    const uint8_t *colors;  /* device [V][color_channels] or NULL */
+    int64_t n_vertices, n_faces;
+    int32_t vertex_dtype;   /* HIVE_GLTF_F32 / HIVE_GLTF_F64 */
+    int32_t face_dtype;     /* HIVE_GLTF_I32 / HIVE_GLTF_I64 */
+    int32_t color_channels; /* 3 or 4 (read only with colours) */
+    int32_t reserved;
+} hive_gltf_mesh;
+typedef struct hive_gltf_view {
+    int64_t offset, length; /* bytes; an absent view is {0, 0} */
+} hive_gltf_view;
+/* Host only (no context, no device; the pointers of a mesh are only tested against NULL) -> views[n][4] indexed by hive_gltf_kind, *total_bytes the buffer's
+ * length.  A failure's message is hive_last_error(NULL). */
+int hive_gltf_layout(const hive_gltf_mesh *meshes, int n, int quantize, hive_gltf_view *views, int64_t *total_bytes);
+/* Three launches for any n (bounds, bounds final stage, pack) behind ONE upload of the descriptor table: d_out (device, 4-byte aligned, out_bytes >= the layout's
+ * total) receives every view and the padding inside the layout's total; bounds (host) [n][2][3] = lo, hi per mesh in float64.  lut: 256 bytes in host memory or
+ * NULL.  Returns after the device has finished (the bounds come back with the error words). */
+int hive_gltf_pack(hive_ctx *ctx, const hive_gltf_mesh *meshes, int n, int quantize, const uint8_t *lut, uint8_t *d_out, int64_t out_bytes, double *bounds);
+
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
  * (x 1/1000 as float32, > max_depth -> 0), optional mask (non-zero -> depth 0, fusion.py:121).
