@@ -138,6 +138,8 @@ SIGNATURES = {
     "hive_pairs_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hive_gltf_layout": (c_int, [c_void_p, c_int, c_int, c_void_p, P(c_int64)]),
     "hive_gltf_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "hive_jpeg_layout": (c_int, [c_void_p, c_int, c_int, c_void_p, P(c_int64)]),
+    "hive_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "hive_depth_apply_mask_se": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "hive_vit_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, P(c_void_p)]),
     "hive_vit_weights_modified": (c_int, [c_void_p]),
@@ -209,6 +211,14 @@ class GltfMesh(ctypes.Structure):
 class GltfView(ctypes.Structure):
     """``hive_gltf_view``: byte offset and length of one buffer view ({0, 0}: absent)."""
     _fields_ = [("offset", c_int64), ("length", c_int64)]
+
+
+JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2}  # hive_jpeg_subsampling
+
+
+class JpegImage(ctypes.Structure):
+    """``hive_jpeg_image``: one picture of hive_jpeg_layout / hive_jpeg_encode (the device pointer as an integer)."""
+    _fields_ = [("data", c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("pitch", c_int64)]
 
 
 _lib = None

@@ -4,7 +4,8 @@ the reference calls ``trimesh.exchange.export.export_scene``, :921-936, and ``dr
 The geometry of a scene is packed on the device into the file's final byte layout by csrc/gltf.hip (``hive_gltf_layout`` / ``hive_gltf_pack``: three launches
 per scene, the rules in include/hive_mi355x.h) and comes to the host in ONE copy.  trimesh, pygltflib and draco_transcoder are absent here: the container is
 written from the glTF 2.0 specification (and KHR_mesh_quantization in place of draco) and is not pinned against trimesh's exporter, not pinned against three.js.
-No NORMAL is written: the viewer and the experiments' renderer are unlit.
+No NORMAL is written: the viewer and the experiments' renderer are unlit.  Textures are embedded as PNG (the default: a host encoder, the reference's format) or,
+with ``texture_format="jpeg"``, as baseline JPEG encoded on the device by csrc/jpeg.hip: every texture of the scene in one call and one download.
 """
 import io
 import json
@@ -22,6 +23,7 @@ FLOAT, UNSIGNED_BYTE, UNSIGNED_SHORT, UNSIGNED_INT = 5126, 5121, 5123, 5125
 ARRAY_BUFFER, ELEMENT_ARRAY_BUFFER = 34962, 34963
 QUANTIZATION = "KHR_mesh_quantization"
 KNOWN_EXTENSIONS = (QUANTIZATION,)
+TEXTURE_FORMATS = ("png", "jpeg")
 _COMPONENT = {FLOAT: "<f4", UNSIGNED_BYTE: "u1", UNSIGNED_SHORT: "<u2", UNSIGNED_INT: "<u4"}
 _WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4}
 
@@ -199,13 +201,20 @@ def camera_json(camera):
             "extras": {"resolution": [w, h], "focal": [fx, fy]}}
 
 
-def write_glb(path, scene, quantize=False, lut=None, ctx=None, timings=None):
+def write_glb(path, scene, quantize=False, lut=None, ctx=None, timings=None, texture_format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """Write the scene as one binary glTF 2.0 file.  Geometry: layout, pack, ONE device-to-host copy.  Every textured mesh gets its atlas as an embedded PNG with
-    one image, texture and material (``baseColorTexture`` only).  One scene; its root node ``"world"`` carries the scene transform as a column-major ``matrix``
+    one image, texture and material (``baseColorTexture`` only); with ``texture_format="jpeg"`` the atlases are baseline JPEG files (``image/jpeg``) of
+    ``jpeg_quality`` and ``jpeg_subsampling``, all encoded on the device in one call (``hive_amd.jpeg.encode``) and downloaded once, and ``timings`` gets a
+    ``jpeg`` key in place of ``png``.  One scene; its root node ``"world"`` carries the scene transform as a column-major ``matrix``
     (and the camera), its children are the scene's nodes in order.  Meshes without faces are left out.  ``quantize``: KHR_mesh_quantization (uint16 positions
     under a node scale / translation, uint16 uv, uint16 indices up to 65535 vertices).  ``lut``: 256 bytes applied to the RGB of vertex colours.  Returns the
     byte counts per kind (``geometry``, ``images``, ``json``, ``total``).  ``timings``: a dict that receives the seconds of pack, download, png and file write."""
     import time
+    if texture_format not in TEXTURE_FORMATS:
+        raise ValueError(f"texture_format {texture_format!r} is not one of {TEXTURE_FORMATS}")
+    if texture_format == "jpeg":
+        from hive_amd import jpeg
+        jpeg.check_settings(jpeg_quality, jpeg_subsampling)
     clock = [time.perf_counter()]
 
     def lap(key):
@@ -272,21 +281,26 @@ def write_glb(path, scene, quantize=False, lut=None, ctx=None, timings=None):
             doc["nodes"].append(node)
             doc["meshes"].append({"primitives": [primitive]})
         lap("json")
+        textured = [k for k in range(len(drawn)) if views[k, _lib.GLTF_TEXCOORD, 1]]
+        encoded = {}
+        if texture_format == "jpeg" and textured:
+            atlases = [mesh_fields(drawn[k][1])[3] for k in textured]
+            encoded = dict(zip(textured, jpeg.encode([a if a.shape[2] == 3 else a[:, :, :3] for a in atlases], jpeg_quality, jpeg_subsampling, ctx)))
         for k, (name, m) in enumerate(drawn):
             texture = mesh_fields(m)[3]
             if not views[k, _lib.GLTF_TEXCOORD, 1]:
                 continue
-            png = _png_bytes(texture)
+            png = encoded[k] if texture_format == "jpeg" else _png_bytes(texture)
             for key in ("images", "textures", "materials"):
                 doc.setdefault(key, [])
-            doc["images"].append({"bufferView": add_view(len(binary), len(png)), "mimeType": "image/png"})
+            doc["images"].append({"bufferView": add_view(len(binary), len(png)), "mimeType": "image/" + texture_format})
             doc["textures"].append({"source": len(doc["images"]) - 1})
             doc["materials"].append({"pbrMetallicRoughness": {"baseColorTexture": {"index": len(doc["textures"]) - 1}}})
             doc["meshes"][k]["primitives"][0]["material"] = len(doc["materials"]) - 1
             binary += _pad4(png, b"\0")
             n_images += len(png)
         doc["buffers"] = [{"byteLength": len(binary)}]
-        lap("png")
+        lap(texture_format)
     text = _pad4(json.dumps(doc, separators=(",", ":")).encode("utf-8"), b" ")
     chunks = struct.pack("<II", len(text), CHUNK_JSON) + text
     if binary:
@@ -427,8 +441,9 @@ def read_glb(path):
                 start, size = view.get("byteOffset", 0), view["byteLength"]
             except (KeyError, IndexError, TypeError) as e:
                 raise GltfError(f"node {node.get('name')!r}: the material's base colour texture does not resolve ({e!r})")
-            _require(image.get("mimeType") == "image/png" and 0 <= start and start % 4 == 0 and start + size <= len(binary),
-                     f"node {node.get('name')!r}: the image is a PNG in a 4-byte aligned view inside the buffer")
+            _require(image.get("mimeType") in ("image/png", "image/jpeg") and 0 <= start and start % 4 == 0 and start + size <= len(binary),
+                     f"node {node.get('name')!r}: the image is a PNG or a JPEG in a 4-byte aligned view inside the buffer")
+            _require(image["mimeType"] == "image/png" or binary[start:start + size][:3] == b"\xFF\xD8\xFF", f"node {node.get('name')!r}: the image/jpeg view does not start FF D8 FF")
             texture = np.array(Image.open(io.BytesIO(binary[start:start + size])).convert("RGB"))
             mesh = {"vertices": vertices, "faces": faces.astype(np.int64), "uv": uv, "texture": texture}
         scene.add_geometry(mesh, node.get("name"))

@@ -239,27 +239,29 @@ class Pipeline:
         return foreground_scene, background_scene
 
     @classmethod
-    def _write_meshes_to_disk(cls, mesh_path: str, foreground_scene, background_scene, overwrite_ok=False, quantize=False, background_lut=None):
+    def _write_meshes_to_disk(cls, mesh_path: str, foreground_scene, background_scene, overwrite_ok=False, quantize=False, background_lut=None, texture_format="png",
+                              jpeg_quality=90):
         """pipeline.py:902-919 -> (path of fg.glb, path of bg.glb).  (The folder already holds this run's PLY files, so unlike the reference's it is made with
         ``exist_ok=True``; ``overwrite_ok`` guards the export folder, ``_export_video_webxr``.)"""
         os.makedirs(mesh_path, exist_ok=True)
-        return (cls._write_mesh_to_disk(mesh_path, "fg", foreground_scene, quantize=quantize),
-                cls._write_mesh_to_disk(mesh_path, "bg", background_scene, quantize=quantize, lut=background_lut))
+        return (cls._write_mesh_to_disk(mesh_path, "fg", foreground_scene, quantize=quantize, texture_format=texture_format, jpeg_quality=jpeg_quality),
+                cls._write_mesh_to_disk(mesh_path, "bg", background_scene, quantize=quantize, lut=background_lut, texture_format=texture_format, jpeg_quality=jpeg_quality))
 
     @classmethod
-    def _write_mesh_to_disk(cls, base_folder: str, scene_name: str, scene, quantize=False, lut=None) -> str:
-        """pipeline.py:921-936: ``<base_folder>/<scene_name>.glb`` through ``gltf.write_glb``."""
+    def _write_mesh_to_disk(cls, base_folder: str, scene_name: str, scene, quantize=False, lut=None, texture_format="png", jpeg_quality=90) -> str:
+        """pipeline.py:921-936: ``<base_folder>/<scene_name>.glb`` through ``gltf.write_glb``; the textures as ``options.texture_format`` says (PNG unless asked)."""
         output_path = os.path.join(base_folder, f"{scene_name}.glb")
-        sizes = gltf.write_glb(output_path, scene, quantize=quantize, lut=lut)
+        sizes = gltf.write_glb(output_path, scene, quantize=quantize, lut=lut, texture_format=texture_format, jpeg_quality=jpeg_quality)
         logging.info(f"Wrote mesh data to {output_path} ({sizes['total']} bytes)")
         return output_path
 
     def _compress_with_quantisation(self, path_to_glb: str, scene, lut=None):
         """Where the reference runs draco_transcoder over the file (:938-980): the scene is written again with KHR_mesh_quantization, the plain file is
-        replaced, and ``profiling['mesh_compression'][foreground | background]`` gets the reference's four keys from the two file sizes."""
+        replaced, and ``profiling['mesh_compression'][foreground | background]`` gets the reference's four keys from the two file sizes.  The textures keep
+        the plain file's format (``options.texture_format``)."""
         src_path = Path(path_to_glb)
         tmp_path = src_path.with_name(f"{src_path.stem}_tmp{src_path.suffix}")
-        gltf.write_glb(str(tmp_path), scene, quantize=True, lut=lut)
+        gltf.write_glb(str(tmp_path), scene, quantize=True, lut=lut, texture_format=self.options.texture_format, jpeg_quality=self.options.jpeg_quality)
         size_before, size_after = os.path.getsize(src_path), os.path.getsize(tmp_path)
         shutil.move(str(tmp_path), str(src_path))
         name = {"fg": "foreground", "bg": "background"}.get(src_path.stem, src_path.stem)
@@ -353,7 +355,7 @@ class Pipeline:
         ply_seconds = self.profiling.get("timing", {}).get("mesh_export", 0.0)
         with timed_block("Wrote glTF data in", self.profiling, ("timing", "mesh_export")):
             fg_path, bg_path = self._write_meshes_to_disk(mesh_path, foreground_scene, background_scene, overwrite_ok=self.storage_options.overwrite_ok,
-                                                          background_lut=lut)
+                                                          background_lut=lut, texture_format=self.options.texture_format, jpeg_quality=self.options.jpeg_quality)
         self.profiling["timing"]["mesh_export"] += ply_seconds
         with timed_block("Compressed mesh data in", self.profiling, ("timing", "mesh_compression", "total")):
             with timed_block("Quantised the foreground scene in", self.profiling, ("timing", "mesh_compression", "foreground")):

@@ -873,6 +873,40 @@ int hive_gltf_layout(const hive_gltf_mesh *meshes, int n, int quantize, hive_glt
  * NULL.  Returns after the device has finished (the bounds come back with the error words). */
 int hive_gltf_pack(hive_ctx *ctx, const hive_gltf_mesh *meshes, int n, int quantize, const uint8_t *lut, uint8_t *d_out, int64_t out_bytes, double *bounds);
 
+/* ---- baseline JPEG: the textures of a glTF file (`image/jpeg`) encoded on the device -- csrc/jpeg.hip.  The reference embeds PNG (trimesh) and has no such
+ * step.  The bytes are libjpeg's, as Pillow (libjpeg-turbo) writes them with quality = q, subsampling 4:4:4 or 4:2:0, optimize = False, restart_marker_rows = 1;
+ * tests/jpeg_restatement.py states the same rules in numpy and tests/test_jpeg_cpu.py pins that restatement against Pillow, whole files.  Integer arithmetic only.
+ *   tables     Annex K quantisation tables scaled by 5000 / q (q < 50) or 200 - 2 q: clip((base * scale + 50) / 100, 1, 255); the four Annex K Huffman tables.
+ *   colour     Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;
+ *              Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ *   edges      the MCU is 8 x 8 (4:4:4) or 16 x 16 (4:2:0).  Columns past the width repeat the last column at full resolution.  Rows past the height repeat
+ *              the last row, except the chroma of 4:2:0: there rows repeat up to an EVEN height, the picture is down-sampled, and the last DOWN-SAMPLED row
+ *              repeats.  Down-sampling: (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, .. along the output row.
+ *   transform  samples - 128, libjpeg's slow integer DCT (Loeffler, Ligtenberg, Moschytz; CONST_BITS 13, PASS1_BITS 2; rows, then columns), quantised as
+ *              sign(c) * ((|c| + (d >> 1)) / d), d = table << 3.
+ *   dummies    luminance blocks of 4:2:0 past ceil(W / 8) or ceil(H / 8): zero AC; past the right edge the DC of the block to the left in the MCU, in a
+ *              row past the bottom the DC of Y01 in both blocks.
+ *   scan       one interleaved scan (Y00 Y01 Y10 Y11 Cb Cr, or Y Cb Cr), zigzag order, DC differences per component, run / size codes with ZRL and EOB,
+ *              0x00 behind every 0xFF.  The restart interval is one MCU row: 1-bits up to the byte, RST(n mod 8), predictors back to 0; EOI behind the last.
+ *   header     SOI, APP0 (JFIF 1.1, density 1 x 1, no units), DQT 0, DQT 1, SOF0, DHT DC0, AC0, DC1, AC1, DRI, SOS: 629 bytes.
+ * The same bytes on every run, for a picture alone or anywhere in a batch. */
+typedef enum hive_jpeg_subsampling { HIVE_JPEG_444 = 0, HIVE_JPEG_420 = 2 } hive_jpeg_subsampling; /* Pillow's numbers */
+typedef struct hive_jpeg_image {
+    const uint8_t *data; /* device [height][pitch] bytes: width pixels of R, G, B at the start of every row */
+    int32_t height, width;
+    int64_t pitch;       /* bytes from one row to the next, >= 3 * width */
+} hive_jpeg_image;
+/* Host only (no context, no device) -> offsets[n], each a multiple of 4, and *total_bytes: room for the WORST case of every file.  A block's longest coding is
+ * a DC code of 11 bits with 11 value bits and 63 AC coefficients of a 16-bit code with 10 value bits each (a ZRL or EOB only replaces longer codes):
+ * 22 + 63 * 26 = 1660 bits, taken as 52 words = 208 bytes.  Stuffing can at most double every byte: 416 bytes per block.  Every MCU row adds a marker of 2
+ * bytes (its padding to a byte is inside the block bound), the file 629 bytes of header: bound = 629 + 416 * blocks + 2 * MCU rows, up to a multiple of 4,
+ * blocks = MCUs * 3 (4:4:4) or * 6 (4:2:0).  Fails on n < 1, an unknown subsampling, a side of 0 or above 65535; the message is hive_last_error(NULL). */
+int hive_jpeg_layout(const hive_jpeg_image *images, int n, int subsampling, int64_t *offsets, int64_t *total_bytes);
+/* Seven launches for any n behind ONE upload of the picture table: file i goes to d_out + offsets[i] (device; out_bytes >= the layout's total, or the call fails
+ * naming the bytes needed, before any launch; nothing is ever written past out_bytes), its length to sizes[i] (host).  quality 1 .. 100.  At most 2^22 blocks
+ * per call.  Returns after the device has finished (the sizes come back in one small copy). */
+int hive_jpeg_encode(hive_ctx *ctx, const hive_jpeg_image *images, int n, int quality, int subsampling, uint8_t *d_out, int64_t out_bytes, int64_t *sizes);
+
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
  * (x 1/1000 as float32, > max_depth -> 0), optional mask (non-zero -> depth 0, fusion.py:121).
