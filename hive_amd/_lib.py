@@ -140,6 +140,8 @@ SIGNATURES = {
     "hive_gltf_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "hive_jpeg_layout": (c_int, [c_void_p, c_int, c_int, c_void_p, P(c_int64)]),
     "hive_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "hive_png_layout": (c_int, [c_void_p, c_int, c_void_p, P(c_int64)]),
+    "hive_png_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "hive_depth_apply_mask_se": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "hive_vit_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, P(c_void_p)]),
     "hive_vit_weights_modified": (c_int, [c_void_p]),
@@ -214,11 +216,17 @@ class GltfView(ctypes.Structure):
 
 
 JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2}  # hive_jpeg_subsampling
+PNG_KIND = {"gray8": 0, "gray16": 1, "rgb8": 2}  # hive_png_kind
 
 
 class JpegImage(ctypes.Structure):
     """``hive_jpeg_image``: one picture of hive_jpeg_layout / hive_jpeg_encode (the device pointer as an integer)."""
     _fields_ = [("data", c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("pitch", c_int64)]
+
+
+class PngImage(ctypes.Structure):
+    """``hive_png_image``: one picture of hive_png_layout / hive_png_encode (the device pointer as an integer)."""
+    _fields_ = [("pixels", c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("pitch", c_int64), ("kind", ctypes.c_int32)]
 
 
 _lib = None

@@ -39,14 +39,14 @@ class DatasetAdaptor:
         return (os.path.isdir(path) and all(os.path.isfile(pjoin(path, f)) for f in cls.required_files)
                 and all(os.path.isdir(pjoin(path, f)) for f in cls.required_folders))
 
-    def convert(self, estimate_pose, estimate_depth, inpainting_mode=InpaintingMode.Off, static_camera=False, no_cache=False, profiling=None):
+    def convert(self, estimate_pose, estimate_depth, inpainting_mode=InpaintingMode.Off, static_camera=False, no_cache=False, profiling=None, png_encoder="host"):
         raise NotImplementedError(f"{type(self).__name__}.convert: this capture format needs stages outside the dense-compute path of "
                                   f"this build (COLMAP / ffmpeg / capture-specific decoding, SURVEY.md section 2 row 11); convert the "
                                   f"sequence with the reference and open the resulting HIVE folder, or use a TUM-layout folder")
 
-    def _inpaint_frame_data(self, mode: InpaintingMode):
+    def _inpaint_frame_data(self, mode: InpaintingMode, png_encoder="host"):
         """Inpaints the RGB frames, depth maps and masks of the converted folder and writes them to disk (dataset_adaptors.py:473-571)."""
-        inpaint_frame_data(self.output_path, mode)
+        inpaint_frame_data(self.output_path, mode, png_encoder=png_encoder)
 
 
 class TUMAdaptor(DatasetAdaptor):
@@ -125,10 +125,11 @@ class TUMAdaptor(DatasetAdaptor):
         return (1000 * depth_map).astype(np.uint16)  # convert to mm from metres.
 
     def convert(self, estimate_pose=False, estimate_depth=False, inpainting_mode=InpaintingMode.Off, static_camera=False, no_cache=False,
-                profiling=None) -> HiveDataset:
+                profiling=None, png_encoder="host") -> HiveDataset:
         """Write the HIVE-format folder and return it as a ``HiveDataset`` (dataset_adaptors.py:176-266).
         Instance masks need detectron2 (out of scope): empty masks are written, i.e. a static scene.
-        ``estimate_depth=True`` replaces the sensor depth by DPT-Hybrid estimates (needs the weights file)."""
+        ``estimate_depth=True`` replaces the sensor depth by DPT-Hybrid estimates (needs the weights file).  ``png_encoder`` ("host" | "gpu") goes to
+        ``estimate_depth_dpt`` and ``inpaint_frame_data``; the frames copied here are always written by the host encoder."""
         if estimate_pose:
             raise NotImplementedError("pose estimation runs COLMAP, which is outside the dense-compute scope")
         if static_camera:
@@ -151,11 +152,11 @@ class TUMAdaptor(DatasetAdaptor):
                 depth_mm = self.depth_to_mm(raw)
                 Image.fromarray(depth_mm).save(pjoin(out, "depth", name))  # uint16 -> 16-bit PNG
         if estimate_depth:
-            estimate_depth_dpt(ImageFolderDataset(pjoin(out, "rgb")), pjoin(out, "depth"))
+            estimate_depth_dpt(ImageFolderDataset(pjoin(out, "rgb")), pjoin(out, "depth"), png_encoder=png_encoder)
         np.savetxt(pjoin(out, HiveDataset.camera_matrix_filename), self.intrinsic_matrix)
         Trajectory(self.camera_trajectory.values[:self.num_frames]).save(pjoin(out, HiveDataset.camera_trajectory_filename))
         with timed_block("Inpainted the frame data in", profiling, ('timing', 'load_dataset', 'inpainting')):  # (dataset_adaptors.py:261-262)
-            self._inpaint_frame_data(mode=inpainting_mode)
+            self._inpaint_frame_data(mode=inpainting_mode, png_encoder=png_encoder)
         return HiveDataset(out)
 
 
@@ -227,7 +228,7 @@ def _write_png(path, array):
     Image.fromarray(array).save(path)  # uint8 [H][W] / [H][W][3] -> 8-bit PNG, uint16 [H][W] -> 16-bit PNG
 
 
-def inpaint_frame_data(dataset_path, mode: InpaintingMode, ctx=None, batch_size=32):
+def inpaint_frame_data(dataset_path, mode: InpaintingMode, ctx=None, batch_size=32, png_encoder="host"):
     """``DatasetAdaptor._inpaint_frame_data`` (dataset_adaptors.py:473-571) on a HIVE-format folder: the instance masks are dilated with a 5 x 5
     element five times, colour and depth are filled under them (radius 30) and written to ``rgb_inpainted/`` and ``depth_inpainted/`` under the
     file names and bit depths of ``rgb/`` and ``depth/``; ``mask_inpainted/`` gets an all-zero mask per frame (the background then has no
@@ -235,7 +236,11 @@ def inpaint_frame_data(dataset_path, mode: InpaintingMode, ctx=None, batch_size=
 
     ``Off`` does nothing; ``CV2_Image_Depth`` runs Telea's method on the GPU, ``batch_size`` frames per call, in the level order that
     ``hive_inpaint_telea`` states (not cv2's heap order: INTEGRATION.md); the three modes with LaMa raise ``NotImplementedError``.  The PNG
-    files of a batch are written by a thread pool while the GPU fills the next one."""
+    files of a batch are written by a thread pool while the GPU fills the next one.  ``png_encoder="gpu"``: the three files of every frame of a batch are
+    compressed on the device in one ``hive_amd.png.encode`` call (same pixels, the device encoder's bytes) and the pool only writes them; the default
+    ``"host"`` is Pillow, as before."""
+    from hive_amd import png
+    png.check_encoder(png_encoder)
     mode = InpaintingMode(mode)
     if mode == InpaintingMode.Off:
         return
@@ -273,6 +278,14 @@ def inpaint_frame_data(dataset_path, mode: InpaintingMode, ctx=None, batch_size=
             filled_rgb, filled_depth = inpaint_frames(torch.from_numpy(rgb).to(device), torch.from_numpy(depth).to(device),
                                                       torch.from_numpy(np.ascontiguousarray(mask != 0, dtype=np.uint8)).to(device),
                                                       dilation=INPAINTING_MASK_DILATION, radius=INPAINTING_RADIUS, ctx=ctx)
+            if png_encoder == "gpu":
+                black = torch.zeros(mask.shape[1:], dtype=torch.uint8, device=device)
+                files = png.encode([picture for j in range(len(index)) for picture in (filled_rgb[j], filled_depth[j].view(torch.uint16), black)], ctx=ctx)
+                names = [pjoin(folder, names.image_filenames[i]) for i in index for folder, names in ((out_rgb, rgb_set), (out_depth, depth_set), (out_mask, mask_set))]
+                for done in pending:
+                    done.result()
+                pending = [writers.submit(png.write_file, name, data) for name, data in zip(names, files)]
+                continue
             filled_rgb, filled_depth = filled_rgb.cpu().numpy(), filled_depth.cpu().numpy()
             for done in pending:  # at most two batches of files in flight
                 done.result()
@@ -288,12 +301,12 @@ def inpaint_frame_data(dataset_path, mode: InpaintingMode, ctx=None, batch_size=
         writers.shutdown(wait=True)
 
 
-def _open_hive_folder(path, inpainting_mode, profiling=None) -> HiveDataset:
+def _open_hive_folder(path, inpainting_mode, profiling=None, png_encoder="host") -> HiveDataset:
     """A HIVE folder as it is; with an inpainting mode and no inpainted frames yet, those are made first (the masks come with the folder)."""
     dataset = HiveDataset(path)
     if inpainting_mode != InpaintingMode.Off and not dataset.has_inpainted_frame_data:
         with timed_block("Inpainted the frame data in", profiling, ('timing', 'load_dataset', 'inpainting')):
-            inpaint_frame_data(path, inpainting_mode)
+            inpaint_frame_data(path, inpainting_mode, png_encoder=png_encoder)
         dataset = HiveDataset(path)
     return dataset
 
@@ -318,11 +331,11 @@ def get_dataset(storage_options, colmap_options=None, pipeline_options=None, res
     pipeline_options = pipeline_options or PipelineOptions()
     dataset_path, output_path = str(storage_options.dataset_path), str(storage_options.output_path)
     if not storage_options.no_cache and HiveDataset.is_valid_folder_structure(output_path):
-        return _open_hive_folder(output_path, pipeline_options.inpainting_mode, profiling)
+        return _open_hive_folder(output_path, pipeline_options.inpainting_mode, profiling, pipeline_options.png_encoder)
     base = dict(base_path=dataset_path, output_path=output_path, num_frames=pipeline_options.num_frames, frame_step=pipeline_options.frame_step,
                 colmap_options=colmap_options)
     if HiveDataset.is_valid_folder_structure(dataset_path):
-        return _open_hive_folder(dataset_path, pipeline_options.inpainting_mode, profiling)
+        return _open_hive_folder(dataset_path, pipeline_options.inpainting_mode, profiling, pipeline_options.png_encoder)
     if TUMAdaptor.is_valid_folder_structure(dataset_path):
         converter = TUMAdaptor(**base)
     elif UnrealAdaptor.is_valid_folder_structure(dataset_path):
@@ -338,4 +351,4 @@ def get_dataset(storage_options, colmap_options=None, pipeline_options=None, res
         raise RuntimeError(f"Could not recognise the dataset format for the dataset at {dataset_path}.")
     return converter.convert(estimate_pose=pipeline_options.estimate_pose, estimate_depth=pipeline_options.estimate_depth,
                              inpainting_mode=pipeline_options.inpainting_mode, static_camera=pipeline_options.static_camera,
-                             no_cache=storage_options.no_cache, profiling=profiling)
+                             no_cache=storage_options.no_cache, profiling=profiling, png_encoder=pipeline_options.png_encoder)

@@ -97,7 +97,27 @@ def _write_png16(path, depth_mm_u16):
     Image.fromarray(np.ascontiguousarray(depth_mm_u16, dtype=np.uint16)).save(path)  # uint16 -> 16-bit PNG
 
 
-def estimate_depth_dpt(rgb_dataset, output_path: str, weights_filename='dpt_hybrid_nyu.pt', optimize=True, batch_size=8, dtype=None):
+def write_depth_pngs(depth_mm_device, paths, ctx=None, writers=None):
+    """Write the uint16 millimetre maps ``depth_mm_device`` ([B, H, W] on the GPU, uint16 or the int16 view of it that ``forward_frames`` returns) as 16-bit
+    PNG files at ``paths`` without bringing their pixels to the host: one ``hive_amd.png.encode`` call for the batch, one download of the compressed bytes,
+    then plain file writes -- through the executor ``writers`` if one is given (its futures are returned), else here.  Any PNG reader gives the pixels
+    ``_write_png16`` files give; the bytes are the device encoder's."""
+    from hive_amd import png
+    if not depth_mm_device.is_cuda or depth_mm_device.dim() != 3 or depth_mm_device.dtype not in (torch.int16, torch.uint16):
+        raise ValueError(f"depth_mm_device: a [B, H, W] uint16 (or int16-viewed) tensor on the GPU, got {depth_mm_device.dtype} {tuple(depth_mm_device.shape)}")
+    paths = list(paths)
+    if len(paths) != depth_mm_device.shape[0]:
+        raise ValueError(f"{len(paths)} paths for {depth_mm_device.shape[0]} depth maps")
+    maps = depth_mm_device.view(torch.uint16)
+    files = png.encode([maps[j] for j in range(len(paths))], ctx=ctx)
+    if writers is None:
+        for path, data in zip(paths, files):
+            png.write_file(path, data)
+        return []
+    return [writers.submit(png.write_file, path, data) for path, data in zip(paths, files)]
+
+
+def estimate_depth_dpt(rgb_dataset, output_path: str, weights_filename='dpt_hybrid_nyu.pt', optimize=True, batch_size=8, dtype=None, png_encoder="host"):
     """Estimate a depth map for every frame of ``rgb_dataset`` and write it as ``%06d.png`` (16-bit,
     millimetres) into ``output_path`` -- the side effect on disk is the contract
     (dataset_adaptors.py:1346-1435).  Frames are batched on the GPU (the reference runs them one by
@@ -108,7 +128,12 @@ def estimate_depth_dpt(rgb_dataset, output_path: str, weights_filename='dpt_hybr
     float16 on the HIP engine (``dtype=torch.bfloat16`` selects the bfloat16 kernels instead: wider range, 3 bits less
     precision).  ``optimize=False`` is the reference's float32 network: PyTorch operators (``engine="torch"``), stated here, not
     a silent substitute -- the HIP engine computes in 16-bit types only.
+
+    ``png_encoder="gpu"``: the maps of a batch that went through ``forward_frames`` are compressed where it left them (``write_depth_pngs``: csrc/png.hip) and the
+    writer threads only write files; the files decode to the same pixels, their bytes are the device encoder's.  The default ``"host"`` is Pillow, as before.
     """
+    from hive_amd import png as png_module
+    png_module.check_encoder(png_encoder)
     weights_dir = os.environ.get('WEIGHTS_PATH', 'weights')
     model_path = os.path.join(weights_dir, weights_filename)
     if not os.path.isfile(model_path):
@@ -148,7 +173,7 @@ def estimate_depth_dpt(rgb_dataset, output_path: str, weights_filename='dpt_hybr
                     frames = torch.from_numpy(np.stack(images)).cuda()
                     h, w = images[0].shape[:2]
                     _, mm, _ = model.forward_frames(frames, max_depth=65.535, net_size=network_size(h, w))
-                    depth_mm = mm.cpu().numpy().view(np.uint16)
+                    depth_mm = mm if png_encoder == "gpu" else mm.cpu().numpy().view(np.uint16)
                 else:  # optimize=False (PyTorch float32) or frames that are not uint8 RGB of one size: the host transform, frame by frame
                     preds = []
                     for im in images:
@@ -160,7 +185,10 @@ def estimate_depth_dpt(rgb_dataset, output_path: str, weights_filename='dpt_hybr
                             prediction = torch.nn.functional.interpolate(prediction.unsqueeze(1), size=im.shape[:2], mode="nearest").squeeze(1)
                         preds.append((prediction[0] * 1000.0).clamp(0, 65535).to(torch.int32).cpu().numpy().astype(np.uint16))
                     depth_mm = preds
-                pending.append(write_batch(start, depth_mm))
+                if torch.is_tensor(depth_mm):  # png_encoder="gpu": still on the device
+                    pending.append(write_depth_pngs(depth_mm, [os.path.join(output_path, f"{start + j:06d}.png") for j in range(len(images))], writers=writers))
+                else:
+                    pending.append(write_batch(start, depth_mm))
                 while len(pending) > 4:
                     for f in pending.pop(0):
                         f.result()

@@ -201,17 +201,20 @@ def camera_json(camera):
             "extras": {"resolution": [w, h], "focal": [fx, fy]}}
 
 
-def write_glb(path, scene, quantize=False, lut=None, ctx=None, timings=None, texture_format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
+def write_glb(path, scene, quantize=False, lut=None, ctx=None, timings=None, texture_format="png", jpeg_quality=90, jpeg_subsampling="4:2:0", png_encoder="host"):
     """Write the scene as one binary glTF 2.0 file.  Geometry: layout, pack, ONE device-to-host copy.  Every textured mesh gets its atlas as an embedded PNG with
     one image, texture and material (``baseColorTexture`` only); with ``texture_format="jpeg"`` the atlases are baseline JPEG files (``image/jpeg``) of
     ``jpeg_quality`` and ``jpeg_subsampling``, all encoded on the device in one call (``hive_amd.jpeg.encode``) and downloaded once, and ``timings`` gets a
-    ``jpeg`` key in place of ``png``.  One scene; its root node ``"world"`` carries the scene transform as a column-major ``matrix``
+    ``jpeg`` key in place of ``png``.  ``png_encoder="gpu"`` (with ``texture_format="png"``): the PNG files are compressed on the device too
+    (``hive_amd.png.encode``: the same pixels, the device encoder's bytes), all atlases in one call; the default ``"host"`` is Pillow.  One scene; its root node ``"world"`` carries the scene transform as a column-major ``matrix``
     (and the camera), its children are the scene's nodes in order.  Meshes without faces are left out.  ``quantize``: KHR_mesh_quantization (uint16 positions
     under a node scale / translation, uint16 uv, uint16 indices up to 65535 vertices).  ``lut``: 256 bytes applied to the RGB of vertex colours.  Returns the
     byte counts per kind (``geometry``, ``images``, ``json``, ``total``).  ``timings``: a dict that receives the seconds of pack, download, png and file write."""
     import time
     if texture_format not in TEXTURE_FORMATS:
         raise ValueError(f"texture_format {texture_format!r} is not one of {TEXTURE_FORMATS}")
+    from hive_amd import png as png_module
+    png_module.check_encoder(png_encoder)
     if texture_format == "jpeg":
         from hive_amd import jpeg
         jpeg.check_settings(jpeg_quality, jpeg_subsampling)
@@ -283,14 +286,16 @@ def write_glb(path, scene, quantize=False, lut=None, ctx=None, timings=None, tex
         lap("json")
         textured = [k for k in range(len(drawn)) if views[k, _lib.GLTF_TEXCOORD, 1]]
         encoded = {}
-        if texture_format == "jpeg" and textured:
+        if textured and (texture_format == "jpeg" or png_encoder == "gpu"):
             atlases = [mesh_fields(drawn[k][1])[3] for k in textured]
-            encoded = dict(zip(textured, jpeg.encode([a if a.shape[2] == 3 else a[:, :, :3] for a in atlases], jpeg_quality, jpeg_subsampling, ctx)))
+            atlases = [a if a.shape[2] == 3 else a[:, :, :3] for a in atlases]
+            files = jpeg.encode(atlases, jpeg_quality, jpeg_subsampling, ctx) if texture_format == "jpeg" else png_module.encode(atlases, ctx)
+            encoded = dict(zip(textured, files))
         for k, (name, m) in enumerate(drawn):
             texture = mesh_fields(m)[3]
             if not views[k, _lib.GLTF_TEXCOORD, 1]:
                 continue
-            png = encoded[k] if texture_format == "jpeg" else _png_bytes(texture)
+            png = encoded[k] if k in encoded else _png_bytes(texture)
             for key in ("images", "textures", "materials"):
                 doc.setdefault(key, [])
             doc["images"].append({"bufferView": add_view(len(binary), len(png)), "mimeType": "image/" + texture_format})

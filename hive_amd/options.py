@@ -442,14 +442,17 @@ class PipelineOptions(Options):
               _Flag('export_gltf', 'export_gltf', bool, False, 'centre the scenes and write mesh/fg.glb, mesh/bg.glb and metadata.json, then export them to --webxr_path'),
               _Flag('texture_format', 'texture_format', str, 'png', 'how --export_gltf embeds the textures of fg.glb: png (host encoder) or jpeg (baseline JPEG encoded on the GPU)',
                     ('png', 'jpeg')),
-              _Flag('jpeg_quality', 'jpeg_quality', int, 90, 'quality (1 .. 100) of --texture_format jpeg'))
+              _Flag('jpeg_quality', 'jpeg_quality', int, 90, 'quality (1 .. 100) of --texture_format jpeg'),
+              _Flag('png_encoder', 'png_encoder', str, 'host', 'who compresses the PNG files of depth estimation, frame inpainting and --texture_format png: host (Pillow / zlib) '
+                    'or gpu (the same pixels, the device encoder\'s bytes)', ('host', 'gpu')))
 
     def __init__(self, num_frames=-1, frame_step=15, estimate_pose=False, estimate_depth=False, background_only=False, static_camera=False,
                  align_scene=False, inpainting_mode=InpaintingMode.Off, billboard=False, disable_scaling=False, disable_coverage_constraint=False,
-                 log_file='logs.log', export_gltf=False, texture_format='png', jpeg_quality=90):
+                 log_file='logs.log', export_gltf=False, texture_format='png', jpeg_quality=90, png_encoder='host'):
         self.export_gltf = export_gltf
         self.texture_format = texture_format
         self.jpeg_quality = jpeg_quality
+        self.png_encoder = png_encoder
         self.disable_scaling = disable_scaling
         self.disable_coverage_constraint = disable_coverage_constraint
         self.num_frames = num_frames

@@ -240,18 +240,20 @@ class Pipeline:
 
     @classmethod
     def _write_meshes_to_disk(cls, mesh_path: str, foreground_scene, background_scene, overwrite_ok=False, quantize=False, background_lut=None, texture_format="png",
-                              jpeg_quality=90):
+                              jpeg_quality=90, png_encoder="host"):
         """pipeline.py:902-919 -> (path of fg.glb, path of bg.glb).  (The folder already holds this run's PLY files, so unlike the reference's it is made with
         ``exist_ok=True``; ``overwrite_ok`` guards the export folder, ``_export_video_webxr``.)"""
         os.makedirs(mesh_path, exist_ok=True)
-        return (cls._write_mesh_to_disk(mesh_path, "fg", foreground_scene, quantize=quantize, texture_format=texture_format, jpeg_quality=jpeg_quality),
-                cls._write_mesh_to_disk(mesh_path, "bg", background_scene, quantize=quantize, lut=background_lut, texture_format=texture_format, jpeg_quality=jpeg_quality))
+        return (cls._write_mesh_to_disk(mesh_path, "fg", foreground_scene, quantize=quantize, texture_format=texture_format, jpeg_quality=jpeg_quality,
+                                        png_encoder=png_encoder),
+                cls._write_mesh_to_disk(mesh_path, "bg", background_scene, quantize=quantize, lut=background_lut, texture_format=texture_format, jpeg_quality=jpeg_quality,
+                                        png_encoder=png_encoder))
 
     @classmethod
-    def _write_mesh_to_disk(cls, base_folder: str, scene_name: str, scene, quantize=False, lut=None, texture_format="png", jpeg_quality=90) -> str:
+    def _write_mesh_to_disk(cls, base_folder: str, scene_name: str, scene, quantize=False, lut=None, texture_format="png", jpeg_quality=90, png_encoder="host") -> str:
         """pipeline.py:921-936: ``<base_folder>/<scene_name>.glb`` through ``gltf.write_glb``; the textures as ``options.texture_format`` says (PNG unless asked)."""
         output_path = os.path.join(base_folder, f"{scene_name}.glb")
-        sizes = gltf.write_glb(output_path, scene, quantize=quantize, lut=lut, texture_format=texture_format, jpeg_quality=jpeg_quality)
+        sizes = gltf.write_glb(output_path, scene, quantize=quantize, lut=lut, texture_format=texture_format, jpeg_quality=jpeg_quality, png_encoder=png_encoder)
         logging.info(f"Wrote mesh data to {output_path} ({sizes['total']} bytes)")
         return output_path
 
@@ -261,7 +263,8 @@ class Pipeline:
         the plain file's format (``options.texture_format``)."""
         src_path = Path(path_to_glb)
         tmp_path = src_path.with_name(f"{src_path.stem}_tmp{src_path.suffix}")
-        gltf.write_glb(str(tmp_path), scene, quantize=True, lut=lut, texture_format=self.options.texture_format, jpeg_quality=self.options.jpeg_quality)
+        gltf.write_glb(str(tmp_path), scene, quantize=True, lut=lut, texture_format=self.options.texture_format, jpeg_quality=self.options.jpeg_quality,
+                       png_encoder=self.options.png_encoder)
         size_before, size_after = os.path.getsize(src_path), os.path.getsize(tmp_path)
         shutil.move(str(tmp_path), str(src_path))
         name = {"fg": "foreground", "bg": "background"}.get(src_path.stem, src_path.stem)
@@ -319,7 +322,7 @@ class Pipeline:
             if adaptor is not None:
                 dataset = adaptor.convert(estimate_pose=self.estimate_pose, estimate_depth=self.estimate_depth, inpainting_mode=self.options.inpainting_mode,
                                           static_camera=self.options.static_camera, no_cache=bool(self.storage_options and self.storage_options.no_cache),
-                                          profiling=self.profiling)
+                                          profiling=self.profiling, png_encoder=self.options.png_encoder)
             elif dataset is None:
                 resize_to = None if self.options.disable_scaling else 640
                 dataset = get_dataset(self.storage_options, self.colmap_options, self.options, resize_to=resize_to, profiling=self.profiling)
@@ -355,7 +358,8 @@ class Pipeline:
         ply_seconds = self.profiling.get("timing", {}).get("mesh_export", 0.0)
         with timed_block("Wrote glTF data in", self.profiling, ("timing", "mesh_export")):
             fg_path, bg_path = self._write_meshes_to_disk(mesh_path, foreground_scene, background_scene, overwrite_ok=self.storage_options.overwrite_ok,
-                                                          background_lut=lut, texture_format=self.options.texture_format, jpeg_quality=self.options.jpeg_quality)
+                                                          background_lut=lut, texture_format=self.options.texture_format, jpeg_quality=self.options.jpeg_quality,
+                                                          png_encoder=self.options.png_encoder)
         self.profiling["timing"]["mesh_export"] += ply_seconds
         with timed_block("Compressed mesh data in", self.profiling, ("timing", "mesh_compression", "total")):
             with timed_block("Quantised the foreground scene in", self.profiling, ("timing", "mesh_compression", "foreground")):

@@ -907,6 +907,47 @@ int hive_jpeg_layout(const hive_jpeg_image *images, int n, int subsampling, int6
  * per call.  Returns after the device has finished (the sizes come back in one small copy). */
 int hive_jpeg_encode(hive_ctx *ctx, const hive_jpeg_image *images, int n, int quality, int subsampling, uint8_t *d_out, int64_t out_bytes, int64_t *sizes);
 
+/* ---- PNG: depth maps, masks and textures encoded on the device -- csrc/png.hip.  Lossless: the decoded pixels are the input's; the bytes are this encoder's own
+ * (not zlib's, not Pillow's) and a function of the picture's bytes alone: the same on every run, for a picture alone or anywhere in a batch.
+ * tests/png_restatement.py states the same rules in numpy.  Integer arithmetic only.
+ *   file       signature, IHDR (no interlace), ONE IDAT, IEND.  Gray 8 / gray 16 (colour type 0; 16-bit samples most significant byte first) / RGB 8 (type 2).
+ *   IDAT       one zlib stream: 78 01, the deflate blocks, the Adler-32 of the filtered rows.  Chunk CRC-32s and the Adler-32 are combined on the device from
+ *              per-segment parts by the bytes that follow each part; nothing walks the bytes serially.
+ *   filter     per row all five filters against the RAW row above (zeros above the first); the smallest sum of |signed byte| wins, ties to the lowest type.
+ *              Stated, and not pinned against Pillow's filter heuristic (equal on smooth pictures, not on noisy ones).
+ *   segments   the filtered stream (a filter byte in front of every row) is cut every S = 8192 bytes; a segment becomes ONE dynamic block (BTYPE 2), or one
+ *              stored block where the dynamic coding below is not smaller than 5 + its bytes.  Noise never expands beyond the stored form.
+ *   joining    byte-aligned: behind every dynamic block but the last an EMPTY stored block (000, zeros up to the byte, 00 00 FF FF).  The last block carries
+ *              BFINAL and is padded with zeros.
+ *   matches    at position p (room = min(258, bytes to the end of p's segment)) three candidate distances: the bytes of one pixel; one row (row bytes + 1);
+ *              p minus the nearest earlier position whose three bytes equal p's three (exact equality, from a stable sort of the positions by those bytes; p's
+ *              three bytes must lie inside the picture).  A candidate counts if 1 <= distance <= min(p, 32768); its length is the run of equal bytes, which may
+ *              reach back into earlier segments and overlap p, never past room; under 3, or exactly 3 further than 4096 back, it is no match.  The longest
+ *              wins, ties to the smaller distance.
+ *   parse      greedy from the segment's start: a match where there is one (skip its length), else a literal.
+ *   codes      lengths by Huffman's algorithm: leaves in order of (count, symbol); always join the two smallest of (next leaf, oldest joined node), a leaf
+ *              before a node of equal weight.  Deeper than the limit (15; 7 for the code-length code): every used count becomes (count + 1) >> 1 and the tree
+ *              is built again.  An alphabet with fewer than two used symbols (a block with one distance code, or none) gives a count of 1 to its lowest unused
+ *              symbols until two are used, so every table sent is complete.  Codes are canonical (RFC 1951 3.2.2).
+ *   header     HLIT / HDIST are trimmed to the last used symbol (at least 257 / 1); the code lengths are sent ONE BY ONE: the repeat symbols 16, 17, 18 are
+ *              not used; HCLEN is trimmed (at least 4). */
+typedef enum hive_png_kind { HIVE_PNG_GRAY8 = 0, HIVE_PNG_GRAY16 = 1, HIVE_PNG_RGB8 = 2 } hive_png_kind;
+typedef struct hive_png_image {
+    const void *pixels; /* device [height][pitch] bytes: width pixels at the start of every row; uint16 samples in host byte order */
+    int32_t height, width;
+    int64_t pitch;      /* bytes from one row to the next, >= width * bytes per pixel (1, 2, 3) */
+    int32_t kind;       /* hive_png_kind */
+} hive_png_image;
+/* Host only (no context, no device) -> offsets[n], each a multiple of 4, and *total_bytes: room for the WORST case of every file, which is all segments stored:
+ * 63 bytes of frame (signature 8, IHDR 25, IDAT's length / type / CRC 12, zlib header 2, Adler-32 4, IEND 12) + the filtered stream H * (1 + row bytes) + 5 per
+ * segment of 8192, up to a multiple of 4.  Fails on n < 1, an unknown kind, a side of 0 or above 65535, more than 2^27 stream bytes; the message is
+ * hive_last_error(NULL). */
+int hive_png_layout(const hive_png_image *images, int n, int64_t *offsets, int64_t *total_bytes);
+/* Fourteen launches for any n behind ONE upload of the picture table: file i goes to d_out + offsets[i] (device; out_bytes >= the layout's total, or the call
+ * fails naming the bytes needed, before any launch; nothing is ever written past out_bytes), its length to sizes[i] (host).  At most 2^27 bytes of filtered
+ * stream per call.  Returns after the device has finished (the sizes come back in one small copy). */
+int hive_png_encode(hive_ctx *ctx, const hive_png_image *images, int n, uint8_t *d_out, int64_t out_bytes, int64_t *sizes);
+
 /* ---- depth hand-off DPT -> TSDF ----------------------------------------------------- */
 /* dataset_adaptors.py:1432-1433 (x1000 -> uint16 truncation) then io.py:1032-1039
  * (x 1/1000 as float32, > max_depth -> 0), optional mask (non-zero -> depth 0, fusion.py:121).
