@@ -9,13 +9,13 @@
 //
 // One upload carries the whole descriptor table: the segments (one per buffer view: source, destination, the elements before it), the meshes of the bounds pass
 // (the chunks before each), the colour table and the two error words.
-//   bounds        one workgroup per CHUNK of 1024 vertices of one mesh (found by binary search in the chunk prefix): a thread takes vertices chunk * 1024 + j * 256
+//   bounds        one workgroup per CHUNK of 1024 vertices of one mesh (found in the chunk prefix by hive_internal.hpp's last_not_after): a thread takes vertices chunk * 1024 + j * 256
 //                 + thread, j = 0 .. 3, the 64 lanes combine in a butterfly, the four waves through LDS -> partial[chunk] = {min xyz, max xyz}.  A vertex that is
 //                 not finite lowers error word 0 to its mesh (integer atomic minimum).
 //   bounds, final one workgroup per MESH over its chunks' partials (thread k takes chunks k, k + 256, ..) -> bounds[mesh] = {lo xyz, hi xyz, s xyz}, s the
 //                 quantisation step (hi - lo) / 65535.0, 1.0 on a flat axis.
 //   pack          one thread per output ELEMENT (a vertex of POSITION / TEXCOORD_0 / COLOR_0, a face of the indices) over the concatenated element ranges of all
-//                 segments, its segment found by binary search in the element prefix.  An index outside [0, V) lowers error word 1 to its mesh.
+//                 segments, its segment found in the element prefix the same way.  An index outside [0, V) lowers error word 1 to its mesh.
 // The kernels are memory-bound: a vertex is read once per attribute and written once; stores are plain 16- and 32-bit C++ stores (views are 4-byte aligned,
 // uint16 indices 2-byte aligned).
 #include "hive_internal.hpp"
@@ -77,14 +77,7 @@ __global__ __launch_bounds__(GL_THREADS) void gltf_bounds_kernel(const GltfBound
                                                                  unsigned *__restrict__ flags) {
     __shared__ double lds[GL_THREADS / 64][6];
     const long long chunk = blockIdx.x;
-    int lo = 0, hi = n_meshes - 1;  // the last mesh whose first chunk is not after this one
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_chunk <= chunk)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
+    const int lo = last_not_after(n_meshes, chunk, [meshes](int i) { return meshes[i].first_chunk; });  // the mesh that holds this chunk
     const GltfBoundsMesh mesh = meshes[lo];
     double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
     bool bad = false;
@@ -134,15 +127,7 @@ __global__ __launch_bounds__(GL_THREADS) void gltf_pack_kernel(const GltfSeg *__
                                                                const uint8_t *__restrict__ lut, const double *__restrict__ bounds, unsigned *__restrict__ flags) {
     const long long e = (long long)blockIdx.x * GL_THREADS + threadIdx.x;
     if (e >= total) return;
-    int lo = 0, hi = n_segs - 1;  // the last segment that does not start after this element
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (segs[mid].first <= e)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    const GltfSeg s = segs[lo];
+    const GltfSeg s = segs[last_not_after(n_segs, e, [segs](int i) { return segs[i].first; })];  // the segment that holds this element
     const long long i = e - s.first;
     if (s.kind == HIVE_GLTF_POSITION) {
         if (!quantize) {

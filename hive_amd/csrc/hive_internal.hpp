@@ -188,6 +188,52 @@ __device__ __forceinline__ unsigned block_exclusive(unsigned c, unsigned *lds) {
     __syncthreads();
     return before + inc - c;
 }
+// block_exclusive, and the workgroup's total in *total (every thread gets it)
+__device__ __forceinline__ unsigned block_exclusive_total(unsigned c, unsigned *lds, unsigned *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = c;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = (unsigned)__shfl_up((int)inc, off);
+        if (lane >= off) inc += o;
+    }
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+    for (int w = 0; w < 256 / 64; ++w) {
+        if (w < wave) before += lds[w];
+        all += lds[w];
+    }
+    __syncthreads();
+    *total = all;
+    return before + inc - c;
+}
+// A 256-thread workgroup scans `count` values 256 at a time: store(i, the sum of load(0 .. i - 1)) for every i < count; returns the sum of all (in every
+// thread).  Every thread of the workgroup calls it with the same count
+template <class Load, class Store>
+__device__ __forceinline__ unsigned block_scan_chunks(unsigned count, unsigned *lds, Load load, Store store) {
+    unsigned carry = 0;
+    for (unsigned base = 0; base < count; base += 256) {
+        const unsigned i = base + threadIdx.x;
+        unsigned chunk;
+        const unsigned at = block_exclusive_total(i < count ? load(i) : 0u, lds, &chunk);
+        if (i < count) store(i, carry + at);
+        carry += chunk;
+    }
+    return carry;
+}
+// the last of n >= 1 table rows whose first element first_of(row) is not after `at` (rows ascend; row 0 starts at or before every `at` asked for)
+template <class At, class FirstOf>
+__device__ __forceinline__ int last_not_after(int n, At at, FirstOf first_of) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first_of(mid) <= at)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
 // regions of one block of device scratch, 256-byte aligned, in the order they are taken.  With a null base the layout only sizes: take() returns
 // null, bytes() is what to reserve; the same takes over the reserved block then give the pointers.
 struct hive_scratch_layout {
@@ -201,6 +247,32 @@ struct hive_scratch_layout {
     }
     size_t bytes() const { return off; }
 };
+// ---- the host frame the picture encoders share (jpeg.hip, png.hip); `name` is "jpeg" / "png" in the error texts ----
+inline int hive_picture_sides(hive_ctx *ctx, const char *name, int i, int height, int width) {
+    HIVE_REQUIRE(ctx, height >= 1 && height <= 65535 && width >= 1 && width <= 65535, "%s: picture %d is %d x %d (sides of 1 .. 65535)", name, i, height, width);
+    return HIVE_OK;
+}
+inline int hive_picture_room(hive_ctx *ctx, const char *name, int64_t out_bytes, int64_t total_bytes) {
+    HIVE_REQUIRE(ctx, out_bytes >= total_bytes, "%s_encode: out_bytes = %lld is too small: hive_%s_layout asks for %lld bytes", name, (long long)out_bytes, name,
+                 (long long)total_bytes);
+    return HIVE_OK;
+}
+// the picture table and, behind it in the same block of scratch, the tables struct: one upload
+template <class Row, class Tables>
+int hive_upload_tables(hive_ctx *ctx, Row *d_rows, const std::vector<Row> &rows, Tables *d_tab, const Tables &tables) {
+    const size_t tab_at = (size_t)((char *)d_tab - (char *)d_rows);
+    std::vector<uint8_t> both(tab_at + sizeof(Tables), 0);
+    memcpy(both.data(), rows.data(), rows.size() * sizeof(Row));
+    memcpy(both.data() + tab_at, &tables, sizeof(Tables));
+    return hive_upload(ctx, d_rows, both.data(), both.size());
+}
+// behind the launches: the files' sizes into the caller's array, and the stream drained
+inline int hive_read_sizes(hive_ctx *ctx, const long long *d_sizes, int n, int64_t *sizes) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the kernels write long long, the caller reads int64_t");
+    HIVE_CHECK_HIP(ctx, hipMemcpyAsync(sizes, d_sizes, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return HIVE_OK;
+}
 // decimate.hip: quadric edge collapse of a device-resident mesh (hive_mesh_decimate), for the entry points of any translation unit
 struct hive_dec_job {
     const double *pos;                   // [V][3]

@@ -24,7 +24,9 @@
 //   picture scan   one workgroup per picture: exclusive scan of its intervals' lengths -> where each goes, the file's size, and the header.
 //   stuff          one workgroup per interval: every byte to its place behind the 0xFF bytes before it (a block scan per 256 bytes), a 0x00 behind each 0xFF,
 //                  then RSTn or EOI.
-// The kernels move bytes and small integers; none is compute-bound.
+// The kernels move bytes and small integers; none is compute-bound.  The scans and the search are hive_internal.hpp's: block_scan_chunks (block scan, picture
+// scan), block_exclusive_total (stuff: the 0xFF count of a chunk is carried in a register) and last_not_after (the picture of an MCU or an interval); the
+// host frame -- the one upload, the sizes' read-back, the checks of the sides and of out_bytes -- is shared with png.hip through the same header.
 #include "hive_internal.hpp"
 
 #include <algorithm>
@@ -67,18 +69,12 @@ const unsigned char ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25
 __constant__ unsigned char JP_ZIGZAG_OF[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
                                                10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
 
-// the last picture whose first MCU / interval is not after `at`
-template <bool BY_INTERVAL>
-__device__ __forceinline__ int jp_find(const JpegPic *__restrict__ pics, int n, int at) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((BY_INTERVAL ? pics[mid].first_interval : pics[mid].first_mcu) <= at)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
+// the picture that holds MCU / interval `at` of the call
+__device__ __forceinline__ int jp_picture_of_mcu(const JpegPic *__restrict__ pics, int n, int at) {
+    return last_not_after(n, at, [pics](int i) { return pics[i].first_mcu; });
+}
+__device__ __forceinline__ int jp_picture_of_interval(const JpegPic *__restrict__ pics, int n, int at) {
+    return last_not_after(n, at, [pics](int i) { return pics[i].first_interval; });
 }
 
 // JFIF colour conversion in 16-bit fixed point: component 0 Y, 1 Cb, 2 Cr
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_transform_kernel(const JpegPi
         const int mcu = blockIdx.x * MPG + tid / BPM, k = tid % BPM;
         int pic = 0, bx = 0, by = 0, flags = 0;
         if (mcu < total_mcus) {
-            pic = jp_find<false>(pics, n_pics, mcu);
+            pic = jp_picture_of_mcu(pics, n_pics, mcu);
             const JpegPic P = pics[pic];
             const int local = mcu - P.first_mcu, mx = local % P.mcus_x, my = local / P.mcus_x;
             flags = JP_VALID;
@@ -247,7 +243,7 @@ template <int SUB>
 __device__ __forceinline__ JpBlock jp_block(const JpegPic *__restrict__ pics, int n_pics, const short *__restrict__ coef, long long g, int lane) {
     constexpr int BPM = SUB ? 6 : 3;
     const int mcu = (int)(g / BPM), k = (int)(g % BPM);
-    const JpegPic P = pics[jp_find<false>(pics, n_pics, mcu)];
+    const JpegPic P = pics[jp_picture_of_mcu(pics, n_pics, mcu)];
     const int local = mcu - P.first_mcu, mx = local % P.mcus_x;
     long long pred = -1;  // the previous block of the same component in the interval
     if (SUB && k >= 1 && k <= 3)
@@ -284,22 +280,11 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_block_scan_kernel(const JpegP
                                                                      unsigned *__restrict__ block_off, unsigned *__restrict__ interval_bits) {
     constexpr int BPM = SUB ? 6 : 3;
     __shared__ unsigned lds[JP_THREADS / 64];
-    __shared__ unsigned chunk_total;
-    const JpegPic P = pics[jp_find<true>(pics, n_pics, blockIdx.x)];
+    const JpegPic P = pics[jp_picture_of_interval(pics, n_pics, blockIdx.x)];
     const long long first = ((long long)P.first_mcu + (long long)(blockIdx.x - P.first_interval) * P.mcus_x) * BPM;
-    const int count = P.mcus_x * BPM;
-    unsigned carry = 0;
-    for (int base = 0; base < count; base += JP_THREADS) {
-        const int i = base + threadIdx.x;
-        const unsigned c = i < count ? block_bits[first + i] : 0u;
-        const unsigned at = block_exclusive(c, lds);
-        if (i < count) block_off[first + i] = carry + at;
-        if (threadIdx.x == JP_THREADS - 1) chunk_total = at + c;
-        __syncthreads();
-        carry += chunk_total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) interval_bits[blockIdx.x] = carry;
+    const unsigned bits = block_scan_chunks((unsigned)(P.mcus_x * BPM), lds, [&](unsigned i) { return block_bits[first + i]; },
+                                            [&](unsigned i, unsigned at) { block_off[first + i] = at; });
+    if (threadIdx.x == 0) interval_bits[blockIdx.x] = bits;
 }
 
 // n <= 27 bits of v at bit `pos` of a stream whose 32-bit words hold their bits most significant first
@@ -353,7 +338,7 @@ template <int SUB>
 __device__ __forceinline__ JpInterval jp_interval(const JpegPic *__restrict__ pics, int n_pics, const unsigned *__restrict__ stream, int interval) {
     constexpr int BPM = SUB ? 6 : 3;
     JpInterval o;
-    o.P = pics[jp_find<true>(pics, n_pics, interval)];
+    o.P = pics[jp_picture_of_interval(pics, n_pics, interval)];
     o.local = interval - o.P.first_interval;
     o.last = o.local == o.P.mcus_y - 1;
     o.stream = stream + ((long long)o.P.first_mcu + (long long)o.local * o.P.mcus_x) * BPM * JP_BLOCK_WORDS;
@@ -381,20 +366,10 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_picture_scan_kernel(const Jpe
                                                                        const unsigned *__restrict__ interval_bytes, unsigned *__restrict__ interval_off,
                                                                        uint8_t *__restrict__ out, long long *__restrict__ sizes) {
     __shared__ unsigned lds[JP_THREADS / 64];
-    __shared__ unsigned chunk_total;
     const JpegPic P = pics[blockIdx.x];
-    unsigned carry = 0;
-    for (int base = 0; base < P.mcus_y; base += JP_THREADS) {
-        const int i = base + threadIdx.x;
-        const unsigned c = i < P.mcus_y ? interval_bytes[P.first_interval + i] : 0u;
-        const unsigned at = block_exclusive(c, lds);
-        if (i < P.mcus_y) interval_off[P.first_interval + i] = carry + at;
-        if (threadIdx.x == JP_THREADS - 1) chunk_total = at + c;
-        __syncthreads();
-        carry += chunk_total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sizes[blockIdx.x] = (long long)JP_HEADER + carry;
+    const unsigned scan_bytes = block_scan_chunks((unsigned)P.mcus_y, lds, [&](unsigned i) { return interval_bytes[P.first_interval + i]; },
+                                                  [&](unsigned i, unsigned at) { interval_off[P.first_interval + i] = at; });
+    if (threadIdx.x == 0) sizes[blockIdx.x] = (long long)JP_HEADER + scan_bytes;
     uint8_t *dst = out + P.out_off;
     for (int i = threadIdx.x; i < JP_HEADER; i += JP_THREADS) {
         unsigned b = tab->header[i];
@@ -411,7 +386,6 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_stuff_kernel(const JpegPic *_
                                                                 const unsigned *__restrict__ interval_bits, const unsigned *__restrict__ interval_off,
                                                                 uint8_t *__restrict__ out) {
     __shared__ unsigned lds[JP_THREADS / 64];
-    __shared__ unsigned chunk_total;
     const JpInterval I = jp_interval<SUB>(pics, n_pics, stream, blockIdx.x);
     const unsigned bits = interval_bits[blockIdx.x], nbytes = (bits + 7u) >> 3;
     const long long at = (long long)JP_HEADER + interval_off[blockIdx.x];
@@ -421,16 +395,14 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_stuff_kernel(const JpegPic *_
     for (unsigned base = 0; base < nbytes; base += JP_THREADS) {
         const unsigned j = base + threadIdx.x;
         const unsigned b = j < nbytes ? jp_byte(I.stream, j, nbytes, bits) : 0u, ff = b == 255u;
-        const unsigned before = block_exclusive(ff, lds);
+        unsigned chunk_ff;
+        const unsigned before = block_exclusive_total(ff, lds, &chunk_ff);
         const long long pos = (long long)j + carry + before;
         if (j < nbytes && pos + ff < room) {
             dst[pos] = (uint8_t)b;
             if (ff) dst[pos + 1] = 0;
         }
-        if (threadIdx.x == JP_THREADS - 1) chunk_total = before + ff;
-        __syncthreads();
-        carry += chunk_total;
-        __syncthreads();
+        carry += chunk_ff;
     }
     if (threadIdx.x == 0 && (long long)nbytes + carry + 1 < room) {
         dst[nbytes + carry] = 0xFF;
@@ -540,8 +512,7 @@ int jpeg_layout(hive_ctx *ctx, const hive_jpeg_image *images, int n, int subsamp
     int64_t at = 0;
     for (int i = 0; i < n; ++i) {
         const hive_jpeg_image &im = images[i];
-        HIVE_REQUIRE(ctx, im.height >= 1 && im.height <= 65535 && im.width >= 1 && im.width <= 65535, "jpeg: picture %d is %d x %d (sides of 1 .. 65535)", i, im.height,
-                     im.width);
+        if (int rc = hive_picture_sides(ctx, "jpeg", i, im.height, im.width)) return rc;
         const JpegGrid g = jpeg_grid(im, subsampling == HIVE_JPEG_420);
         if (offsets) offsets[i] = at;
         at += (JP_HEADER + g.blocks * (2 * JP_BLOCK_WORDS * 4) + g.mcus_y * 2 + 3) & ~(int64_t)3;
@@ -589,8 +560,7 @@ int hive_jpeg_encode(hive_ctx *ctx, const hive_jpeg_image *images, int n, int qu
     int64_t total_bytes = 0;
     int rc;
     if ((rc = jpeg_layout(ctx, images, n, subsampling, offsets.data(), &total_bytes))) return rc;
-    HIVE_REQUIRE(ctx, out_bytes >= total_bytes, "jpeg_encode: out_bytes = %lld is too small: hive_jpeg_layout asks for %lld bytes", (long long)out_bytes,
-                 (long long)total_bytes);
+    if ((rc = hive_picture_room(ctx, "jpeg", out_bytes, total_bytes))) return rc;
     const int sub = subsampling == HIVE_JPEG_420;
     std::vector<JpegPic> pics((size_t)n);
     long long mcus = 0, intervals = 0;
@@ -623,7 +593,6 @@ int hive_jpeg_encode(hive_ctx *ctx, const hive_jpeg_image *images, int n, int qu
         L.off = 0;
         JpegPic *d_pics = L.take<JpegPic>((size_t)n);
         JpegTables *d_tab = L.take<JpegTables>(1);
-        const size_t table_bytes = L.bytes();  // one upload
         short *d_coef = L.take<short>((size_t)blocks * 64);
         unsigned *d_block_bits = L.take<unsigned>((size_t)blocks), *d_block_off = L.take<unsigned>((size_t)blocks);
         unsigned *d_interval_bits = L.take<unsigned>((size_t)intervals), *d_interval_bytes = L.take<unsigned>((size_t)intervals);
@@ -635,19 +604,13 @@ int hive_jpeg_encode(hive_ctx *ctx, const hive_jpeg_image *images, int n, int qu
             L.base = (char *)ctx->d_scratch;
             continue;
         }
-        std::vector<uint8_t> table(table_bytes, 0);
-        memcpy(table.data(), pics.data(), pics.size() * sizeof(JpegPic));
-        memcpy(table.data() + ((char *)d_tab - L.base), &tables, sizeof(tables));
-        if ((rc = hive_upload(ctx, L.base, table.data(), table.size()))) return rc;
+        if ((rc = hive_upload_tables(ctx, d_pics, pics, d_tab, tables))) return rc;
         rc = sub ? jpeg_launch<1>(ctx, d_pics, n, mcus, blocks, intervals, d_tab, d_coef, d_block_bits, d_block_off, d_interval_bits, d_interval_bytes, d_interval_off,
                                   d_stream, d_out, d_sizes)
                  : jpeg_launch<0>(ctx, d_pics, n, mcus, blocks, intervals, d_tab, d_coef, d_block_bits, d_block_off, d_interval_bits, d_interval_bytes, d_interval_off,
                                   d_stream, d_out, d_sizes);
         if (rc) return rc;
-        std::vector<long long> back((size_t)n);
-        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(back.data(), d_sizes, back.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < n; ++i) sizes[i] = back[(size_t)i];
+        return hive_read_sizes(ctx, d_sizes, n, sizes);
     }
     return HIVE_OK;
 }

@@ -30,26 +30,6 @@ constexpr int RS_NORM_WORDS = 8;      // cx_i, cy_i, s_i, cx_j, cy_j, s_j, ok (1
 constexpr int RS_SUMS = 44;           // the upper triangle of the 8 x 8 normal equations and their right-hand side
 constexpr double RS_EPS = 0x1p-40;    // a pivot with |a| <= 2^-40 rejects: normalised coordinates are of order 1
 
-// exclusive offset of this thread's count in a 256-thread workgroup, and the workgroup's total
-__device__ __forceinline__ unsigned pr_block_exclusive(unsigned c, unsigned *lds, unsigned *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = c;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = (unsigned)__shfl_up((int)inc, off);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, all = 0;
-    for (int w = 0; w < PR_THREADS / 64; ++w) {
-        if (w < wave) before += lds[w];
-        all += lds[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - c;
-}
-
 // the keypoint counts of pair p's two pictures; 0 and 0 for a pair that names a picture outside 0 .. N - 1
 __device__ __forceinline__ void pr_pair(const int32_t *__restrict__ pairs, const unsigned *__restrict__ counts, int N, int stride, int p, int &pi, int &pj, int &Q, int &T) {
     pi = pairs[2 * p], pj = pairs[2 * p + 1];
@@ -113,8 +93,8 @@ __global__ __launch_bounds__(PR_THREADS) void pair_filter_kernel(const float *__
             }
         }
         unsigned all_ratio, all_keep;
-        (void)pr_block_exclusive(by_ratio ? 1u : 0u, scan, &all_ratio);
-        const unsigned at = kept + pr_block_exclusive(keep ? 1u : 0u, scan, &all_keep);
+        (void)block_exclusive_total(by_ratio ? 1u : 0u, scan, &all_ratio);
+        const unsigned at = kept + block_exclusive_total(keep ? 1u : 0u, scan, &all_keep);
         if (keep) {
             float *o = out + (size_t)at * PR_ROW_WORDS;
             o[0] = xi, o[1] = yi, o[2] = xj, o[3] = yj, o[4] = zi, o[5] = zj;
@@ -427,7 +407,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_offsets_kernel(const int32_t 
         unsigned n = 0;
         if (p < P && pair_counts[2 * p + 1] >= min_features && result[3 * p + 2] >= min_features) n = (unsigned)result[3 * p + 2];
         unsigned all;
-        const unsigned at = pr_block_exclusive(n, scan, &all);
+        const unsigned at = block_exclusive_total(n, scan, &all);
         if (p < P) kept[p] = (int)n, offsets[p] = before + at;
         before += all;
     }
@@ -449,7 +429,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_compact_kernel(const float *_
         const int k = k0 + threadIdx.x;
         const bool in = k < M && mask[(size_t)p * stride + k] != 0;
         unsigned all;
-        const unsigned at = before + pr_block_exclusive(in ? 1u : 0u, scan, &all);
+        const unsigned at = before + block_exclusive_total(in ? 1u : 0u, scan, &all);
         if (in && at < (unsigned)kept[p]) dst[2 * (size_t)at] = src[2 * (size_t)k], dst[2 * (size_t)at + 1] = src[2 * (size_t)k + 1];
         before += all;
     }

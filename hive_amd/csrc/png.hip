@@ -20,7 +20,9 @@
 //   picture        one workgroup per picture: exclusive scan of the segment sizes, the Adler-32 and the IDAT CRC combined from the segments' parts by
 //                  their distance to the end, and every byte of the file outside the segments.
 //   place          one workgroup per segment: its bytes behind the segments before it.
-// The kernels move bytes and small integers; none is compute-bound.
+// The kernels move bytes and small integers; none is compute-bound.  The scans and the search are hive_internal.hpp's: block_scan_chunks (sort scan,
+// picture), block_exclusive_total (the segment's token loop: a chunk's bits are carried in a register) and last_not_after (the picture of a row or a
+// segment); the host frame -- the one upload, the sizes' read-back, the checks of the sides and of out_bytes -- is shared with jpeg.hip through the same header.
 #include "hive_internal.hpp"
 
 #include <algorithm>
@@ -67,19 +69,12 @@ __constant__ unsigned short PG_DIST_BASE[30] = {1,   2,   3,   4,   5,   7,    9
 __constant__ unsigned char PG_DIST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
 __constant__ unsigned char PG_CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-enum { PG_BY_ROW, PG_BY_SEG };
-// the last picture whose first row / segment is not after `at`
-template <int BY>
-__device__ __forceinline__ int pg_find(const PngPic *__restrict__ pics, int n, int at) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((BY == PG_BY_ROW ? pics[mid].first_row : pics[mid].first_seg) <= at)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
+// the picture that holds row / segment `at` of the call
+__device__ __forceinline__ int pg_picture_of_row(const PngPic *__restrict__ pics, int n, int at) {
+    return last_not_after(n, at, [pics](int i) { return pics[i].first_row; });
+}
+__device__ __forceinline__ int pg_picture_of_segment(const PngPic *__restrict__ pics, int n, int at) {
+    return last_not_after(n, at, [pics](int i) { return pics[i].first_seg; });
 }
 
 // byte x of row y as PNG orders the samples (16-bit samples most significant byte first; the pictures hold them in host order, the least significant first)
@@ -99,7 +94,7 @@ __device__ __forceinline__ int pg_filtered(int type, int x, int a, int b, int c)
 __global__ __launch_bounds__(PG_THREADS) void png_filter_kernel(const PngPic *__restrict__ pics, int n_pics, int total_rows, uint8_t *__restrict__ stream) {
     const int row = blockIdx.x * (PG_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= total_rows) return;  // the whole wave
-    const PngPic P = pics[pg_find<PG_BY_ROW>(pics, n_pics, row)];
+    const PngPic P = pics[pg_picture_of_row(pics, n_pics, row)];
     const int y = row - P.first_row, bpp = P.kind == HIVE_PNG_GRAY8 ? 1 : P.kind == HIVE_PNG_GRAY16 ? 2 : 3;
     unsigned sum[5] = {0, 0, 0, 0, 0};
     for (int x = lane; x < P.rowbytes; x += 64) {
@@ -153,20 +148,9 @@ __global__ __launch_bounds__(PG_THREADS) void png_sort_count_kernel(const uint8_
 // grid (256 digits): the digit's tile counts -> exclusive offsets in place, and its total
 __global__ __launch_bounds__(PG_THREADS) void png_sort_scan_kernel(unsigned *__restrict__ hist, unsigned tiles, unsigned *__restrict__ totals) {
     __shared__ unsigned lds[PG_THREADS / 64];
-    __shared__ unsigned chunk_total;
     unsigned *row = hist + (size_t)blockIdx.x * tiles;
-    unsigned carry = 0;
-    for (unsigned base = 0; base < tiles; base += PG_THREADS) {
-        const unsigned i = base + threadIdx.x;
-        const unsigned c = i < tiles ? row[i] : 0u;
-        const unsigned at = block_exclusive(c, lds);
-        if (i < tiles) row[i] = carry + at;
-        if (threadIdx.x == PG_THREADS - 1) chunk_total = at + c;
-        __syncthreads();
-        carry += chunk_total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+    const unsigned total = block_scan_chunks(tiles, lds, [&](unsigned i) { return row[i]; }, [&](unsigned i, unsigned at) { row[i] = at; });
+    if (threadIdx.x == 0) totals[blockIdx.x] = total;
 }
 
 // grid (tiles): every position of the tile to its place in `out`.  Thread d walks the tile's digits in order and numbers those equal to d.
@@ -367,11 +351,11 @@ __global__ __launch_bounds__(PG_THREADS) void png_segment_kernel(const PngPic *_
     __shared__ unsigned char lit_len[PG_LIT], dist_len[PG_DIST], cl_len[PG_CL];
     __shared__ PgBuilder builder;
     __shared__ unsigned scan_lds[PG_THREADS / 64];
-    __shared__ unsigned chunk_total, block_bits, crc_acc;
+    __shared__ unsigned header_bits, block_bits, crc_acc;  // header_bits: of a dynamic block in front of its first token, from lane 0 to all
     __shared__ unsigned long long adler_a, adler_b;
     __shared__ int hlit, hdist, hclen;
     const int tid = threadIdx.x;
-    const PngPic P = pics[pg_find<PG_BY_SEG>(pics, n_pics, blockIdx.x)];
+    const PngPic P = pics[pg_picture_of_segment(pics, n_pics, blockIdx.x)];
     const int seg = blockIdx.x - P.first_seg, s0 = seg * PG_SEGMENT, L = min(PG_SEGMENT, P.stream_len - s0), final = seg == P.nseg - 1;
     const int bpp = P.kind == HIVE_PNG_GRAY8 ? 1 : P.kind == HIVE_PNG_GRAY16 ? 2 : 3;
     const uint8_t *st = stream + P.stream_off;  // the picture's stream
@@ -468,11 +452,10 @@ __global__ __launch_bounds__(PG_THREADS) void png_segment_kernel(const PngPic *_
                 const unsigned e = cl_code[k < hlit ? lit_len[k] : dist_len[k - hlit]];
                 pg_put(image, pos, e & 0xFFFFu, e >> 16), pos += e >> 16;
             }
-            chunk_total = pos;
+            header_bits = pos;
         }
         __syncthreads();
-        unsigned carry = chunk_total;  // bits in front of this chunk of positions
-        __syncthreads();
+        unsigned carry = header_bits;  // bits in front of this chunk of positions (header_bits is not written again)
         for (int base = 0; base < L; base += PG_THREADS) {
             const int i = base + tid;
             unsigned first = 0, first_bits = 0, second = 0, second_bits = 0;
@@ -491,13 +474,11 @@ __global__ __launch_bounds__(PG_THREADS) void png_segment_kernel(const PngPic *_
                     first_bits = le >> 16;
                 }
             }
-            const unsigned at = block_exclusive(first_bits + second_bits, scan_lds);
+            unsigned chunk_bits;
+            const unsigned at = block_exclusive_total(first_bits + second_bits, scan_lds, &chunk_bits);
             pg_put(image, carry + at, first, first_bits);
             pg_put(image, carry + at + first_bits, second, second_bits);
-            if (tid == PG_THREADS - 1) chunk_total = at + first_bits + second_bits;
-            __syncthreads();
-            carry += chunk_total;
-            __syncthreads();
+            carry += chunk_bits;
         }
         if (tid == 0) {
             pg_put(image, carry, lit_code[256] & 0xFFFFu, lit_code[256] >> 16);
@@ -552,25 +533,15 @@ __global__ __launch_bounds__(PG_THREADS) void png_picture_kernel(const PngPic *_
                                                                  const unsigned *__restrict__ seg_crc, const unsigned *__restrict__ seg_adler,
                                                                  unsigned *__restrict__ seg_off, uint8_t *__restrict__ out, long long *__restrict__ sizes) {
     __shared__ unsigned lds[PG_THREADS / 64];
-    __shared__ unsigned chunk_total, crc_acc;
+    __shared__ unsigned crc_acc;
     __shared__ unsigned long long s1, s2;
     const PngPic P = pics[blockIdx.x];
     if (threadIdx.x == 0) {
         crc_acc = 0;
         s1 = s2 = 0;
     }
-    unsigned carry = 0;
-    for (int base = 0; base < P.nseg; base += PG_THREADS) {
-        const int i = base + threadIdx.x;
-        const unsigned c = i < P.nseg ? seg_bytes[P.first_seg + i] : 0u;
-        const unsigned at = block_exclusive(c, lds);
-        if (i < P.nseg) seg_off[P.first_seg + i] = carry + at;
-        if (threadIdx.x == PG_THREADS - 1) chunk_total = at + c;
-        __syncthreads();
-        carry += chunk_total;
-        __syncthreads();
-    }
-    const unsigned deflate_bytes = carry;
+    const unsigned deflate_bytes = block_scan_chunks((unsigned)P.nseg, lds, [&](unsigned i) { return seg_bytes[P.first_seg + i]; },
+                                                     [&](unsigned i, unsigned at) { seg_off[P.first_seg + i] = at; });
     // Adler-32 of the stream: s1 = 1 + every byte; s2 = every running s1 = the length + every segment's own sum + its byte sum times the bytes behind it.
     // CRC of "IDAT" + data: every segment's remainder moved by the bytes behind it (the Adler-32's four among them)
     unsigned long long a_sum = 0, b_sum = 0;
@@ -624,7 +595,7 @@ __global__ __launch_bounds__(PG_THREADS) void png_picture_kernel(const PngPic *_
 // grid (segments): the slot's bytes to their place in the file
 __global__ __launch_bounds__(PG_THREADS) void png_place_kernel(const PngPic *__restrict__ pics, int n_pics, const uint8_t *__restrict__ slots,
                                                                const unsigned *__restrict__ seg_bytes, const unsigned *__restrict__ seg_off, uint8_t *__restrict__ out) {
-    const PngPic P = pics[pg_find<PG_BY_SEG>(pics, n_pics, blockIdx.x)];
+    const PngPic P = pics[pg_picture_of_segment(pics, n_pics, blockIdx.x)];
     const uint8_t *slot = slots + (size_t)blockIdx.x * PG_SLOT;
     const unsigned nbytes = min(seg_bytes[blockIdx.x], (unsigned)PG_SLOT);
     uint8_t *dst = out + P.out_off + PG_DATA_AT + seg_off[blockIdx.x];
@@ -641,8 +612,7 @@ int png_layout(hive_ctx *ctx, const hive_png_image *images, int n, int64_t *offs
         const hive_png_image &im = images[i];
         HIVE_REQUIRE(ctx, im.kind == HIVE_PNG_GRAY8 || im.kind == HIVE_PNG_GRAY16 || im.kind == HIVE_PNG_RGB8, "png: picture %d: unknown kind %d (%d gray 8, %d gray 16, %d RGB 8)",
                      i, im.kind, HIVE_PNG_GRAY8, HIVE_PNG_GRAY16, HIVE_PNG_RGB8);
-        HIVE_REQUIRE(ctx, im.height >= 1 && im.height <= 65535 && im.width >= 1 && im.width <= 65535, "png: picture %d is %d x %d (sides of 1 .. 65535)", i, im.height,
-                     im.width);
+        if (int rc = hive_picture_sides(ctx, "png", i, im.height, im.width)) return rc;
         const int64_t stream = (int64_t)im.height * (1 + (int64_t)im.width * png_bpp(im.kind));
         HIVE_REQUIRE(ctx, stream <= PG_MAX_STREAM, "png: picture %d has %lld bytes of rows (at most %lld per call)", i, (long long)stream, PG_MAX_STREAM);
         if (offsets) offsets[i] = at;
@@ -669,8 +639,7 @@ int hive_png_encode(hive_ctx *ctx, const hive_png_image *images, int n, uint8_t 
     int64_t total_bytes = 0;
     int rc;
     if ((rc = png_layout(ctx, images, n, offsets.data(), &total_bytes))) return rc;
-    HIVE_REQUIRE(ctx, out_bytes >= total_bytes, "png_encode: out_bytes = %lld is too small: hive_png_layout asks for %lld bytes", (long long)out_bytes,
-                 (long long)total_bytes);
+    if ((rc = hive_picture_room(ctx, "png", out_bytes, total_bytes))) return rc;
     std::vector<PngPic> pics((size_t)n);
     long long positions = 0, segments = 0, rows = 0;
     for (int i = 0; i < n; ++i) {
@@ -706,7 +675,6 @@ int hive_png_encode(hive_ctx *ctx, const hive_png_image *images, int n, uint8_t 
         L.off = 0;
         PngPic *d_pics = L.take<PngPic>((size_t)n);
         PngTables *d_tab = L.take<PngTables>(1);
-        const size_t table_bytes = L.bytes();  // one upload
         uint8_t *d_stream = L.take<uint8_t>((size_t)N + 4);
         unsigned *d_order_a = L.take<unsigned>((size_t)N), *d_order_b = L.take<unsigned>((size_t)N);
         unsigned *d_hist = L.take<unsigned>((size_t)tiles * 256), *d_totals = L.take<unsigned>(256);
@@ -719,10 +687,7 @@ int hive_png_encode(hive_ctx *ctx, const hive_png_image *images, int n, uint8_t 
             L.base = (char *)ctx->d_scratch;
             continue;
         }
-        std::vector<uint8_t> table(table_bytes, 0);
-        memcpy(table.data(), pics.data(), pics.size() * sizeof(PngPic));
-        memcpy(table.data() + ((char *)d_tab - L.base), &tables, sizeof(tables));
-        if ((rc = hive_upload(ctx, L.base, table.data(), table.size()))) return rc;
+        if ((rc = hive_upload_tables(ctx, d_pics, pics, d_tab, tables))) return rc;
         const dim3 threads(PG_THREADS);
         hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((rows + 3) / 4)), threads, 0, ctx->stream, d_pics, n, (int)rows, d_stream);
         // three stable passes, the last by the first byte: identity -> a -> b -> a
@@ -745,10 +710,7 @@ int hive_png_encode(hive_ctx *ctx, const hive_png_image *images, int n, uint8_t 
         hipLaunchKernelGGL(png_place_kernel, dim3((unsigned)segments), threads, 0, ctx->stream, d_pics, n, (const uint8_t *)d_slots, (const unsigned *)d_seg_bytes,
                            (const unsigned *)d_seg_off, d_out);
         HIVE_CHECK_HIP(ctx, hipGetLastError());
-        std::vector<long long> back((size_t)n);
-        HIVE_CHECK_HIP(ctx, hipMemcpyAsync(back.data(), d_sizes, back.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIVE_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < n; ++i) sizes[i] = back[(size_t)i];
+        return hive_read_sizes(ctx, d_sizes, n, sizes);
     }
     return HIVE_OK;
 }

@@ -16,6 +16,7 @@ from collections import OrderedDict
 import numpy as np
 
 from hive_amd import _lib
+from hive_amd._pictures import is_torch as _is_torch
 from hive_amd.mesh import Mesh
 
 GLB_MAGIC, GLB_VERSION, CHUNK_JSON, CHUNK_BIN = 0x46546C67, 2, 0x4E4F534A, 0x004E4942
@@ -30,10 +31,6 @@ _WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4}
 
 class GltfError(ValueError):
     """A .glb that ``read_glb`` refuses."""
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 def mesh_fields(mesh):

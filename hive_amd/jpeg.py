@@ -4,13 +4,9 @@ restart_marker_rows=1``; tests/jpeg_restatement.py restates them in numpy.  The 
 """
 import numpy as np
 
-from hive_amd import _lib
+from hive_amd import _lib, _pictures
 
 SUBSAMPLINGS = tuple(_lib.JPEG_SUBSAMPLING)
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 def check_settings(quality, subsampling):
@@ -55,13 +51,8 @@ def encode_to_device(images, quality=90, subsampling="4:2:0", ctx=None):
     ctx = ctx or _lib.default_context()
     ctx.follow_torch_stream()
     dev = torch.device("cuda", ctx.device)
-    keep, table = [], (_lib.JpegImage * len(images))()
-    for row, image in zip(table, images):
-        t = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image))
-        t = t.to(dev)
-        if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]:
-            t = t.contiguous()
-        keep.append(t)
+    keep, table = [_pictures.device_rows(image, dev, (3, 1)) for image in images], (_lib.JpegImage * len(images))()
+    for row, t in zip(table, keep):
         row.data, row.height, row.width, row.pitch = t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)
     n, code = len(images), _lib.JPEG_SUBSAMPLING[subsampling]
     offsets, total, sizes = np.zeros(n, np.int64), _lib.c_int64(0), np.zeros(n, np.int64)
@@ -73,12 +64,6 @@ def encode_to_device(images, quality=90, subsampling="4:2:0", ctx=None):
 
 def encode(images, quality=90, subsampling="4:2:0", ctx=None):
     """The JPEG file of one (H, W, 3) uint8 picture as ``bytes``, or of a list of pictures as a list of ``bytes``: one encoder call and one download for all."""
-    import torch
     single = not isinstance(images, (list, tuple))
-    packed, offsets, sizes = encode_to_device([images] if single else images, quality, subsampling, ctx)
-    # the files fill a small part of their worst-case bounds: join them on the device and download only those bytes
-    pieces = [packed[int(o):int(o + s)] for o, s in zip(offsets, sizes)]
-    host = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).cpu().numpy().tobytes()
-    ends = np.cumsum(sizes)
-    files = [host[int(e - s):int(e)] for e, s in zip(ends, sizes)]
+    files = _pictures.files_of(*encode_to_device([images] if single else images, quality, subsampling, ctx))
     return files[0] if single else files

@@ -5,7 +5,7 @@ of every caller: ``png_encoder="gpu"`` selects this one.
 """
 import numpy as np
 
-from hive_amd import _lib
+from hive_amd import _lib, _pictures
 
 ENCODERS = ("host", "gpu")
 KINDS = tuple(_lib.PNG_KIND)
@@ -21,10 +21,6 @@ def write_file(path, data):
     """What a writer thread does with an encoded file."""
     with open(path, "wb") as f:
         f.write(data)
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 def kind_of(k, image):
@@ -67,14 +63,9 @@ def encode_to_device(images, ctx=None):
     ctx = ctx or _lib.default_context()
     ctx.follow_torch_stream()
     dev = torch.device("cuda", ctx.device)
-    keep, table = [], (_lib.PngImage * len(images))()
-    for row, image, kind in zip(table, images, kinds):
-        t = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image))
-        t = t.to(dev)
-        inner = t.stride()[1:] == ((3, 1) if kind == "rgb8" else (1,))
-        if not inner or t.stride(0) < t.shape[1] * (3 if kind == "rgb8" else 1):
-            t = t.contiguous()
-        keep.append(t)
+    keep = [_pictures.device_rows(image, dev, (3, 1) if kind == "rgb8" else (1,)) for image, kind in zip(images, kinds)]
+    table = (_lib.PngImage * len(images))()
+    for row, t, kind in zip(table, keep, kinds):
         row.pixels, row.height, row.width, row.kind = t.data_ptr(), t.shape[0], t.shape[1], _lib.PNG_KIND[kind]
         row.pitch = t.stride(0) * t.element_size()
     n = len(images)
@@ -87,12 +78,6 @@ def encode_to_device(images, ctx=None):
 
 def encode(images, ctx=None):
     """The PNG file of one picture as ``bytes``, or of a list of pictures as a list of ``bytes``: one encoder call and one download for all."""
-    import torch
     single = not isinstance(images, (list, tuple))
-    packed, offsets, sizes = encode_to_device([images] if single else images, ctx)
-    # the files fill a part of their all-stored bounds: join them on the device and download only those bytes
-    pieces = [packed[int(o):int(o + s)] for o, s in zip(offsets, sizes)]
-    host = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).cpu().numpy().tobytes()
-    ends = np.cumsum(sizes)
-    files = [host[int(e - s):int(e)] for e, s in zip(ends, sizes)]
+    files = _pictures.files_of(*encode_to_device([images] if single else images, ctx))
     return files[0] if single else files

@@ -14,6 +14,8 @@ SUBSAMPLINGS = ("4:4:4", "4:2:0")
 PILLOW_SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2}
 CONTENTS = ("gradient_noise", "noise", "flat", "blocks", "impulses")
 LARGE = (480, 640)
+# 257 MCU rows in one picture, outside SIZES: the picture-level scan of the intervals takes a second chunk of 256.  (height, width, content, quality, subsampling)
+LONG = ((2056, 8, "gradient_noise", 90, "4:4:4"), (4112, 8, "gradient_noise", 90, "4:2:0"))
 
 
 @functools.lru_cache(maxsize=None)

@@ -27,6 +27,19 @@ CONTENTS = ("1x1", "1x7", "7x1", "S-1", "S", "S+1", "straddle", "flat", "halves_
             "mask")
 ONLY = {"all_bytes": ("gray8",), "depth_480x640": ("gray16",)}
 SIZE_RECORD = (("ramp_noise", "gray16"), ("ramp", "rgb8"), ("mask", "gray8"), ("depth_480x640", "gray16"))
+# gray8, 1025 x 2047, pixel (x // 5 + 3 y) % 256: a stream of 1025 * 2048 = 2 099 200 bytes, 257 segments and 1025 sort tiles, so the picture-level scans take a
+# second chunk of 256.  The restatement needs seconds for it: its file is recorded here (tests/test_png_cpu.py checks the record against the restatement, the
+# GPU test checks the GPU's file against the record and reads it back)
+LONG_SHAPE = (1025, 2047)
+LONG_RECORD = {"length": 25126, "sha256": "73d73adee4592c651b28ba84099316e66cadebead15ff3b56b945e4a61950c82"}
+
+
+@functools.lru_cache(maxsize=None)
+def long_picture():
+    yy, xx = np.mgrid[0:LONG_SHAPE[0], 0:LONG_SHAPE[1]]
+    a = ((xx // 5 + 3 * yy) % 256).astype(np.uint8)
+    a.setflags(write=False)
+    return a
 
 
 def _as_kind(values, kind):

@@ -44,6 +44,14 @@ def test_restatement_equals_pillows_file(quality, subsampling):
         assert mine[:2] == b"\xFF\xD8" and mine[-2:] == b"\xFF\xD9" and len(mine) > R.HEADER_BYTES == 629
 
 
+@needs_pillow_jpeg
+@pytest.mark.parametrize("case", C.LONG)
+def test_restatement_equals_pillows_file_past_256_intervals(case):
+    mine, counters = C.restated(*case)
+    assert counters["intervals"] == 257
+    assert mine == _pillow_file(C.picture(*case[:3]), *case[3:])
+
+
 def test_case_list_reaches_every_corner_of_the_rule():
     total = {}
     for subsampling in C.SUBSAMPLINGS:

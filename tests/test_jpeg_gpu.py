@@ -44,6 +44,19 @@ def test_bytes_equal_the_restatement(gpu_ctx, quality, subsampling):
         _opens_without_warning(got, height, width)
 
 
+@pytest.mark.parametrize("case", C.LONG)
+def test_bytes_equal_the_restatement_past_256_intervals(gpu_ctx, case):
+    """257 MCU rows: the picture scan's second chunk of 256 intervals, alone and as the middle picture of three (its first interval is not the call's first)."""
+    from hive_amd import jpeg
+    quality, subsampling = case[3:]
+    want = C.restated(*case)[0]
+    long = _device(C.picture(*case[:3]))
+    assert jpeg.encode(long, quality, subsampling, ctx=gpu_ctx) == want
+    around = [(9, 17, "noise"), (24, 40, "gradient_noise")]
+    batch = jpeg.encode([_device(C.picture(*around[0])), long, _device(C.picture(*around[1]))], quality, subsampling, ctx=gpu_ctx)
+    assert batch == [C.restated(*around[0], quality, subsampling)[0], want, C.restated(*around[1], quality, subsampling)[0]]
+
+
 @pytest.mark.parametrize("subsampling", C.SUBSAMPLINGS)
 def test_a_batch_equals_each_alone_in_either_order_and_runs_repeat(gpu_ctx, subsampling):
     from hive_amd import jpeg

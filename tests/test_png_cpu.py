@@ -201,6 +201,19 @@ def test_the_size_record(content, kind):
     assert ours <= LEVEL1_PINS[(content, kind)] * level1, (ours, level1, level6)
 
 
+def test_the_long_record_is_the_restatements_file():
+    """The slow one (seconds): 257 segments and 1025 sort tiles.  The file recorded for the GPU test is the restatement's, and Pillow reads the input back."""
+    import hashlib
+    picture = C.long_picture()
+    stream = picture.shape[0] * (1 + picture.shape[1])
+    assert -(-stream // C.S) == 257 and -(-stream // 2048) == 1025
+    data = R.encode(picture)
+    assert {"length": len(data), "sha256": hashlib.sha256(data).hexdigest()} == C.LONG_RECORD
+    from PIL import Image
+    image = Image.open(io.BytesIO(data))
+    assert image.mode == "L" and np.array_equal(np.array(image), picture)
+
+
 def test_png_encoder_names_are_checked_without_a_gpu():
     from hive_amd import png
     from hive_amd.options import PipelineOptions

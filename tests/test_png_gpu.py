@@ -35,6 +35,22 @@ def test_bytes_equal_the_restatement(gpu_ctx):
         assert isinstance(got, bytes) and len(got) == len(want) and got == want, (content, kind, len(got), len(want))
 
 
+def test_the_long_picture_is_the_recorded_file(gpu_ctx):
+    """257 segments and 1025 sort tiles in one picture: the second chunk of the picture's scan and of the sort's.  The restatement's file is recorded
+    (tests/png_cases.py, checked on the CPU); a wrong segment offset, CRC or Adler sum also fails the decode.  Alone, and behind a 1 x 7 (first_seg = 1)."""
+    import hashlib
+    from hive_amd import png
+    picture = C.long_picture()
+    long = _device(picture)
+    alone = png.encode(long, ctx=gpu_ctx)
+    small, second = png.encode([_device(C.picture("1x7", "gray8")), long], ctx=gpu_ctx)
+    assert small == C.restated("1x7", "gray8")[0]
+    for data in (alone, second):
+        assert {"length": len(data), "sha256": hashlib.sha256(data).hexdigest()} == C.LONG_RECORD
+        mode, pixels = _decoded(data)
+        assert mode == "L" and np.array_equal(pixels, picture)
+
+
 def test_a_mixed_batch_equals_each_alone_in_either_order_and_runs_repeat(gpu_ctx):
     from hive_amd import png
     cases = C.cases(with_large=False)
