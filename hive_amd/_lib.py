@@ -412,6 +412,11 @@ _default_ctx = {}
 _tls = threading.local()
 
 
+def context_for(ctx, device):
+    """``ctx``, or the calling thread's default context of the torch ``device``; either way bound to torch's current stream there."""
+    return (ctx or default_context(device.index or 0)).follow_torch_stream()
+
+
 def default_context(device=None):
     """Per-thread, per-device default context (the reference calls the geometric functions from a
     ThreadPool, hive/pipeline.py:491; a hive_ctx is not re-entrant)."""

@@ -41,17 +41,6 @@ struct CentroidParams {
     int H, W, tiles;
 };
 
-// butterfly over the 64 lanes, then the four waves in order; the result is valid in thread 0
-__device__ __forceinline__ void ct_block_sum(double s[4], double (*lds)[4]) {
-    for (int off = 32; off > 0; off >>= 1)
-        for (int k = 0; k < 4; ++k) s[k] += __shfl_xor(s[k], off);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 4; ++k) lds[threadIdx.x >> 6][k] = s[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 4; ++k) s[k] = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-}
-
 // grid (tiles, frames): partial[frame][tile] = {sum x, sum y, sum z, count} (counts are exact in a double: < 2^30 pixels)
 __global__ __launch_bounds__(CT_THREADS) void centroid_tile_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, CentroidParams p,
                                                                    double *__restrict__ partial) {
@@ -69,7 +58,7 @@ __global__ __launch_bounds__(CT_THREADS) void centroid_tile_kernel(const float *
             s[3] += 1.0;
         }
     }
-    ct_block_sum(s, lds);
+    block_butterfly_sum<4>(s, lds);
     if (threadIdx.x == 0)
         for (int k = 0; k < 4; ++k) partial[((size_t)blockIdx.y * p.tiles + blockIdx.x) * 4 + k] = s[k];
 }
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(CT_THREADS) void centroid_frame_kernel(const double
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int t = threadIdx.x; t < tiles; t += CT_THREADS)
         for (int k = 0; k < 4; ++k) s[k] += partial[((size_t)blockIdx.x * tiles + t) * 4 + k];
-    ct_block_sum(s, lds);
+    block_butterfly_sum<4>(s, lds);
     if (threadIdx.x == 0) {
         const double c = s[3];
         for (int k = 0; k < 3; ++k) out[(size_t)blockIdx.x * 4 + k] = c > 0.0 ? s[k] / c : 0.0;
@@ -110,11 +99,6 @@ struct FtsArgs {
 };
 
 using namespace hive_pose;  // Vec3, Pose, load_pose, rotate_inverse, rotate_forward
-
-__device__ __forceinline__ double wave_sum(double s) {
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
 
 // per-frame terms of the loss at the current parameters
 __device__ __forceinline__ void fts_terms(const FtsArgs &a) {
@@ -154,9 +138,9 @@ __device__ __forceinline__ void fts_chunk_sums(const FtsArgs &a, int slot) {
             s1 += t[1];
             s2 += t[2];
         }
-        sr = wave_sum(sr);
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
+        sr = wave_butterfly_sum(sr);
+        s1 = wave_butterfly_sum(s1);
+        s2 = wave_butterfly_sum(s2);
         if (lane == 0) {
             const double n1 = sqrt(s1), n2 = sqrt(s2);
             a.chunk_sums[(size_t)c * 4 + 0] = n1;
@@ -168,7 +152,7 @@ __device__ __forceinline__ void fts_chunk_sums(const FtsArgs &a, int slot) {
     if (wave == 0) {
         double s = 0.0;
         for (int c = lane; c < a.C; c += 64) s += a.chunk_sums[(size_t)c * 4 + 2];
-        s = wave_sum(s);
+        s = wave_butterfly_sum(s);
         if (lane == 0) a.losses[slot] = s;
     }
 }

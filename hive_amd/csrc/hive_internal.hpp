@@ -207,6 +207,44 @@ __device__ __forceinline__ unsigned block_exclusive_total(unsigned c, unsigned *
     *total = all;
     return before + inc - c;
 }
+// ---- the two float64 workgroup sums whose order include/hive_mi355x.h states; float64 without contraction, so the bits depend on the values alone ----
+// The fixed tree: v[q][0] = the sum of v[q][0 .. THREADS) for each of the COLS columns by v[q][t] += v[q][t + off], off = THREADS / 2 .. 1, one barrier per
+// level for all columns.  Every thread of the THREADS-thread workgroup calls it after writing its own v[q][threadIdx.x]; the sums are there for every thread
+// on return (similarity.hip, lpips.hip, track.hip)
+template <int THREADS, int COLS>
+__device__ __forceinline__ void block_tree_sum(double (*v)[THREADS]) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if (t < off) {
+#pragma unroll
+            for (int q = 0; q < COLS; ++q) v[q][t] = v[q][t] + v[q][t + off];
+        }
+        __syncthreads();
+    }
+}
+// the butterfly over the 64 lanes of a wave, s = s + s[lane ^ off], off = 32 .. 1: every lane gets the same total (fts.hip: a chunk's sums, one wave each)
+__device__ __forceinline__ double wave_butterfly_sum(double s) {
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+// s[0 .. COUNT) over a 256-thread workgroup: the butterfly in every wave, then the four waves left to right; valid in thread 0 alone.  `lds` holds a row per
+// wave.  No barrier behind the sum: no caller (fts.hip's centroid kernels, poseopt.hip's loss and step kernels) touches `lds` again or reads another
+// thread's result; one that did would put its own barrier in between.  The butterfly is wave_butterfly_sum per value with the offsets outermost: value by
+// value the same additions, but po_step_kernel<false, true> needs 166 VGPRs in place of 120 when the values are outermost
+template <int COUNT, int WIDTH>
+__device__ __forceinline__ void block_butterfly_sum(double *s, double (*lds)[WIDTH]) {
+    static_assert(COUNT <= WIDTH, "a row of lds holds every value");
+    for (int off = 32; off > 0; off >>= 1)
+        for (int j = 0; j < COUNT; ++j) s[j] += __shfl_xor(s[j], off);
+    if ((threadIdx.x & 63) == 0)
+        for (int j = 0; j < COUNT; ++j) lds[threadIdx.x >> 6][j] = s[j];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int j = 0; j < COUNT; ++j) s[j] = ((lds[0][j] + lds[1][j]) + lds[2][j]) + lds[3][j];
+}
+// ceil(a / b) for launch grids
+inline int hive_div_up(long long a, int b) { return (int)((a + b - 1) / b); }
 // A 256-thread workgroup scans `count` values 256 at a time: store(i, the sum of load(0 .. i - 1)) for every i < count; returns the sum of all (in every
 // thread).  Every thread of the workgroup calls it with the same count
 template <class Load, class Store>

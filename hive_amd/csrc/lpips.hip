@@ -53,15 +53,6 @@ struct LpShape {
     int KW, stride, pad, K;
 };
 
-// v[0] = the sum of v[0 .. 256) by the fixed tree of the picture scores: v[t] += v[t + off], off = 128 .. 1
-__device__ __forceinline__ void lp_tree(double *v) {
-    __syncthreads();
-    for (int off = LP_THREADS / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) v[threadIdx.x] = v[threadIdx.x] + v[threadIdx.x + off];
-        __syncthreads();
-    }
-}
-
 // grid (ceil(M / 64), ceil(Cout / 64)).  MODE 0 / 1: `in` f32 [B][H][W][Cin].  MODE 2: ref / est u8 [nc][H][W][3]; picture b of the launch is set b / nc
 // (sets 0 .. variants - 1 the reference, plain then masked; set `variants` the estimate), picture b % nc.
 template <int MODE>
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(LP_THREADS) void lpips_tail_kernel(const float *__r
     if (p >= hw) d = 0.0;  // (a pixel past the end saw zeros: 0 / 1e-10 - 0 / 1e-10)
     if (p < hw && dist) dist[((size_t)v * dist_pictures + n) * hw + p] = d;
     red[t] = d;
-    lp_tree(red);
+    block_tree_sum<LP_THREADS, 1>(&red);  // the fixed tree of the picture scores
     if (t == 0) partials[(size_t)z * gridDim.x + blockIdx.x] = red[0];
 }
 

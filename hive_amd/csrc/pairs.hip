@@ -3,7 +3,7 @@
 // the second compaction by its inlier mask.  gfx950 only.  The rules are stated in include/hive_mi355x.h above hive_pairs_match and restated in numpy in
 // tests/ransac_restatement.py.  cv2's USAC_MAGSAC is randomised and absent: the RANSAC here is a stated rule of its own and is not pinned against cv2.
 //
-//   match     rule `knn` (knn_core.hpp, shared with sift.hip) between the two pictures a pair names
+//   match     rule `knn` (knn_match_kernel of knn_core.hpp, the kernel sift.hip launches too) between the two pictures a pair names
 //   filter    a query survives when both pictures have min_features keypoints, not (double) d0 > ratio * (double) d1, and the depth at both rounded positions
 //             is not 0; survivors keep the query order (a workgroup scan, no atomic decides an order)
 //   RANSAC    float64, one rounding per operation (the Makefile's EXACT flags): Hartley normalisation of both sides with lane-order sums; `trials` minimal
@@ -11,7 +11,7 @@
 //             errors within the threshold; the winner by one 64-bit integer atomic maximum of count << 32 | (0xFFFFFFFF - trial); one least-squares refit
 //   compact   the rows of every kept pair, in pair order, inliers in row order
 //
-// Kernels: pair_knn_kernel (one thread per query), pair_filter_kernel (one workgroup per pair), ransac_norm_kernel (one wave per pair), ransac_trial_kernel (one
+// Kernels: knn_match_kernel (knn_core.hpp: one thread per query), pair_filter_kernel (one workgroup per pair), ransac_norm_kernel (one wave per pair), ransac_trial_kernel (one
 // lane per trial; the pair's normalised points go through LDS in chunks, every lane reads the same address), ransac_finish_kernel (one wave per pair),
 // pair_offsets_kernel (one workgroup), pair_compact_kernel (one workgroup per pair).  No floating-point atomic: the same bits on every run and at every place.
 #include <cmath>
@@ -22,40 +22,11 @@
 namespace {
 
 constexpr int PR_THREADS = 256;
-constexpr int PR_KP_WORDS = 6;        // hive_sift_detect's keypoint row
-constexpr int PR_DESC = 128;
 constexpr int PR_ROW_WORDS = 8;       // x_i, y_i, x_j, y_j, depth_i, depth_j (f32); query index, train index (i32)
 constexpr int RS_CHUNK = 512;         // normalised points staged at a time: 16 KiB of LDS
 constexpr int RS_NORM_WORDS = 8;      // cx_i, cy_i, s_i, cx_j, cy_j, s_j, ok (1 / 0), unused
 constexpr int RS_SUMS = 44;           // the upper triangle of the 8 x 8 normal equations and their right-hand side
 constexpr double RS_EPS = 0x1p-40;    // a pivot with |a| <= 2^-40 rejects: normalised coordinates are of order 1
-
-// the keypoint counts of pair p's two pictures; 0 and 0 for a pair that names a picture outside 0 .. N - 1
-__device__ __forceinline__ void pr_pair(const int32_t *__restrict__ pairs, const unsigned *__restrict__ counts, int N, int stride, int p, int &pi, int &pj, int &Q, int &T) {
-    pi = pairs[2 * p], pj = pairs[2 * p + 1];
-    const bool ok = pi >= 0 && pi < N && pj >= 0 && pj < N;
-    if (!ok) pi = pj = 0;
-    Q = ok ? (int)min(counts[3 * pi + 2], (unsigned)stride) : 0;
-    T = ok ? (int)min(counts[3 * pj + 2], (unsigned)stride) : 0;
-}
-
-// grid (ceil(stride / 64), P): knn_kernel of sift.hip with the pictures taken from the pair list
-__global__ __launch_bounds__(KNN_TILE) void pair_knn_kernel(const uint8_t *__restrict__ desc, const unsigned *__restrict__ counts, const int32_t *__restrict__ pairs, int N,
-                                                            int stride, int32_t *__restrict__ idx, float *__restrict__ dist) {
-    __shared__ unsigned tile[KNN_TILE][KNN_WORDS + 1];
-    const int p = blockIdx.y, q = blockIdx.x * KNN_TILE + threadIdx.x;
-    int pi, pj, Q, T;
-    pr_pair(pairs, counts, N, stride, p, pi, pj, Q, T);
-    if ((int)blockIdx.x * KNN_TILE >= Q) return;
-    const unsigned *qd = (const unsigned *)(desc + (size_t)pi * stride * PR_DESC), *td = (const unsigned *)(desc + (size_t)pj * stride * PR_DESC);
-    unsigned b0, b1;
-    int i0, i1;
-    knn_two_nearest(qd, td, Q, T, q, tile, b0, b1, i0, i1);
-    if (q >= Q) return;
-    const size_t at = ((size_t)p * stride + q) * 2;
-    idx[at] = i0, idx[at + 1] = i1;
-    dist[at] = i0 < 0 ? INFINITY : sqrtf((float)b0), dist[at + 1] = i1 < 0 ? INFINITY : sqrtf((float)b1);
-}
 
 // depth at the rounded position, clamped into the picture
 __device__ __forceinline__ float pr_depth_at(const float *__restrict__ depth, int H, int W, float x, float y) {
@@ -71,9 +42,9 @@ __global__ __launch_bounds__(PR_THREADS) void pair_filter_kernel(const float *__
     __shared__ unsigned scan[PR_THREADS / 64];
     const int p = blockIdx.x, t = threadIdx.x;
     int pi, pj, Q, T;
-    pr_pair(pairs, counts, N, stride, p, pi, pj, Q, T);
+    knn_pair(pairs, counts, N, stride, p, pi, pj, Q, T);
     if (min(Q, T) < max(min_features, 2)) Q = 0;
-    const float *qk = kps + (size_t)pi * stride * PR_KP_WORDS, *tk = kps + (size_t)pj * stride * PR_KP_WORDS;
+    const float *qk = kps + (size_t)pi * stride * KNN_KP_WORDS, *tk = kps + (size_t)pj * stride * KNN_KP_WORDS;
     const float *di = depth + (size_t)pi * H * W, *dj = depth + (size_t)pj * H * W;
     float *out = rows + (size_t)p * stride * PR_ROW_WORDS;
     unsigned kept = 0, passed = 0;
@@ -87,7 +58,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_filter_kernel(const float *__
             tr = idx[at];
             by_ratio = tr >= 0 && idx[at + 1] >= 0 && !((double)dist[at] > ratio * (double)dist[at + 1]);
             if (by_ratio) {
-                xi = qk[(size_t)q * PR_KP_WORDS], yi = qk[(size_t)q * PR_KP_WORDS + 1], xj = tk[(size_t)tr * PR_KP_WORDS], yj = tk[(size_t)tr * PR_KP_WORDS + 1];
+                xi = qk[(size_t)q * KNN_KP_WORDS], yi = qk[(size_t)q * KNN_KP_WORDS + 1], xj = tk[(size_t)tr * KNN_KP_WORDS], yj = tk[(size_t)tr * KNN_KP_WORDS + 1];
                 zi = pr_depth_at(di, H, W, xi, yi), zj = pr_depth_at(dj, H, W, xj, yj);
                 keep = zi != 0.0f && zj != 0.0f;
             }
@@ -435,8 +406,6 @@ __global__ __launch_bounds__(PR_THREADS) void pair_compact_kernel(const float *_
     }
 }
 
-int pr_div_up(long long a, int b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
 
 extern "C" {
@@ -457,8 +426,8 @@ int hive_pairs_match(hive_ctx *ctx, const float *d_keypoints, const uint8_t *d_d
         if (int rc = hive_reserve_device(ctx, &ctx->d_scratch, &ctx->scratch_bytes, 2 * half)) return rc;
         d_indices = (int32_t *)ctx->d_scratch, d_distances = (float *)((char *)ctx->d_scratch + half);
     }
-    hipLaunchKernelGGL(pair_knn_kernel, dim3((unsigned)pr_div_up(capacity, KNN_TILE), (unsigned)P), dim3(KNN_TILE), 0, ctx->stream, d_descriptors,
-                       (const unsigned *)d_counts, d_pairs, N, capacity, d_indices, d_distances);
+    const KnnArgs a = {d_descriptors, d_descriptors, (const unsigned *)d_counts, d_pairs, N, 0, 0, capacity, 0, 0};
+    hipLaunchKernelGGL(knn_match_kernel, dim3((unsigned)hive_div_up(capacity, KNN_TILE), (unsigned)P), dim3(KNN_TILE), 0, ctx->stream, a, d_indices, d_distances);
     hipLaunchKernelGGL(pair_filter_kernel, dim3((unsigned)P), dim3(PR_THREADS), 0, ctx->stream, d_keypoints, (const unsigned *)d_counts, d_pairs, N, capacity, d_indices,
                        d_distances, d_depth, H, W, ratio, min_features, d_rows, d_pair_counts);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
@@ -481,7 +450,7 @@ int hive_ransac_homography(hive_ctx *ctx, const float *d_rows, int row_words, co
     unsigned long long *best = (unsigned long long *)((char *)ctx->d_scratch + norm_bytes);
     HIVE_CHECK_HIP(ctx, hipMemsetAsync(best, 0, best_bytes, ctx->stream));
     hipLaunchKernelGGL(ransac_norm_kernel, dim3((unsigned)P), dim3(64), 0, ctx->stream, d_rows, row_words, d_counts, count_stride, stride, need, norm);
-    hipLaunchKernelGGL(ransac_trial_kernel, dim3((unsigned)pr_div_up(trials, PR_THREADS), (unsigned)P), dim3(PR_THREADS), 0, ctx->stream, d_rows, row_words, d_counts,
+    hipLaunchKernelGGL(ransac_trial_kernel, dim3((unsigned)hive_div_up(trials, PR_THREADS), (unsigned)P), dim3(PR_THREADS), 0, ctx->stream, d_rows, row_words, d_counts,
                        count_stride, d_keys, stride, need, norm, threshold, trials, seed, best);
     hipLaunchKernelGGL(ransac_finish_kernel, dim3((unsigned)P), dim3(64), 0, ctx->stream, d_rows, row_words, d_counts, count_stride, d_keys, stride, need, norm, threshold, seed,
                        best, d_H, d_mask, d_result);

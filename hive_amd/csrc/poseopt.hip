@@ -58,23 +58,10 @@ struct PoArgs {
     double max_distance;   // < 0: no clip
 };
 
-// lane butterfly, then the waves in order; valid in thread 0
-template <int COUNT>
-__device__ __forceinline__ void po_block_sum(double *s, double (*lds)[PO_ACC]) {
-    for (int off = 32; off > 0; off >>= 1)
-        for (int j = 0; j < COUNT; ++j) s[j] += __shfl_xor(s[j], off);
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < COUNT; ++j) lds[threadIdx.x >> 6][j] = s[j];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int j = 0; j < COUNT; ++j) s[j] = ((lds[0][j] + lds[1][j]) + lds[2][j]) + lds[3][j];
-    __syncthreads();
-}
-
 __device__ __forceinline__ double po_loss_sum(const double *partial, int n, double (*lds)[PO_ACC]) {
     double s[1] = {0.0};
     for (int f = threadIdx.x; f < n; f += PO_THREADS) s[0] += partial[f];
-    po_block_sum<1>(s, lds);
+    block_butterfly_sum<1>(s, lds);
     return s[0];
 }
 
@@ -176,7 +163,7 @@ __global__ __launch_bounds__(PO_THREADS) void po_step_kernel(PoArgs a, int epoch
         const int entry = a.entries[e];
         po_entry<IMAGE2D, AFFINE>(a.k, par, a.raw, a.cam, a.index_i, a.index_j, entry >> 1, entry & 1, acc);
     }
-    po_block_sum<PO_ACC>(acc, lds);
+    block_butterfly_sum<PO_ACC>(acc, lds);
     if (threadIdx.x != 0) return;
     po_frame_tail<AFFINE>(a.k, par, f, acc);
     a.partial[f] = acc[9];

@@ -18,7 +18,7 @@
 //
 // Kernels: sift_base_kernel (one thread per doubled pixel), sift_blur_kernel (one workgroup per 32 x 32 tile, per picture), sift_half_kernel, sift_detect_kernel
 // (one thread per pixel, layer and picture), sift_orient_kernel and sift_describe_kernel (one wave per candidate / keypoint), sift_rank_kernel and
-// sift_unique_kernel (one thread per keypoint), knn_kernel (one thread per query), mifd_kernel (one thread per pair).
+// sift_unique_kernel (one thread per keypoint), knn_match_kernel (knn_core.hpp: one thread per query), mifd_kernel (one thread per pair).
 #include <cfloat>
 #include <cmath>
 
@@ -36,9 +36,9 @@ constexpr int SF_MAX_OCTAVES = 16;
 constexpr int SF_BORDER = 5;
 constexpr int SF_STEPS = 5;
 constexpr int SF_ORI_BINS = 36;
-constexpr int SF_D = 4, SF_N = 8, SF_DESC = SF_D * SF_D * SF_N;
+constexpr int SF_D = 4, SF_N = 8;
+static_assert(SF_D * SF_D * SF_N == KNN_DESC, "the matcher reads the descriptors the detector writes");
 constexpr int SF_CAND_WORDS = 8;  // x, y, size, response (f32); packed octave, layer, r, c (i32)
-constexpr int SF_KP_WORDS = 6;    // x, y, size, angle, response, octave (all f32)
 
 struct SfTaps {
     float g[SF_MAX_TAPS];
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(64) void sift_orient_kernel(SfPyramid pyr, const fl
         if (fabsf(angle - 360.0f) < FLT_EPSILON) angle = 0.0f;
         const unsigned slot = atomicAdd(counts + 3 * n + 1, 1u);
         if (slot >= (unsigned)capacity) continue;
-        float *k = raw + ((size_t)n * capacity + slot) * SF_KP_WORDS;
+        float *k = raw + ((size_t)n * capacity + slot) * KNN_KP_WORDS;
         // the first octave is -1: positions and size halve, the octave byte becomes (o - 1) & 255
         k[0] = me[0] * 0.5f, k[1] = me[1] * 0.5f, k[2] = me[2] * 0.5f, k[3] = angle, k[4] = me[3];
         k[5] = (float)((packed & ~255) | ((packed - 1) & 255));
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(64) void sift_orient_kernel(SfPyramid pyr, const fl
 // -1, 0, 1: the order of (x, y, size, angle, response, octave)
 __device__ __forceinline__ int sift_key_cmp(const float *a, const float *b) {
 #pragma unroll
-    for (int k = 0; k < SF_KP_WORDS; ++k) {
+    for (int k = 0; k < KNN_KP_WORDS; ++k) {
         if (a[k] < b[k]) return -1;
         if (a[k] > b[k]) return 1;
     }
@@ -373,16 +373,16 @@ __global__ __launch_bounds__(SF_THREADS) void sift_rank_kernel(const float *__re
     const int n = blockIdx.y, i = blockIdx.x * SF_THREADS + threadIdx.x;
     const int total = (int)min(counts[3 * n + 1], (unsigned)capacity);
     if (i >= total) return;
-    const float *base = raw + (size_t)n * capacity * SF_KP_WORDS;
-    float me[SF_KP_WORDS];
-    for (int k = 0; k < SF_KP_WORDS; ++k) me[k] = base[(size_t)i * SF_KP_WORDS + k];
+    const float *base = raw + (size_t)n * capacity * KNN_KP_WORDS;
+    float me[KNN_KP_WORDS];
+    for (int k = 0; k < KNN_KP_WORDS; ++k) me[k] = base[(size_t)i * KNN_KP_WORDS + k];
     int rank = 0;
     for (int j = 0; j < total; ++j) {
-        const int cmp = sift_key_cmp(base + (size_t)j * SF_KP_WORDS, me);
+        const int cmp = sift_key_cmp(base + (size_t)j * KNN_KP_WORDS, me);
         rank += (cmp < 0 || (cmp == 0 && j < i)) ? 1 : 0;
     }
-    float *o = sorted + ((size_t)n * capacity + rank) * SF_KP_WORDS;
-    for (int k = 0; k < SF_KP_WORDS; ++k) o[k] = me[k];
+    float *o = sorted + ((size_t)n * capacity + rank) * KNN_KP_WORDS;
+    for (int k = 0; k < KNN_KP_WORDS; ++k) o[k] = me[k];
 }
 
 // drops every keypoint equal to the one before it; grid (ceil(capacity / 256), N)
@@ -391,25 +391,25 @@ __global__ __launch_bounds__(SF_THREADS) void sift_unique_kernel(const float *__
     const int total = (int)min(counts[3 * n + 1], (unsigned)capacity);
     if (total == 0 && i == 0) counts[3 * n + 2] = 0;
     if (i >= total) return;
-    const float *base = sorted + (size_t)n * capacity * SF_KP_WORDS;
+    const float *base = sorted + (size_t)n * capacity * KNN_KP_WORDS;
     int before = 0;
-    for (int j = 1; j <= i; ++j) before += sift_key_cmp(base + (size_t)j * SF_KP_WORDS, base + (size_t)(j - 1) * SF_KP_WORDS) != 0 ? 1 : 0;
-    const bool first = i == 0 || sift_key_cmp(base + (size_t)i * SF_KP_WORDS, base + (size_t)(i - 1) * SF_KP_WORDS) != 0;
+    for (int j = 1; j <= i; ++j) before += sift_key_cmp(base + (size_t)j * KNN_KP_WORDS, base + (size_t)(j - 1) * KNN_KP_WORDS) != 0 ? 1 : 0;
+    const bool first = i == 0 || sift_key_cmp(base + (size_t)i * KNN_KP_WORDS, base + (size_t)(i - 1) * KNN_KP_WORDS) != 0;
     // `before` counts the distinct keys among 1 .. i; slot 0 is always distinct
     const int slot = first ? (i == 0 ? 0 : before) : -1;
     if (slot >= 0)
-        for (int k = 0; k < SF_KP_WORDS; ++k) out[((size_t)n * capacity + slot) * SF_KP_WORDS + k] = base[(size_t)i * SF_KP_WORDS + k];
+        for (int k = 0; k < KNN_KP_WORDS; ++k) out[((size_t)n * capacity + slot) * KNN_KP_WORDS + k] = base[(size_t)i * KNN_KP_WORDS + k];
     if (i == total - 1) counts[3 * n + 2] = (unsigned)(before + 1);
 }
 
 // one wave per keypoint; grid (capacity, N)
 __global__ __launch_bounds__(64) void sift_describe_kernel(SfPyramid pyr, const float *__restrict__ kps, int capacity, const unsigned *__restrict__ counts,
                                                            uint8_t *__restrict__ desc) {
-    __shared__ float part[64][SF_DESC + 1];
-    __shared__ float dst[SF_DESC];
+    __shared__ float part[64][KNN_DESC + 1];
+    __shared__ float dst[KNN_DESC];
     const int lane = threadIdx.x, n = blockIdx.y;
     if (blockIdx.x >= counts[3 * n + 2]) return;
-    const float *kp = kps + ((size_t)n * capacity + blockIdx.x) * SF_KP_WORDS;
+    const float *kp = kps + ((size_t)n * capacity + blockIdx.x) * KNN_KP_WORDS;
     const int packed = (int)kp[5], ob = packed & 255, layer = (packed >> 8) & 255;
     const int octave = ob < 128 ? ob : ob - 256, o = octave + 1;
     const float scale = ldexpf(1.0f, -octave);
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SfPyramid pyr, const 
     int radius = (int)rintf(hist_width * (float)1.4142135623730951 * (float)(SF_D + 1) * 0.5f);
     radius = min(radius, (int)sqrt((double)h * h + (double)w * w));
     cos_t = cos_t / hist_width, sin_t = sin_t / hist_width;
-    for (int b = 0; b < SF_DESC; ++b) part[lane][b] = 0.0f;
+    for (int b = 0; b < KNN_DESC; ++b) part[lane][b] = 0.0f;
     const int len = 2 * radius + 1;
     for (int p = lane; p < len * len; p += 64) {
         const int i = p / len - radius, j = p % len - radius;
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SfPyramid pyr, const 
         }
     }
     __syncthreads();
-    for (int b = lane; b < SF_DESC; b += 64) {
+    for (int b = lane; b < KNN_DESC; b += 64) {
         float acc = 0.0f;
         for (int l = 0; l < 64; ++l) acc = acc + part[l][b];
         dst[b] = acc;
@@ -467,34 +467,16 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SfPyramid pyr, const 
     __syncthreads();
     if (lane != 0) return;
     float nrm2 = 0.0f;
-    for (int k = 0; k < SF_DESC; ++k) nrm2 = nrm2 + dst[k] * dst[k];
+    for (int k = 0; k < KNN_DESC; ++k) nrm2 = nrm2 + dst[k] * dst[k];
     const float thr = sqrtf(nrm2) * 0.2f;
     nrm2 = 0.0f;
-    for (int k = 0; k < SF_DESC; ++k) {
+    for (int k = 0; k < KNN_DESC; ++k) {
         const float v = fminf(dst[k], thr);
         dst[k] = v, nrm2 = nrm2 + v * v;
     }
     const float s = 512.0f / fmaxf(sqrtf(nrm2), FLT_EPSILON);
-    uint8_t *out = desc + ((size_t)n * capacity + blockIdx.x) * SF_DESC;
-    for (int k = 0; k < SF_DESC; ++k) out[k] = (uint8_t)fminf(fmaxf(rintf(dst[k] * s), 0.0f), 255.0f);
-}
-
-// The two nearest train descriptors of every query descriptor; one thread per query, grid (ceil(max Q / 64), pairs).  Pair p: queries of picture q_base + p,
-// trains of picture t_base + p, `stride` descriptors a picture; their numbers from counts[3 * picture + 2] when counts is given, else Q and T.
-__global__ __launch_bounds__(KNN_TILE) void knn_kernel(const uint8_t *__restrict__ query, const uint8_t *__restrict__ train, const unsigned *__restrict__ counts,
-                                                       int q_base, int t_base, int stride, int Q, int T, int32_t *__restrict__ idx, float *__restrict__ dist) {
-    __shared__ unsigned tile[KNN_TILE][KNN_WORDS + 1];
-    const int p = blockIdx.y, q = blockIdx.x * KNN_TILE + threadIdx.x;
-    if (counts) Q = (int)min(counts[3 * (q_base + p) + 2], (unsigned)stride), T = (int)min(counts[3 * (t_base + p) + 2], (unsigned)stride);
-    if ((int)blockIdx.x * KNN_TILE >= Q) return;
-    const unsigned *qd = (const unsigned *)(query + (size_t)(q_base + p) * stride * SF_DESC), *td = (const unsigned *)(train + (size_t)(t_base + p) * stride * SF_DESC);
-    unsigned b0, b1;
-    int i0, i1;
-    knn_two_nearest(qd, td, Q, T, q, tile, b0, b1, i0, i1);  // knn_core.hpp
-    if (q >= Q) return;
-    const size_t at = ((size_t)p * stride + q) * 2;
-    idx[at] = i0, idx[at + 1] = i1;
-    dist[at] = i0 < 0 ? INFINITY : sqrtf((float)b0), dist[at + 1] = i1 < 0 ? INFINITY : sqrtf((float)b1);
+    uint8_t *out = desc + ((size_t)n * capacity + blockIdx.x) * KNN_DESC;
+    for (int k = 0; k < KNN_DESC; ++k) out[k] = (uint8_t)fminf(fmaxf(rintf(dst[k] * s), 0.0f), 255.0f);
 }
 
 // the ratio test and the mean distance of a pair; one thread per pair
@@ -503,8 +485,8 @@ __global__ __launch_bounds__(64) void mifd_kernel(const float *__restrict__ kps,
                                                   double *__restrict__ score, int32_t *__restrict__ matches) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= pairs) return;
-    const int Q = (int)min(counts[3 * (q_base + p) + 2], (unsigned)stride), T = (int)min(counts[3 * (t_base + p) + 2], (unsigned)stride);
-    const float *qk = kps + (size_t)(q_base + p) * stride * SF_KP_WORDS, *tk = kps + (size_t)(t_base + p) * stride * SF_KP_WORDS;
+    const int Q = knn_count(counts, q_base + p, stride), T = knn_count(counts, t_base + p, stride);
+    const float *qk = kps + (size_t)(q_base + p) * stride * KNN_KP_WORDS, *tk = kps + (size_t)(t_base + p) * stride * KNN_KP_WORDS;
     int kept = 0;
     double sum = 0.0;
     if (Q >= 2 && T >= 2)
@@ -512,7 +494,7 @@ __global__ __launch_bounds__(64) void mifd_kernel(const float *__restrict__ kps,
             const size_t at = ((size_t)p * stride + q) * 2;
             if (!(dist[at] < ratio * dist[at + 1])) continue;
             const int j = idx[at];
-            const float dx = qk[(size_t)q * SF_KP_WORDS] - tk[(size_t)j * SF_KP_WORDS], dy = qk[(size_t)q * SF_KP_WORDS + 1] - tk[(size_t)j * SF_KP_WORDS + 1];
+            const float dx = qk[(size_t)q * KNN_KP_WORDS] - tk[(size_t)j * KNN_KP_WORDS], dy = qk[(size_t)q * KNN_KP_WORDS + 1] - tk[(size_t)j * KNN_KP_WORDS + 1];
             const double ddx = (double)dx, ddy = (double)dy;
             sum = sum + sqrt(ddx * ddx + ddy * ddy);
             ++kept;
@@ -520,8 +502,6 @@ __global__ __launch_bounds__(64) void mifd_kernel(const float *__restrict__ kps,
     matches[p] = kept;
     score[p] = (Q < 2 || T < 2 || kept < min_matches || kept == 0) ? (double)NAN : sum / (double)kept;
 }
-
-int sf_div_up(long long a, int b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 
@@ -585,8 +565,8 @@ int hive_sift_create(hive_ctx *ctx, int H, int W, int max_images, int nfeatures,
             h /= 2, w /= 2;
         }
         s->cand = lay.take<float>((size_t)max_images * capacity * SF_CAND_WORDS);
-        s->raw = lay.take<float>((size_t)max_images * capacity * SF_KP_WORDS);
-        s->sorted = lay.take<float>((size_t)max_images * capacity * SF_KP_WORDS);
+        s->raw = lay.take<float>((size_t)max_images * capacity * KNN_KP_WORDS);
+        s->sorted = lay.take<float>((size_t)max_images * capacity * KNN_KP_WORDS);
         if (pass == 0) {
             const hipError_t e = hipMalloc(&s->mem, lay.bytes());
             if (e != hipSuccess) {
@@ -620,19 +600,19 @@ int hive_sift_detect(hive_sift *sift, const uint8_t *d_gray, const uint8_t *d_ma
     const int H = sift->H, W = sift->W, L = sift->layers, L3 = L + 3, cap = sift->capacity;
     unsigned *counts = (unsigned *)d_counts;
     HIVE_CHECK_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)N * 3 * sizeof(unsigned), st));
-    hipLaunchKernelGGL(sift_base_kernel, dim3((unsigned)sf_div_up(4ll * H * W, SF_THREADS), (unsigned)N), dim3(SF_THREADS), 0, st, d_gray, H, W, sift->base);
+    hipLaunchKernelGGL(sift_base_kernel, dim3((unsigned)hive_div_up(4ll * H * W, SF_THREADS), (unsigned)N), dim3(SF_THREADS), 0, st, d_gray, H, W, sift->base);
     SfPyramid pyr = {};
     pyr.octaves = sift->octaves, pyr.layers = L;
     for (int o = 0; o < sift->octaves; ++o) {
         const int h = sift->oh[o], w = sift->ow[o];
         const size_t plane = (size_t)h * w, stride = plane * L3;
-        const dim3 tiles((unsigned)sf_div_up(w, SF_TILE), (unsigned)sf_div_up(h, SF_TILE), (unsigned)N);
+        const dim3 tiles((unsigned)hive_div_up(w, SF_TILE), (unsigned)hive_div_up(h, SF_TILE), (unsigned)N);
         pyr.gauss[o] = sift->gauss[o], pyr.h[o] = h, pyr.w[o] = w;
         if (o == 0) {
             hipLaunchKernelGGL(sift_blur_kernel, tiles, dim3(SF_THREADS), 0, st, sift->base, plane, sift->gauss[0], stride, h, w, sift->taps[0]);
         } else {
             const int ph = sift->oh[o - 1], pw = sift->ow[o - 1];
-            hipLaunchKernelGGL(sift_half_kernel, dim3((unsigned)sf_div_up((long long)plane, SF_THREADS), (unsigned)N), dim3(SF_THREADS), 0, st,
+            hipLaunchKernelGGL(sift_half_kernel, dim3((unsigned)hive_div_up((long long)plane, SF_THREADS), (unsigned)N), dim3(SF_THREADS), 0, st,
                                sift->gauss[o - 1] + (size_t)L * ph * pw, (size_t)ph * pw * L3, pw, sift->gauss[o], stride, h, w);
         }
         for (int i = 1; i < L3; ++i)
@@ -650,11 +630,11 @@ int hive_sift_detect(hive_sift *sift, const uint8_t *d_gray, const uint8_t *d_ma
         a.octave = o, a.h = h, a.w = w, a.layers = L, a.H = H, a.W = W, a.capacity = cap;
         a.threshold = (float)std::floor(0.5 * (double)sift->contrast_threshold / L * 255.0);
         a.contrast_threshold = sift->contrast_threshold, a.edge_threshold = sift->edge_threshold, a.sigma = sift->sigma;
-        hipLaunchKernelGGL(sift_detect_kernel, dim3((unsigned)sf_div_up((long long)h * w, SF_THREADS), (unsigned)(N * L)), dim3(SF_THREADS), 0, st, sift->gauss[o],
+        hipLaunchKernelGGL(sift_detect_kernel, dim3((unsigned)hive_div_up((long long)h * w, SF_THREADS), (unsigned)(N * L)), dim3(SF_THREADS), 0, st, sift->gauss[o],
                            (size_t)h * w * L3, a, d_mask, counts, sift->cand);
     }
     hipLaunchKernelGGL(sift_orient_kernel, dim3((unsigned)cap, (unsigned)N), dim3(64), 0, st, pyr, sift->cand, cap, sift->nfeatures, counts, sift->raw);
-    const dim3 per_kp((unsigned)sf_div_up(cap, SF_THREADS), (unsigned)N);
+    const dim3 per_kp((unsigned)hive_div_up(cap, SF_THREADS), (unsigned)N);
     hipLaunchKernelGGL(sift_rank_kernel, per_kp, dim3(SF_THREADS), 0, st, sift->raw, cap, counts, sift->sorted);
     hipLaunchKernelGGL(sift_unique_kernel, per_kp, dim3(SF_THREADS), 0, st, sift->sorted, cap, counts, d_keypoints);
     if (sift->last_stage != 2) hipLaunchKernelGGL(sift_describe_kernel, dim3((unsigned)cap, (unsigned)N), dim3(64), 0, st, pyr, d_keypoints, cap, counts, d_descriptors);
@@ -699,8 +679,8 @@ int hive_knn_match(hive_ctx *ctx, const uint8_t *d_query, int Q, const uint8_t *
     HIVE_REQUIRE(ctx, d_query && d_train && d_indices && d_distances, "knn_match: NULL argument");
     HIVE_REQUIRE(ctx, Q >= 1 && T >= 1 && Q < (1 << 24) && T < (1 << 24), "knn_match: Q = %d, T = %d, need 1 .. 2^24 - 1", Q, T);
     HIVE_REQUIRE(ctx, ((uintptr_t)d_query | (uintptr_t)d_train) % 4 == 0, "knn_match: the descriptors must be 4-byte aligned");
-    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)sf_div_up(Q, KNN_TILE), 1u), dim3(KNN_TILE), 0, ctx->stream, d_query, d_train, (const unsigned *)nullptr, 0, 0,
-                       Q > T ? Q : T, Q, T, d_indices, d_distances);
+    const KnnArgs a = {d_query, d_train, nullptr, nullptr, 0, 0, 0, Q > T ? Q : T, Q, T};
+    hipLaunchKernelGGL(knn_match_kernel, dim3((unsigned)hive_div_up(Q, KNN_TILE), 1u), dim3(KNN_TILE), 0, ctx->stream, a, d_indices, d_distances);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
 }
@@ -713,9 +693,9 @@ int hive_mifd(hive_ctx *ctx, const float *d_keypoints, const uint8_t *d_descript
     HIVE_REQUIRE(ctx, capacity >= 1 && capacity <= 65535 && pairs >= 1 && pairs <= 65535 && query_first >= 0 && train_first >= 0,
                  "mifd: capacity = %d, pairs = %d (1 .. 65535 each), first pictures %d and %d", capacity, pairs, query_first, train_first);
     HIVE_REQUIRE(ctx, (uintptr_t)d_descriptors % 4 == 0, "mifd: the descriptors must be 4-byte aligned");
-    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)sf_div_up(capacity, KNN_TILE), (unsigned)pairs), dim3(KNN_TILE), 0, ctx->stream, d_descriptors, d_descriptors,
-                       (const unsigned *)d_counts, query_first, train_first, capacity, 0, 0, d_indices, d_distances);
-    hipLaunchKernelGGL(mifd_kernel, dim3((unsigned)sf_div_up(pairs, 64)), dim3(64), 0, ctx->stream, d_keypoints, (const unsigned *)d_counts, query_first, train_first, capacity,
+    const KnnArgs a = {d_descriptors, d_descriptors, (const unsigned *)d_counts, nullptr, 0, query_first, train_first, capacity, 0, 0};
+    hipLaunchKernelGGL(knn_match_kernel, dim3((unsigned)hive_div_up(capacity, KNN_TILE), (unsigned)pairs), dim3(KNN_TILE), 0, ctx->stream, a, d_indices, d_distances);
+    hipLaunchKernelGGL(mifd_kernel, dim3((unsigned)hive_div_up(pairs, 64)), dim3(64), 0, ctx->stream, d_keypoints, (const unsigned *)d_counts, query_first, train_first, capacity,
                        pairs, d_indices, d_distances, ratio_threshold, min_matches, d_scores, d_matches);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;

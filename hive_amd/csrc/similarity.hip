@@ -30,15 +30,6 @@ constexpr int MS_LEVELS = 5;
 
 __device__ __forceinline__ int sm_gray(int c0, int c1, int c2, int w0, int w2) { return (w0 * c0 + 9617 * c1 + w2 * c2 + 8192) >> 14; }
 
-// v[0] = the sum of v[0 .. 256) by the fixed tree: v[t] += v[t + off], off = 128 .. 1
-__device__ __forceinline__ void sm_tree(double *v) {
-    __syncthreads();
-    for (int off = SM_THREADS / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) v[threadIdx.x] = v[threadIdx.x] + v[threadIdx.x + off];
-        __syncthreads();
-    }
-}
-
 // grid (tiles_x, tiles_y, variants * N)
 __global__ __launch_bounds__(SM_THREADS) void similarity_ssim_kernel(const uint8_t *__restrict__ ref, const uint8_t *__restrict__ est, int N, int H, int W, int w0,
                                                                      int w2, double *__restrict__ partials, unsigned long long *__restrict__ sse,
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(SM_THREADS) void similarity_ssim_kernel(const uint8
         if (map) map[((size_t)z * Hm + i) * Wm + j] = S;
     }
     red[t] = acc;
-    sm_tree(red);
+    block_tree_sum<SM_THREADS, 1>(&red);
     if (t == 0) {
         partials[((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = red[0];
         if (sse_tile) atomicAdd(sse + z, (unsigned long long)sse_tile);
@@ -178,11 +169,11 @@ __global__ __launch_bounds__(SM_THREADS) void similarity_msssim_kernel(const uin
     }
     const size_t tiles = (size_t)gridDim.x * gridDim.y, tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     red[t] = acc_cs;
-    sm_tree(red);
+    block_tree_sum<SM_THREADS, 1>(&red);
     if (t == 0) partials[(size_t)z * tiles + tile] = red[0];
     __syncthreads();
     red[t] = acc_ssim;
-    sm_tree(red);
+    block_tree_sum<SM_THREADS, 1>(&red);
     if (t == 0) partials[((size_t)gridDim.z + z) * tiles + tile] = red[0];
 }
 
@@ -230,7 +221,7 @@ __global__ __launch_bounds__(SM_THREADS) void similarity_finish_kernel(const dou
     double acc = 0.0;
     for (long long k = threadIdx.x; k < per_row; k += SM_THREADS) acc = acc + row[k];
     red[threadIdx.x] = acc;
-    sm_tree(red);
+    block_tree_sum<SM_THREADS, 1>(&red);
     if (threadIdx.x == 0) out[blockIdx.x] = red[0] / divisor;
 }
 
@@ -252,8 +243,6 @@ __global__ __launch_bounds__(SM_THREADS) void similarity_combine_kernel(const do
     out[e] = sum / 3.0;
 }
 
-int sm_div_up(int a, int b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 extern "C" {
@@ -270,7 +259,7 @@ int hive_similarity_ssim_psnr(hive_ctx *ctx, const uint8_t *d_ref, const uint8_t
     HIVE_REQUIRE(ctx, (long long)variants * N <= 65535, "similarity_ssim_psnr: variants * N = %lld exceeds 65535", (long long)variants * N);
     HIVE_REQUIRE(ctx, rgb_order == 0 || rgb_order == 1, "similarity_ssim_psnr: rgb_order = %d, need 0 (bgr) or 1 (rgb)", rgb_order);
     HIVE_CHECK_HIP(ctx, hipMemsetAsync(d_sse, 0, (size_t)variants * N * sizeof(int64_t), ctx->stream));
-    const dim3 grid((unsigned)sm_div_up(W - (SM_WIN - 1), SM_TILE), (unsigned)sm_div_up(H - (SM_WIN - 1), SM_TILE), (unsigned)(variants * N));
+    const dim3 grid((unsigned)hive_div_up(W - (SM_WIN - 1), SM_TILE), (unsigned)hive_div_up(H - (SM_WIN - 1), SM_TILE), (unsigned)(variants * N));
     HIVE_REQUIRE(ctx, grid.y <= 65535, "similarity_ssim_psnr: H = %d has too many tile rows", H);
     hipLaunchKernelGGL(similarity_ssim_kernel, grid, dim3(SM_THREADS), 0, ctx->stream, d_ref, d_est, N, H, W, rgb_order ? 4899 : 1868, rgb_order ? 1868 : 4899,
                        d_partials, (unsigned long long *)d_sse, d_map, d_gray_ref, d_gray_est);
@@ -293,7 +282,7 @@ int hive_similarity_msssim_level(hive_ctx *ctx, const uint8_t *d_ref_u8, const u
     HIVE_REQUIRE(ctx, (long long)variants * N * 3 <= 65535, "similarity_msssim_level: variants * N * 3 = %lld exceeds 65535", (long long)variants * N * 3);
     MsWindow win;
     memcpy(win.g, window, sizeof(win.g));
-    const dim3 grid((unsigned)sm_div_up(w - (MS_TAPS - 1), MS_TW), (unsigned)sm_div_up(h - (MS_TAPS - 1), MS_TH), (unsigned)(variants * N * 3));
+    const dim3 grid((unsigned)hive_div_up(w - (MS_TAPS - 1), MS_TW), (unsigned)hive_div_up(h - (MS_TAPS - 1), MS_TH), (unsigned)(variants * N * 3));
     HIVE_REQUIRE(ctx, grid.y <= 65535, "similarity_msssim_level: h = %d has too many tile rows", h);
     const long long n = (long long)(variants + 1) * N * 3 * ((h + 1) / 2) * ((w + 1) / 2);  // pooled values
     HIVE_REQUIRE(ctx, (n + SM_THREADS - 1) / SM_THREADS < (1ll << 31), "similarity_msssim_level: %lld pooled values are too many for one launch", n);

@@ -138,14 +138,7 @@ __global__ __launch_bounds__(TK_THREADS) void icp_terms_kernel(IcpParams p, cons
     }
 #pragma unroll
     for (int q = 0; q < TK_COLS; ++q) red[q][t] = term[q];
-    __syncthreads();
-    for (int off = TK_THREADS / 2; off > 0; off >>= 1) {
-        if (t < off) {
-#pragma unroll
-            for (int q = 0; q < TK_COLS; ++q) red[q][t] = red[q][t] + red[q][t + off];
-        }
-        __syncthreads();
-    }
+    block_tree_sum<TK_THREADS, TK_COLS>(red);
     if (t < TK_COLS) partials[(size_t)blockIdx.x * TK_COLS + t] = red[t][0];
 }
 
@@ -157,8 +150,6 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(const double *__restrict
     for (long long b = 0; b < rows; ++b) acc = acc + partials[(size_t)b * TK_COLS + q];
     out[q] = acc;
 }
-
-dim3 tk_grid(long long n) { return dim3((unsigned)((n + TK_THREADS - 1) / TK_THREADS)); }
 
 }  // namespace
 
@@ -184,13 +175,13 @@ int hive_frame_maps(hive_ctx *ctx, const float *d_depth, int H, int W, const flo
             const size_t from = at;
             at += (size_t)hs * ws, h = hs / 2, w = ws / 2;
             fx = fx / 2.0, fy = fy / 2.0, cx = (cx - 0.5) / 2.0, cy = (cy - 0.5) / 2.0;
-            hipLaunchKernelGGL(pyr_down_kernel, tk_grid((long long)h * w), dim3(TK_THREADS), 0, ctx->stream, (const float *)(d_depth_pyr + from), ws, d_depth_pyr + at, h,
+            hipLaunchKernelGGL(pyr_down_kernel, dim3((unsigned)hive_div_up((long long)h * w, TK_THREADS)), dim3(TK_THREADS), 0, ctx->stream, (const float *)(d_depth_pyr + from), ws, d_depth_pyr + at, h,
                                w, pyr_delta);
         }
         float *Kl = K_levels + 9 * l;
         Kl[0] = (float)fx, Kl[1] = 0.f, Kl[2] = (float)cx, Kl[3] = 0.f, Kl[4] = (float)fy, Kl[5] = (float)cy, Kl[6] = 0.f, Kl[7] = 0.f, Kl[8] = 1.f;
         const MapCam c = {Kl[0], Kl[4], Kl[2], Kl[5]};
-        hipLaunchKernelGGL(frame_maps_kernel, tk_grid((long long)h * w), dim3(TK_THREADS), 0, ctx->stream, (const float *)(d_depth_pyr + at), h, w, c,
+        hipLaunchKernelGGL(frame_maps_kernel, dim3((unsigned)hive_div_up((long long)h * w, TK_THREADS)), dim3(TK_THREADS), 0, ctx->stream, (const float *)(d_depth_pyr + at), h, w, c,
                            d_vertex_pyr + 3 * at, d_normal_pyr + 3 * at);
     }
     HIVE_CHECK_HIP(ctx, hipGetLastError());

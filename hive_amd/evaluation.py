@@ -18,6 +18,7 @@ import numpy as np
 
 from hive_amd import _lib
 from hive_amd._lib import ptr
+from hive_amd._pictures import device_of, is_torch, on_device
 
 NAN = float("nan")
 _MS_LEVELS = 5
@@ -26,10 +27,6 @@ LPIPS_MIN_SIDE = 31  # conv1 gives 7, the two pools 3 and 1: the smallest pictur
 # indices in torchvision's alexnet().features
 _LPIPS_LAYERS = ((3, 64, 11, 4, 2, False), (64, 192, 5, 1, 2, True), (192, 384, 3, 1, 1, True), (384, 256, 3, 1, 1, False), (256, 256, 3, 1, 1, False))
 _ALEX_INDEX = (0, 3, 6, 8, 10)
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 @dataclass
@@ -81,17 +78,6 @@ def _checked_shapes(ref, est, ms_ssim, channel_order):
     return n, h, w, batched
 
 
-def _as_device(a, dev, n, h, w):
-    """The pictures as one contiguous uint8 (n, h, w, 3) tensor on ``dev``: numpy arrays are uploaded, device tensors used in place when contiguous."""
-    import torch
-    if not _is_torch(a):
-        a = np.ascontiguousarray(a)
-        with warnings.catch_warnings():  # a read-only array is fine: it is only copied to the device
-            warnings.simplefilter("ignore", UserWarning)
-            a = torch.from_numpy(a)
-    return a.to(dev).reshape(n, h, w, 3).contiguous()
-
-
 def _psnr(sse, h, w):
     """10 log10(255^2 / mse) in float64 from the integer sums; inf where the planes are equal."""
     out = np.full(sse.shape, np.inf)
@@ -126,12 +112,12 @@ def image_similarity(ref, est, *, ms_ssim=False, mask_background=False, channel_
     and the scores are copied back).  A pair without a score is nan, with the reference's warning; so is a picture with a side below 6, which SIFT cannot handle."""
     n, h, w, batched = _checked_shapes(ref, est, ms_ssim, channel_order)
     import torch
-    dev = next((a.device for a in (ref, est) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
-    ctx = ctx or _lib.default_context(dev.index or 0)
-    ctx.follow_torch_stream()
+    dev = device_of(ref, est)
+    ctx = _lib.context_for(ctx, dev)
     lib, handle = ctx.lib, ctx.handle
 
-    ref_d, est_d = _as_device(ref, dev, n, h, w), _as_device(est, dev, n, h, w)
+    # numpy arrays are uploaded, device tensors used in place when contiguous
+    ref_d, est_d = on_device(ref, dev, shape=(n, h, w, 3)), on_device(est, dev, shape=(n, h, w, 3))
     variants = 2 if mask_background else 1
     vn = variants * n
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
@@ -251,7 +237,7 @@ class LPIPS:
 
     @staticmethod
     def _array(value):
-        return np.asarray(value.detach().cpu().numpy() if _is_torch(value) else value)
+        return np.asarray(value.detach().cpu().numpy() if is_torch(value) else value)
 
     @classmethod
     def from_state_dict(cls, *state_dicts):
@@ -341,7 +327,7 @@ class LPIPS:
         hp, wp = ((h - 3) // 2 + 1, (w - 3) // 2 + 1) if pool else (h, w)
         if min(h, w) < (3 if pool else 1) or min(hp, wp) + 2 * pad < k:
             raise ValueError(f"layer {index} has no output at {h} x {w}")
-        ctx = (ctx or _lib.default_context(x.device.index or 0)).follow_torch_stream()
+        ctx = _lib.context_for(ctx, x.device)
         x = x.contiguous()
         out = torch.empty((n, (hp + 2 * pad - k) // stride + 1, (wp + 2 * pad - k) // stride + 1, cout), dtype=torch.float32, device=x.device)
         ctx.check(ctx.lib.hive_lpips_layer(self.native(ctx), index, ptr(x), n, h, w, ptr(out)))
@@ -356,9 +342,9 @@ class LPIPS:
         n, h, w, _ = _checked_shapes(ref, est, False, "bgr")
         if min(h, w) < LPIPS_MIN_SIDE:
             raise ValueError(f"{h} x {w} is smaller than {LPIPS_MIN_SIDE} x {LPIPS_MIN_SIDE}, the smallest picture with an output in every LPIPS layer")
-        dev = next((a.device for a in (ref, est) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
-        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
-        ref_d, est_d = _as_device(ref, dev, n, h, w), _as_device(est, dev, n, h, w)
+        dev = device_of(ref, est)
+        ctx = _lib.context_for(ctx, dev)
+        ref_d, est_d = on_device(ref, dev, shape=(n, h, w, 3)), on_device(est, dev, shape=(n, h, w, 3))
         variants = 2 if mask_background else 1
         vn = variants * n
         results = torch.empty(6 * vn, dtype=torch.float64, device=dev)  # [0, vn) the scores, then the layer scores [5][variants][n]

@@ -14,14 +14,11 @@ import numpy as np
 
 from hive_amd import _lib
 from hive_amd._lib import ptr
+from hive_amd._pictures import device_of, is_torch, on_device
 
 NAN = float("nan")
 SIFT_MIN_SIDE = 6  # the doubled picture must reach past the 5-pixel border on both sides
 KEYPOINT_FIELDS = ("x", "y", "size", "angle", "response", "octave")
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 def blur_sigmas(n_octave_layers=3, sigma=1.6):
@@ -110,7 +107,7 @@ class SIFT:
             pass
 
     def _context(self, dev):
-        return (self.ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        return _lib.context_for(self.ctx, dev)
 
     def detect_device(self, gray, mask=None, ctx=None, out=None, first=0):
         """The launches alone, nothing synchronises: ``gray`` (and ``mask``) contiguous uint8 device tensors (N, H, W) -> device tensors ``(keypoints float32
@@ -143,21 +140,12 @@ class SIFT:
                 raise _lib.HiveError(_lib.ERR_INVALID, f"SIFT: picture {i} has {int(count)} {what}, more than the capacity {self.capacity}; make the SIFT with a larger capacity")
 
     def _pictures(self, gray, mask):
-        import torch
         batched = len(gray.shape) == 3
         if len(gray.shape) not in (2, 3):
             raise ValueError(f"gray pictures are (H, W) or (N, H, W), got {tuple(gray.shape)}")
-        dev = next((a.device for a in (gray, mask) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
-
-        def device(a, name):
-            if str(a.dtype).replace("torch.", "") != "uint8":
-                raise ValueError(f"{name}: uint8, got {a.dtype}")
-            if not _is_torch(a):
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore", UserWarning)
-                    a = torch.from_numpy(np.ascontiguousarray(a))
-            a = a.to(dev)
-            return (a if batched else a[None]).contiguous()
+        dev = device_of(gray, mask)
+        device = lambda a, name: on_device(a, dev, check=lambda dtype, _: dtype == "uint8", error=lambda a: f"{name}: uint8, got {a.dtype}",
+                                           shape=(-1,) + tuple(gray.shape[-2:]))
         g = device(gray, "gray")
         m = None
         if mask is not None:
@@ -203,21 +191,16 @@ def knn_match(query, train, ctx=None):
     distance, ties to the lower train index: ``(indices int32 (Q, 2), distances float32 (Q, 2))``, of the kind ``query`` is.  With fewer than two train descriptors
     the missing entries are -1 and inf.  This is the exact answer: not pinned against the reference's approximate FLANN search."""
     import torch
-    as_numpy = not _is_torch(query)
-    dev = next((a.device for a in (query, train) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
-
-    def device(a, name):
-        if str(a.dtype).replace("torch.", "") != "uint8" or len(a.shape) != 2 or a.shape[1] != 128:
-            raise ValueError(f"{name}: uint8 (K, 128) descriptors, got {a.dtype} {tuple(a.shape)}")
-        if not _is_torch(a):
-            a = torch.from_numpy(np.ascontiguousarray(a))
-        return a.to(dev).contiguous()
+    as_numpy = not is_torch(query)
+    dev = device_of(query, train)
+    device = lambda a, name: on_device(a, dev, check=lambda dtype, shape: dtype == "uint8" and len(shape) == 2 and shape[1] == 128,
+                                       error=lambda a: f"{name}: uint8 (K, 128) descriptors, got {a.dtype} {tuple(a.shape)}")
     q, t = device(query, "query"), device(train, "train")
     nq, nt = int(q.shape[0]), int(t.shape[0])
     idx = torch.full((nq, 2), -1, dtype=torch.int32, device=dev)
     dist = torch.full((nq, 2), float("inf"), dtype=torch.float32, device=dev)
     if nq and nt:
-        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx = _lib.context_for(ctx, dev)
         ctx.check(ctx.lib.hive_knn_match(ctx.handle, ptr(q), nq, ptr(t), nt, ptr(idx), ptr(dist)))
     return (idx.cpu().numpy(), dist.cpu().numpy()) if as_numpy else (idx, dist)
 
@@ -319,7 +302,7 @@ def match_pairs(features, pairs, depth, ratio=0.7, min_features=2, return_table=
     import torch
     kps, desc, counts = features
     dev, cap, n = kps.device, int(kps.shape[1]), int(kps.shape[0])
-    if not _is_torch(pairs):
+    if not is_torch(pairs):
         host = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
         if len(host) and (host.min() < 0 or host.max() >= n):
             raise ValueError(f"pairs name pictures {int(host.min())} .. {int(host.max())}; the features hold {n}")
@@ -334,7 +317,7 @@ def match_pairs(features, pairs, depth, ratio=0.7, min_features=2, return_table=
     idx = torch.empty((p, cap, 2), dtype=torch.int32, device=dev) if return_table else None
     dist = torch.empty((p, cap, 2), dtype=torch.float32, device=dev) if return_table else None
     if p:
-        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx = _lib.context_for(ctx, dev)
         ctx.check(ctx.lib.hive_pairs_match(ctx.handle, ptr(kps), ptr(desc), ptr(counts), cap, n, ptr(pairs), p, ptr(depth), int(depth.shape[1]), int(depth.shape[2]),
                                            float(ratio), int(min_features), ptr(rows), ptr(pair_counts), ptr(idx), ptr(dist)))
     return (rows, pair_counts, idx, dist) if return_table else (rows, pair_counts)
@@ -353,7 +336,7 @@ def ransac_homography(rows, counts, keys, threshold=3.0, trials=2000, seed=0, mi
     dev, p, stride, words = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(rows.shape[2])
     if counts.dtype != torch.int32 or counts.dim() != 1 or int(counts.shape[0]) != p:
         raise ValueError(f"counts: int32 (P,) with P = {p}, got {counts.dtype} {tuple(counts.shape)}")
-    if not _is_torch(keys):
+    if not is_torch(keys):
         keys = torch.from_numpy(np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1, 2).astype(np.int32))).to(dev)
     if keys.dtype != torch.int32 or tuple(keys.shape) != (p, 2):
         raise ValueError(f"keys: int32 (P, 2) with P = {p}, got {keys.dtype} {tuple(keys.shape)}")
@@ -362,7 +345,7 @@ def ransac_homography(rows, counts, keys, threshold=3.0, trials=2000, seed=0, mi
     mask = torch.empty((p, max(stride, 1)), dtype=torch.uint8, device=dev)[:, :stride]
     result = torch.empty((p, 3), dtype=torch.int32, device=dev)
     if p and stride:
-        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx = _lib.context_for(ctx, dev)
         ctx.check(ctx.lib.hive_ransac_homography(ctx.handle, ptr(rows), words, ptr(counts), int(counts.stride(0)), ptr(keys), p, stride, float(threshold), int(trials),
                                                  int(seed) & 0xFFFFFFFF, int(min_count), ptr(H), ptr(mask), ptr(result)))
     elif p:
@@ -378,15 +361,10 @@ def find_homography(points_i, points_j, threshold=3.0, trials=2000, seed=0, pair
     ``trials`` are cv2's defaults (ransacReprojThreshold 3, maxIters 2000, from recall).  The draws depend on ``seed`` and ``pair_key`` alone, so the result is a
     function of the arguments.  ``return_stats``: also ``(winning trial, the winner's count, the final count)``.  Not pinned against cv2: USAC_MAGSAC is randomised."""
     import torch
-    as_numpy = not _is_torch(points_i)
-    dev = next((a.device for a in (points_i, points_j) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
-
-    def device(a, name):
-        if not _is_torch(a):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 2)))
-        if a.dim() != 2 or a.shape[1] != 2:
-            raise ValueError(f"{name}: (M, 2) points, got {tuple(a.shape)}")
-        return a.to(dev, torch.float32)
+    as_numpy = not is_torch(points_i)
+    dev = device_of(points_i, points_j)
+    device = lambda a, name: on_device(a if is_torch(a) else np.asarray(a, dtype=np.float32).reshape(-1, 2), dev, dtype=torch.float32,
+                                       check=lambda _, shape: len(shape) == 2 and shape[1] == 2, error=lambda a: f"{name}: (M, 2) points, got {tuple(a.shape)}")
     a, b = device(points_i, "points_i"), device(points_j, "points_j")
     if a.shape != b.shape:
         raise ValueError(f"points_i {tuple(a.shape)} and points_j {tuple(b.shape)} differ")
@@ -412,6 +390,6 @@ def compact_pairs(rows, counts, mask, result, min_features, ctx=None):
     kept = torch.zeros(p, dtype=torch.int32, device=dev)
     offsets = torch.zeros(p + 1, dtype=torch.int64, device=dev)
     if p:
-        ctx = (ctx or _lib.default_context(dev.index or 0)).follow_torch_stream()
+        ctx = _lib.context_for(ctx, dev)
         ctx.check(ctx.lib.hive_pairs_compact(ctx.handle, ptr(rows), ptr(counts), ptr(mask), ptr(result), p, stride, int(min_features), ptr(out), ptr(kept), ptr(offsets)))
     return out, kept, offsets

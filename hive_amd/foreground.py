@@ -21,12 +21,9 @@ import numpy as np
 
 from hive_amd import _lib
 from hive_amd._lib import MEM_DEVICE, MEM_HOST, ptr
+from hive_amd._pictures import is_torch as _is_torch
 from hive_amd.options import MeshDecimationOptions, MeshFilteringOptions
 from hive_amd.utils import validate_camera_parameter_shapes, validate_shape
-
-
-def _is_torch(x):
-    return hasattr(x, "data_ptr")
 
 
 def grid_faces(depth, mask, options: MeshFilteringOptions = None, ctx=None, return_vertex_count=False):

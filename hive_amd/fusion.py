@@ -16,6 +16,7 @@ import numpy as np
 
 from hive_amd import _lib
 from hive_amd._lib import MEM_DEVICE, MEM_HOST, ptr
+from hive_amd._pictures import is_torch as _is_torch
 from hive_amd.options import MaskDilationOptions
 
 
@@ -24,10 +25,6 @@ def rigid_transform(xyz, transform):
     xyz_h = np.hstack([xyz, np.ones((len(xyz), 1), dtype=np.float32)])
     xyz_t_h = np.dot(transform, xyz_h.T).T
     return xyz_t_h[:, :3]
-
-
-def _is_torch(x):
-    return hasattr(x, "data_ptr")
 
 
 def get_view_frustum(depth_im, cam_intr, cam_pose, ctx=None):

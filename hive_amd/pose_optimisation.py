@@ -48,8 +48,7 @@ def centroids(depth, masks, camera_matrix, ctx=None):
     from hive_amd.geometric import _kinv
     assert depth.dtype == torch.float32 and masks.dtype == torch.uint8 and depth.dim() == 3 and tuple(depth.shape) == tuple(masks.shape), \
         "depth float32 (n, H, W) and masks uint8 (n, H, W) device tensors"
-    ctx = ctx or _lib.default_context(depth.device.index or 0)
-    ctx.follow_torch_stream()
+    ctx = _lib.context_for(ctx, depth.device)
     depth, masks = depth.contiguous(), masks.contiguous()
     n, h, w = (int(v) for v in depth.shape)
     Kinv = _kinv(np.asarray(camera_matrix).reshape(3, 3))
@@ -628,8 +627,7 @@ def optimise_poses(feature_set, parameters, options=None, residual_type=Residual
         raise ValueError("the feature set holds no correspondence")
     if feature_set.frame_i.index.device.type != "cuda":
         raise ValueError("the feature set must be on the device (FeatureSet.to('cuda')): hive_amd has no CPU fallback")
-    ctx = ctx or _lib.default_context(feature_set.frame_i.index.device.index or 0)
-    ctx.follow_torch_stream()
+    ctx = _lib.context_for(ctx, feature_set.frame_i.index.device)
     epochs = int(options.num_epochs if num_epochs is None else num_epochs)
     affine = alignment == AlignmentType.Affine
     K = feature_set.camera_matrix.detach().cpu().numpy().astype(np.float64)

@@ -8,11 +8,8 @@ import numpy as np
 
 from hive_amd import _lib
 from hive_amd._lib import ptr
+from hive_amd._pictures import is_torch as _is_torch
 from hive_amd.geometric import CameraMatrix, pose_vec2mat
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 def _host(a):

@@ -42,6 +42,65 @@ def literal_bound(vertices, t):
     return 16 * U * (np.linalg.norm(np.asarray(vertices, np.float64) + t, axis=1).max() + np.linalg.norm(t))
 
 
+# ------------------------------------------------------------------------------------------------ centroids
+CENTROID_SIZES = ((5, 7), (64, 65), (130, 97))  # less than a wave; a full tile and a tile of 64 pixels; four tiles: the frame's butterfly has live lanes
+
+
+def _block_sum(s):
+    """s (..., 256, k), one row a thread -> (..., k), what thread 0 holds: in every wave the butterfly s = s + s[lane ^ off], off = 32 .. 1, then the four waves
+    left to right.  numpy adds element-wise and never contracts."""
+    s = s.reshape(s.shape[:-2] + (4, 64, s.shape[-1]))
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        s = s + s[..., lanes ^ off, :]
+    w = s[..., 0, :]
+    return ((w[..., 0, :] + w[..., 1, :]) + w[..., 2, :]) + w[..., 3, :]
+
+
+def centroids_ordered(depth, masks, K_inv):
+    """``hive_fg_centroids`` in the order include/hive_mi355x.h states, numpy float64: tiles of 4096 pixels, thread t of a tile adds its 16 pixels
+    tile + j * 256 + t with j ascending, the block sum, then the tiles likewise (thread k takes tiles k, k + 256, ..), one division.  Returns (centroids float64
+    (n, 3), counts int64 (n,)); ``np.sum`` over the same terms as the second pair, for the test that the order matters."""
+    depth, K_inv = np.asarray(depth, np.float32), np.asarray(K_inv, np.float64).reshape(3, 3)
+    n, h, w = depth.shape
+    tiles = -(-h * w // 4096)
+    i = np.arange(tiles * 4096)
+    pu, pv = (i % w).astype(np.float64), (i // w).astype(np.float64)
+    rays = [(K_inv[r, 0] * pu + K_inv[r, 1] * pv) + K_inv[r, 2] for r in range(3)]
+    out, counts, plain = np.zeros((n, 3)), np.zeros(n, np.int64), np.zeros((n, 3))
+    for f in range(n):
+        z = np.zeros(tiles * 4096)
+        z[:h * w] = depth[f].reshape(-1).astype(np.float64)
+        valid = np.zeros(tiles * 4096, bool)
+        valid[:h * w] = (np.asarray(masks[f]).reshape(-1) != 0) & (depth[f].reshape(-1) > 0)
+        terms = np.stack([np.where(valid, z * ray, 0.0) for ray in rays] + [valid.astype(np.float64)], axis=1).reshape(tiles, 16, 256, 4)
+        s = np.zeros((tiles, 256, 4))
+        for j in range(16):
+            s = s + terms[:, j]
+        partial = _block_sum(s)  # (tiles, 4)
+        s = np.zeros((256, 4))
+        for t in range(tiles):
+            s[t % 256] = s[t % 256] + partial[t]
+        total = _block_sum(s)
+        counts[f] = int(total[3])
+        if total[3] > 0:
+            out[f] = total[:3] / total[3]
+            plain[f] = np.sum(terms.reshape(-1, 4)[:, :3], axis=0) / total[3]
+    return out, counts, plain
+
+
+def centroid_order_case(size, seed=4):
+    """A batch of three H x W frames whose depths are drawn over 2^-6 .. 2^6, so that the order of the additions shows in the last bits; 70 % of the pixels
+    masked in, some without depth, the middle frame's mask empty.  Returns (depth float32, masks uint8, K float64)."""
+    h, w = size
+    rng = np.random.default_rng(seed + 1000 * h + w)
+    depth = (2.0 ** rng.uniform(-6.0, 6.0, (3, h, w))).astype(np.float32)
+    depth[rng.random((3, h, w)) < 0.05] = 0.0
+    masks = (rng.random((3, h, w)) < 0.7).astype(np.uint8) * rng.integers(1, 4, (3, h, w), dtype=np.uint8)
+    masks[1] = 0
+    return depth, masks, np.array([[525.0, 0.0, 0.5 * w - 0.5], [0.0, 520.0, 0.5 * h - 0.5], [0.0, 0.0, 1.0]])
+
+
 # ------------------------------------------------------------------------------------------------ chunks
 def chunks_of(counts, min_chunk_size=3):
     """Runs of consecutive frames with points, at least ``min_chunk_size`` long, as lists of frame indices (the form the reference keeps them in)."""

@@ -90,3 +90,14 @@ def test_restated_run_float32_parameters_bound_the_float64_run():
     # frames of no chunk move too: the weight decay acts on every parameter
     outside = [20, 21, 22, 23, 24, 25, 45]
     assert np.all(r64[outside] != traj.astype(np.float64)[outside])
+
+
+@pytest.mark.parametrize("size", F.CENTROID_SIZES)
+def test_centroid_order_shows_on_the_order_cases(size):
+    """On exactly the inputs of tests/test_fts_gpu.py::test_centroids_in_the_stated_order_bit_for_bit the stated order and ``np.sum`` differ in at least one
+    component: that test would see another order."""
+    depth, masks, K = F.centroid_order_case(size)
+    stated, counts, plain = F.centroids_ordered(depth, masks, np.linalg.inv(K))
+    assert counts[0] > 0 and counts[1] == 0 and counts[2] > 0 and not stated[1].any()
+    assert (stated.view(np.uint64) != plain.view(np.uint64)).any()
+    assert np.allclose(stated, plain, rtol=1e-12, atol=0.0)

@@ -87,6 +87,20 @@ def test_centroids_at_vga_across_upload_chunks(gpu_ctx):
     assert pose_optimisation.find_chunks(counts) == [(0, 3)]
 
 
+@pytest.mark.parametrize("size", F.CENTROID_SIZES)
+def test_centroids_in_the_stated_order_bit_for_bit(gpu_ctx, size):
+    """hive_fg_centroids == the order include/hive_mi355x.h states, restated in numpy float64 (fts_restatement.centroids_ordered), bit for bit: less than one
+    wave, a full tile with a tile of 64 pixels, four tiles; a batch of three whose middle mask is empty; depths over 2^-6 .. 2^6, where
+    tests/test_fts_cpu.py shows that another order gives other bits."""
+    import torch
+    from hive_amd import geometric, pose_optimisation
+    depth, masks, K = F.centroid_order_case(size)
+    want, want_counts, _ = F.centroids_ordered(depth, masks, geometric._kinv(K))
+    got, counts = pose_optimisation.centroids(torch.from_numpy(depth).cuda(), torch.from_numpy(masks).cuda(), K, ctx=gpu_ctx)
+    assert np.array_equal(counts, want_counts) and counts[1] == 0
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (size, got - want)
+
+
 # ------------------------------------------------------------------------------------------------ loss and gradient
 def _case():
     traj, centroids, counts = F.jittery_case()

@@ -242,6 +242,31 @@ def test_more_rows_than_one_step_of_a_workgroup():
     _check(_run([(pi, pj, (5, 6))]), 0, RR.ransac(pi, pj, pair_key=(5, 6)), 1100)
 
 
+@pytest.mark.parametrize("q_first,t_first,n", ((0, 5, 5), (5, 0, 5), (2, 3, 3)))
+def test_pair_list_and_picture_runs_share_one_matcher(q_first, t_first, n):
+    """``match_pairs`` with the pair list [(q_first + p, t_first + p)] and ``score_pairs`` (hive_mifd) on the same triple give the same 2-NN table, byte for
+    byte, over the rows a pair has: capacity 130 (two full tiles of 64 and a tail of 2), pictures with 0, 1, 2, 65 and 130 keypoints on either side.  The
+    triple is filled by hand; rows past a picture's count hold junk that must not be read."""
+    import torch
+    from hive_amd.features import SIFT, match_pairs, score_pairs
+    cap, held = 130, [0, 1, 2, 65, 130, 130, 65, 2, 1, 0]
+    rng = np.random.default_rng(17)
+    desc = torch.from_numpy(rng.integers(0, 256, (10, cap, 128), dtype=np.uint8)).cuda()
+    kps = torch.from_numpy(rng.uniform(0, 7, (10, cap, 6)).astype(np.float32)).cuda()
+    counts = torch.from_numpy(np.repeat(np.array(held, np.int32)[:, None], 3, axis=1)).cuda()
+    feats = (kps, desc, counts)
+    pairs = [(q_first + p, t_first + p) for p in range(n)]
+    _, _, idx_a, dist_a = match_pairs(feats, pairs, torch.ones((10, 8, 8), dtype=torch.float32, device="cuda"), return_table=True)
+    sift = _once("sift130", lambda: SIFT(capacity=cap))
+    _, _, idx_b, dist_b = score_pairs(sift, feats, q_first, t_first, n, sift._context(kps.device))
+    for p, (i, j) in enumerate(pairs):
+        Q, T = held[i], held[j]
+        ia, da = idx_a[p, :Q].cpu().numpy(), dist_a[p, :Q].cpu().numpy()
+        assert _bits(ia) == _bits(idx_b[p, :Q].cpu().numpy()) and _bits(da) == _bits(dist_b[p, :Q].cpu().numpy()), (i, j)
+        assert ((ia[:, 0] >= 0) == (T >= 1)).all() and ((ia[:, 1] >= 0) == (T >= 2)).all() and (ia < max(T, 1)).all()
+        assert (np.isinf(da) == (ia < 0)).all() and (da[:, 0] <= da[:, 1]).all()
+
+
 def test_more_pairs_than_one_step_of_the_offsets_scan():
     """300 pairs of 12 to 20 correspondences; those with fewer than min_features = 14 of them, or of inliers, are dropped: the scan over the pairs in steps of 256."""
     import torch

@@ -56,14 +56,9 @@ def test_frame_maps_match_the_restatement_bit_for_bit(gpu_ctx, size, levels):
 def icp_scenes(oracle_lib):
     """(H, W) -> the corner scene at that size: K, an oracle volume with the first orbit frame, the restated model maps at its pose, the live maps of the
     second orbit frame."""
-    out, orbit = {}, tc.corner_orbit(12)
+    out = {}
     for H, W, voxels in ((24, 32, 32), (47, 63, 64), (48, 64, 64)):
-        K = tc.intrinsics(H, W)
-        vol = tc.fuse_oracle(oracle_lib, orbit[:1], K, H, W, voxels)
-        _, model_v, model_n, _ = tr.raycast_oracle(vol, K, orbit[0], (H, W))
-        depth = tc.room_depth(orbit[1], K, H, W)[0]
-        _, Vs, Ns, _ = tr.frame_maps(depth, K, 1)
-        out[(H, W)] = dict(K=K, vol=vol, voxels=voxels, model_v=model_v, model_n=model_n, live_v=Vs[0], live_n=Ns[0], depth=depth, orbit=orbit)
+        out[(H, W)] = tr.icp_scene(oracle_lib, H, W, voxels)
     return out
 
 

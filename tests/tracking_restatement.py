@@ -4,6 +4,7 @@ hive_amd/tracking.py restated on the host over an oracle volume and the ray-cast
 import numpy as np
 
 import raycast_restatement as rc
+import tracking_cases as tc
 
 f32 = np.float32
 HALF_EVEN, HALF_AWAY = 0, 1
@@ -218,3 +219,13 @@ def track_and_fuse(oracle, color_frames, depth_frames, K, vol_bnds, voxel_size, 
         results.append(res)
         poses.append(pose.copy())
     return vol, np.stack(poses), results
+
+
+def icp_scene(oracle, H, W, voxels):
+    """The corner scene at H x W: K, an oracle volume with the first orbit frame, the restated model maps at its pose, the live maps of the second orbit frame."""
+    orbit, K = tc.corner_orbit(12), tc.intrinsics(H, W)
+    vol = tc.fuse_oracle(oracle, orbit[:1], K, H, W, voxels)
+    _, model_v, model_n, _ = raycast_oracle(vol, K, orbit[0], (H, W))
+    depth = tc.room_depth(orbit[1], K, H, W)[0]
+    _, Vs, Ns, _ = frame_maps(depth, K, 1)
+    return dict(K=K, vol=vol, voxels=voxels, model_v=model_v, model_n=model_n, live_v=Vs[0], live_n=Ns[0], depth=depth, orbit=orbit)
