@@ -18,6 +18,7 @@
 
 #include "hive_internal.hpp"
 #include "knn_core.hpp"
+#include "ransac_core.hpp"
 
 namespace {
 
@@ -76,36 +77,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_filter_kernel(const float *__
     if (t == 0) pair_counts[2 * p] = (int)passed, pair_counts[2 * p + 1] = (int)kept;
 }
 
-// ---- the homography RANSAC: float64, one rounding per operation ----
-__device__ __forceinline__ unsigned rs_mix(unsigned x) {  // lowbias32
-    x ^= x >> 16, x *= 0x7feb352du;
-    x ^= x >> 15, x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ unsigned rs_base(unsigned seed, const int32_t *__restrict__ key) {
-    return rs_mix(rs_mix(rs_mix(seed) ^ (unsigned)key[0]) ^ (unsigned)key[1]);
-}
-
-// four distinct indices below M >= 4, in the order drawn: draw k takes the mulhi(x_k, M - k)-th index not yet chosen, in ascending order
-__device__ __forceinline__ void rs_draw(unsigned base, unsigned t, unsigned M, int &d0, int &d1, int &d2, int &d3) {
-    const unsigned h = rs_mix(base ^ t);
-    const unsigned a = __umulhi(rs_mix(h), M);
-    unsigned b = __umulhi(rs_mix(h ^ 1u), M - 1u);
-    b += b >= a ? 1u : 0u;
-    const unsigned s0 = min(a, b), s1 = max(a, b);
-    unsigned c = __umulhi(rs_mix(h ^ 2u), M - 2u);
-    c += c >= s0 ? 1u : 0u;
-    c += c >= s1 ? 1u : 0u;
-    const unsigned u0 = min(s0, c), u1 = min(max(s0, c), s1), u2 = max(s1, c);
-    unsigned d = __umulhi(rs_mix(h ^ 3u), M - 3u);
-    d += d >= u0 ? 1u : 0u;
-    d += d >= u1 ? 1u : 0u;
-    d += d >= u2 ? 1u : 0u;
-    d0 = (int)a, d1 = (int)b, d2 = (int)c, d3 = (int)d;
-}
-
+// ---- the homography RANSAC: float64, one rounding per operation (the hash, the draw, the count and the lane sum: ransac_core.hpp) ----
 struct RsPoint {
     double X, Y, U, V;
 };
@@ -181,22 +153,6 @@ __device__ __forceinline__ bool rs_inlier(const double h[8], const RsPoint &p, d
     const double du = pu / w - p.U, dv = pv / w - p.V;
     const double e2 = du * du + dv * dv;
     return w > 0.0 && e2 <= thr2;
-}
-
-// a pair's number of correspondences; -1 for a count outside 0 .. stride: such a pair is refused (result -2), never cut
-__device__ __forceinline__ int rs_count(const int32_t *__restrict__ counts, int count_stride, int p, int stride) {
-    const int c = counts[(size_t)p * count_stride];
-    return c < 0 || c > stride ? -1 : c;
-}
-
-// total = 0 + lane 0 + lane 1 + ... + lane 63, on every lane
-__device__ __forceinline__ double rs_lane_sum(double mine, double *lds) {
-    __syncthreads();
-    lds[threadIdx.x] = mine;
-    __syncthreads();
-    double acc = 0.0;
-    for (int l = 0; l < 64; ++l) acc = acc + lds[l];
-    return acc;
 }
 
 // grid (P), one wave: centroid, mean distance and scale of both sides over all M points

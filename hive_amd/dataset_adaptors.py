@@ -10,6 +10,7 @@ import enum
 import logging
 import os
 import shutil
+import warnings
 from os.path import join as pjoin
 
 import numpy as np
@@ -129,9 +130,14 @@ class TUMAdaptor(DatasetAdaptor):
         """Write the HIVE-format folder and return it as a ``HiveDataset`` (dataset_adaptors.py:176-266).
         Instance masks need detectron2 (out of scope): empty masks are written, i.e. a static scene.
         ``estimate_depth=True`` replaces the sensor depth by DPT-Hybrid estimates (needs the weights file).  ``png_encoder`` ("host" | "gpu") goes to
-        ``estimate_depth_dpt`` and ``inpaint_frame_data``; the frames copied here are always written by the host encoder."""
-        if estimate_pose:
-            raise NotImplementedError("pose estimation runs COLMAP, which is outside the dense-compute scope")
+        ``estimate_depth_dpt`` and ``inpaint_frame_data``; the frames copied here are always written by the host encoder.
+        ``estimate_pose=True`` (with the sensor depth): the reference runs COLMAP, which is absent; here the folder is written as usual and
+        ``registration.estimate_trajectory`` (SIFT matches back-projected with the depth, a rigid RANSAC per hierarchical frame pair, the transforms chained) on
+        it replaces the ground-truth file's trajectory, anchored at that file's first pose; frames that no chain of pairs reached are warned about.  Together
+        with ``estimate_depth=True`` it raises: per-frame depth scales would have to be applied before fusion."""
+        if estimate_pose and estimate_depth:
+            raise NotImplementedError("pose estimation on estimated depth: the per-frame depth scales of the registration would have to be applied before fusion; "
+                                      "COLMAP, which the reference runs here, is outside the dense-compute scope")
         if static_camera:
             raise NotImplementedError("the static-camera override is outside the dense-compute scope")
         _check_inpainting_mode(inpainting_mode)
@@ -155,6 +161,13 @@ class TUMAdaptor(DatasetAdaptor):
             estimate_depth_dpt(ImageFolderDataset(pjoin(out, "rgb")), pjoin(out, "depth"), png_encoder=png_encoder)
         np.savetxt(pjoin(out, HiveDataset.camera_matrix_filename), self.intrinsic_matrix)
         Trajectory(self.camera_trajectory.values[:self.num_frames]).save(pjoin(out, HiveDataset.camera_trajectory_filename))
+        if estimate_pose:
+            from hive_amd import registration
+            logging.info("Estimating the camera trajectory from the frames...")
+            estimate = registration.estimate_trajectory(HiveDataset(out))
+            if estimate.lost:
+                warnings.warn(f"pose estimation: no chain of frame pairs reached the frames {estimate.lost}; each copies the pose of a neighbour")
+            estimate.trajectory.save(pjoin(out, HiveDataset.camera_trajectory_filename))
         with timed_block("Inpainted the frame data in", profiling, ('timing', 'load_dataset', 'inpainting')):  # (dataset_adaptors.py:261-262)
             self._inpaint_frame_data(mode=inpainting_mode, png_encoder=png_encoder)
         return HiveDataset(out)

@@ -6,7 +6,9 @@ cv2.SIFT.create()'s parameters as recalled from OpenCV 4.x; cv2 cannot be run be
 reference matches with FLANN (an approximate randomised KD-tree search); the matcher here returns the exact nearest neighbours and is not pinned against FLANN.
 
 ``match_pairs``, ``ransac_homography`` / ``find_homography`` and ``compact_pairs`` (csrc/pairs.hip) are the stages of the reference's ``FeatureExtractor`` behind the
-detector (hive/pose_optimisation.py:437-578); the homography RANSAC is a stated rule of its own, not pinned against cv2's randomised USAC_MAGSAC."""
+detector (hive/pose_optimisation.py:437-578); the homography RANSAC is a stated rule of its own, not pinned against cv2's randomised USAC_MAGSAC.
+``ransac_rigid`` / ``estimate_rigid_transform`` (csrc/register.hip) fit a rigid or similarity transform to the same rows back-projected with their depth: the
+start of ``hive_amd.registration``, where the reference calls COLMAP or BundleFusion (absent; not pinned against either)."""
 import ctypes
 import warnings
 
@@ -377,6 +379,76 @@ def find_homography(points_i, points_j, threshold=3.0, trials=2000, seed=0, pair
         out = (H[0].cpu().numpy() if found else None, mask[0].cpu().numpy())
     else:
         out = (H[0] if found else None, mask[0])
+    return out + (stats,) if return_stats else out
+
+
+def ransac_rigid(rows, counts, keys, camera_matrix=None, threshold=0.05, trials=2000, seed=0, min_count=0, with_scale=False, ctx=None):
+    """The rigid (``with_scale``: similarity) RANSAC of include/hive_mi355x.h (rules ``points`` .. ``outputs`` above ``hive_ransac_rigid``; csrc/register.hip) for
+    P pairs at once.  ``rows``: float32 device tensor (P, stride, W >= 6).  With ``camera_matrix`` (3 x 3, fx, fy, cx, cy are read) a row is ``match_pairs``'s
+    x_i, y_i, x_j, y_j, depth_i, depth_j and both sides are back-projected; with ``camera_matrix=None`` a row is X_i Y_i Z_i X_j Y_j Z_j.  ``counts``: int32
+    device tensor (P,), or a column such as ``match_pairs``'s ``counts[:, 1]``; ``keys``: (P, 2) the frame pairs that seed the draws.  Returns device tensors
+    ``(T float64 (P, 4, 4), scale float64 (P,), rms float64 (P,), mask uint8 (P, stride), result int32 (P, 3))``: T maps camera-i points onto camera-j points
+    and holds scale * R and t; rms is over the final inliers; per pair the winning trial (-1 without a model, -2 for a count outside 0 .. stride), the winner's
+    count and the final count.  A pair with fewer than ``max(min_count, 3)`` correspondences has no model: T, scale and rms are NaN and the mask is 0.
+    ``threshold`` is in the depth's unit; its default 0.05 is a parameter default (5 cm for depth in metres), not a measured quantity.  A function of its inputs
+    alone: all ``trials`` trials run.  Not pinned against cv2's estimateAffine3D, Open3D, BundleFusion or COLMAP (all absent).  Nothing synchronises."""
+    import torch
+    if rows.dtype != torch.float32 or rows.dim() != 3 or int(rows.shape[2]) < 6 or not rows.is_contiguous():
+        raise ValueError(f"rows: contiguous float32 (P, stride, >= 6), got {rows.dtype} {tuple(rows.shape)}")
+    dev, p, stride, words = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(rows.shape[2])
+    if counts.dtype != torch.int32 or counts.dim() != 1 or int(counts.shape[0]) != p:
+        raise ValueError(f"counts: int32 (P,) with P = {p}, got {counts.dtype} {tuple(counts.shape)}")
+    if not is_torch(keys):
+        keys = torch.from_numpy(np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1, 2).astype(np.int32))).to(dev)
+    if keys.dtype != torch.int32 or tuple(keys.shape) != (p, 2):
+        raise ValueError(f"keys: int32 (P, 2) with P = {p}, got {keys.dtype} {tuple(keys.shape)}")
+    keys = keys.contiguous()
+    camera = None
+    if camera_matrix is not None:
+        K = np.asarray(camera_matrix.detach().cpu().numpy() if is_torch(camera_matrix) else camera_matrix, dtype=np.float64)
+        if K.shape != (3, 3):
+            raise ValueError(f"camera_matrix: (3, 3), got {K.shape}")
+        camera = (ctypes.c_double * 4)(K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    T = torch.empty((p, 4, 4), dtype=torch.float64, device=dev)
+    scale = torch.empty(p, dtype=torch.float64, device=dev)
+    rms = torch.empty(p, dtype=torch.float64, device=dev)
+    mask = torch.empty((p, max(stride, 1)), dtype=torch.uint8, device=dev)[:, :stride]
+    result = torch.empty((p, 3), dtype=torch.int32, device=dev)
+    if p and stride:
+        ctx = _lib.context_for(ctx, dev)
+        ctx.check(ctx.lib.hive_ransac_rigid(ctx.handle, ptr(rows), words, ptr(counts), int(counts.stride(0)), ptr(keys), p, stride, camera, float(threshold), int(trials),
+                                            int(seed) & 0xFFFFFFFF, int(min_count), int(bool(with_scale)), ptr(T), ptr(scale), ptr(rms), ptr(mask), ptr(result)))
+    elif p:
+        T.fill_(NAN), scale.fill_(NAN), rms.fill_(NAN)
+        result.copy_(torch.tensor([-1, 0, 0], dtype=torch.int32, device=dev))
+    return T, scale, rms, mask, result
+
+
+def estimate_rigid_transform(points_i, points_j, threshold=0.05, trials=2000, seed=0, pair_key=(0, 0), with_scale=False, return_stats=False, ctx=None):
+    """``ransac_rigid`` for one pair of (M, 3) point sets, numpy arrays or device tensors -> ``(T, mask)``: T float64 (4, 4) mapping ``points_i`` onto
+    ``points_j`` (scale * R and t; None without a model: fewer than three points, or every sample degenerate) and the inlier mask uint8 (M,), of the kind
+    ``points_i`` is.  ``threshold`` is in the points' unit; 0.05 is a parameter default (5 cm for metres), not a measured quantity.  The draws depend on ``seed``
+    and ``pair_key`` alone, so the result is a function of the arguments.  ``return_stats``: also ``(winning trial, the winner's count, the final count, scale,
+    rms)``.  Not pinned against cv2's estimateAffine3D or Open3D (absent)."""
+    import torch
+    as_numpy = not is_torch(points_i)
+    dev = device_of(points_i, points_j)
+    host = lambda a: a if a.ndim == 2 else a.reshape(-1, 3)  # an empty list is (0, 3)
+    device = lambda a, name: on_device(a if is_torch(a) else host(np.asarray(a, dtype=np.float32)), dev, dtype=torch.float32,
+                                       check=lambda _, shape: len(shape) == 2 and shape[1] == 3, error=lambda a: f"{name}: (M, 3) points, got {tuple(a.shape)}")
+    a, b = device(points_i, "points_i"), device(points_j, "points_j")
+    if a.shape != b.shape:
+        raise ValueError(f"points_i {tuple(a.shape)} and points_j {tuple(b.shape)} differ")
+    m = int(a.shape[0])
+    rows = torch.cat([a, b], dim=1).reshape(1, m, 6).contiguous()
+    T, scale, rms, mask, result = ransac_rigid(rows, torch.tensor([m], dtype=torch.int32, device=dev), [pair_key], None, threshold, trials, seed, 0, with_scale, ctx=ctx)
+    host = torch.cat([result[0].double(), scale, rms]).cpu().numpy()  # the one synchronisation
+    stats = (int(host[0]), int(host[1]), int(host[2]), float(host[3]), float(host[4]))
+    found = stats[0] >= 0
+    if as_numpy:
+        out = (T[0].cpu().numpy() if found else None, mask[0].cpu().numpy())
+    else:
+        out = (T[0] if found else None, mask[0])
     return out + (stats,) if return_stats else out
 
 

@@ -291,13 +291,24 @@ class FeatureExtractor:
     (``cv2.USAC_MAGSAC`` is randomised; the RANSAC here is the rule stated in include/hive_mi355x.h, a function of the inputs, ``seed`` and the frame pair).
     ``ransac_threshold`` and ``ransac_trials`` are cv2.findHomography's defaults.  With ``debug_path``, ``frame_pairs.txt`` and ``feature_set.pth`` are written
     there and the feature set is reused while the pair list stays the same (:367-402); the reference's match pictures (``cv2.drawMatchesKnn``) are NOT written.
-    ``sift``: a ``features.SIFT`` to use (one with ``nfeatures = max_features`` and room for 8192 candidates a frame otherwise)."""
+    ``sift``: a ``features.SIFT`` to use (one with ``nfeatures = max_features`` and room for 8192 candidates a frame otherwise).
+
+    ``model="rigid"``: the inlier mask comes from ``features.ransac_rigid`` (csrc/register.hip) on the same rows, back-projected with the dataset's camera
+    matrix, in the place of the homography, which is exact only for a plane or a pure rotation; ``rigid_threshold`` is in the depth's unit (0.05 is a parameter
+    default, 5 cm for metres, not a measured quantity) and ``with_scale`` fits a similarity.  The compaction and the ``FeatureSet`` are as before, and
+    ``pair_transforms = (T, scale, rms, result)`` holds the relative transforms as host arrays after the run (``registration.chain_pairs`` makes a trajectory
+    and per-frame depth scales of them; the hand-off to the Affine alignment is ``scale_parameters = 1 / depth_scale``).  A cached feature set under
+    ``debug_path`` carries no transforms: ``pair_transforms`` stays None when it is reused."""
 
     UPLOAD_CHUNK_FRAMES = 64
     OWN_SIFT_CAPACITY = 8192
 
     def __init__(self, dataset, frame_pairs, feature_extraction_options=None, debug_path=None, sift=None, ransac_threshold=3.0, ransac_trials=2000, seed=0,
-                 device=None):
+                 device=None, model="homography", rigid_threshold=0.05, with_scale=False):
+        if model not in ("homography", "rigid"):
+            raise ValueError(f"model = {model!r}; 'homography' or 'rigid'")
+        self.model, self.rigid_threshold, self.with_scale = model, float(rigid_threshold), bool(with_scale)
+        self.pair_transforms = None  # after a run with model="rigid": host arrays (T (P, 4, 4), scale (P,), rms (P,), result (P, 3)) of features.ransac_rigid
         self.dataset = dataset
         self.frame_pairs = [(int(i), int(j)) for i, j in frame_pairs]
         self.options = feature_extraction_options or FeatureExtractionOptions()
@@ -375,6 +386,8 @@ class FeatureExtractor:
         if len(pairs) == 0:
             out = FeatureSet(camera_matrix, FeatureData().to(device), FeatureData().to(device))
             self.pair_stats = np.zeros((0, 5), dtype=np.int64)
+            if self.model == "rigid":
+                self.pair_transforms = (np.zeros((0, 4, 4)), np.zeros(0), np.zeros(0), np.zeros((0, 3), dtype=np.int64))
         else:
             logging.info("Extracting matching image feature info...")
             frames = sorted(set(pairs.flatten().tolist()))  # only frames that occur in a pair
@@ -385,10 +398,20 @@ class FeatureExtractor:
                 feats = sift.detect_device(gray, mask)
                 pictures = np.vectorize(picture.get)(pairs)
                 rows, counts = F.match_pairs(feats, pictures, depth, ratio=0.7, min_features=self.min_features)
-                _, inlier_mask, result = F.ransac_homography(rows, counts[:, 1], pairs, self.ransac_threshold, self.ransac_trials, self.seed, min_count=self.min_features)
+                rigid = None
+                if self.model == "rigid":
+                    *rigid, inlier_mask, result = F.ransac_rigid(rows, counts[:, 1], pairs, self.dataset.camera_matrix, self.rigid_threshold, self.ransac_trials, self.seed,
+                                                                 min_count=self.min_features, with_scale=self.with_scale)
+                else:
+                    _, inlier_mask, result = F.ransac_homography(rows, counts[:, 1], pairs, self.ransac_threshold, self.ransac_trials, self.seed, min_count=self.min_features)
                 data, kept, offsets = F.compact_pairs(rows, counts, inlier_mask, result, self.min_features)
                 # the one synchronisation: every count in one copy
-                host = torch.cat([feats[2].flatten().long(), counts.flatten().long(), result.flatten().long(), kept.long(), offsets]).cpu().numpy()
+                host = torch.cat([feats[2].flatten().long(), counts.flatten().long(), result.flatten().long(), kept.long(), offsets])
+                if rigid is None:
+                    host = host.cpu().numpy()
+                else:  # the transforms ride in the same copy: every count is far below 2^53
+                    both = torch.cat([host.double()] + [t.flatten() for t in rigid]).cpu().numpy()
+                    host, rigid = both[:len(host)].astype(np.int64), both[len(host):]
             finally:
                 if self.sift is None:
                     sift.close()
@@ -397,6 +420,8 @@ class FeatureExtractor:
             counts_h, result_h = host[3 * n:3 * n + 2 * p].reshape(p, 2), host[3 * n + 2 * p:3 * n + 5 * p].reshape(p, 3)
             kept_h, total = host[3 * n + 5 * p:3 * n + 6 * p], int(host[-1])
             self.pair_stats = np.concatenate([counts_h, result_h[:, :2], kept_h[:, None]], axis=1)
+            if rigid is not None:
+                self.pair_transforms = (rigid[:16 * p].reshape(p, 4, 4), rigid[16 * p:17 * p], rigid[17 * p:], result_h.copy())
             data = data[:total]
             kept_d = kept.long()
             index_i = torch.repeat_interleave(torch.from_numpy(pairs[:, 0].copy()).to(device), kept_d, output_size=total)

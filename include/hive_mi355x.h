@@ -834,6 +834,46 @@ int hive_ransac_homography(hive_ctx *ctx, const float *d_rows, int row_words, co
 int hive_pairs_compact(hive_ctx *ctx, const float *d_rows, const int32_t *d_pair_counts, const uint8_t *d_mask, const int32_t *d_result, int P, int stride,
                        int min_features, float *d_out, int32_t *d_kept, int64_t *d_offsets);
 
+/* ---- frame registration from 3-D feature matches: a rigid (optionally similarity) RANSAC on the back-projected rows of hive_pairs_match -- csrc/register.hip.
+ * It stands where the reference shells out to COLMAP (estimate_pose) and names BundleFusion; cv2's estimateAffine3D, Open3D's correspondence RANSAC, BundleFusion
+ * and COLMAP are all absent, so the rules below are this project's own and are pinned against none of them.  tests/rigid_restatement.py states the same rules in
+ * numpy.  Float64 with one rounding per operation (no fused multiply-add), sqrt and / correctly rounded; parentheses give the order; `lane sum` and `draw` are
+ * the rules above hive_pairs_match.
+ *   points     with a camera (fx, fy, cx, cy) a row is x_i, y_i, x_j, y_j, depth_i, depth_j (float32, widened): Z = depth, X = ((x - cx) Z) / fx,
+ *              Y = ((y - cy) Z) / fy on either side; p the point of side i, q of side j.  Without a camera (NULL) the first six words of a row are
+ *              X_i Y_i Z_i X_j Y_j Z_j.  M < max(min_count, 3): no model.  A count outside 0 .. stride is refused, never cut (winning trial -2).
+ *   draw       the first three draws (k = 0, 1, 2) of rule `draw`: three distinct indices below M, in the order drawn.
+ *   degenerate per side e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2 = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), a . b = (ax bx + ay by) + az bz:
+ *              the sample is rejected when n . n <= (2^-20 (e1 . e1)) (e2 . e2) on either side (sin^2 of the angle at p0 at most 2^-20: scale-free; two equal
+ *              points give 0 <= 0).
+ *   horn       one solver for the minimal sample and the refit.  Centroids cp, cq; p' = p - cp, q' = q - cq; S[a][b] = sum p'_a q'_b, sp = sum p' . p',
+ *              sq = sum q' . q'.  Minimal sample: cp = ((p0 + p1) + p2) / 3 per component, the sums over k = 0, 1, 2 in the order drawn, each added to 0.0.
+ *              N (symmetric 4 x 4): N00 = (Sxx + Syy) + Szz, N11 = (Sxx - Syy) - Szz, N22 = (Syy - Sxx) - Szz, N33 = (Szz - Sxx) - Syy, N01 = Syz - Szy,
+ *              N02 = Szx - Sxz, N03 = Sxy - Syx, N12 = Sxy + Syx, N13 = Szx + Sxz, N23 = Syz + Szy.  Cyclic Jacobi, V = I, S_w = 7 sweeps (measured: 5 reach
+ *              an off-diagonal norm of 2^-52 of the Frobenius norm on every committed case; two more) over (p, q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a
+ *              rotation is skipped when a_pq is exactly 0; theta = (a_qq - a_pp) / (2 a_pq); t = sign(theta) / (|theta| + sqrt(theta theta + 1)),
+ *              sign(theta) = 1 for theta >= 0; c = 1 / sqrt(t t + 1); s = t c; a_pp = a_pp - t a_pq, a_qq = a_qq + t a_pq, a_pq = 0; for the two other r:
+ *              a_rp = c a_rp - s a_rq and a_rq = s a_rp + c a_rq (both from the old values); for r = 0 .. 3 the same with V[r][p], V[r][q].
+ *              (w, x, y, z) = the column of V at the largest a_kk, the lowest k on a tie; negated when w < 0, or when w == 0 and the first non-zero of x, y, z
+ *              is negative; divided by n = sqrt(((w w + x x) + y y) + z z).  R00 = ((w w + x x) - y y) - z z, R01 = 2 (x y - w z), R02 = 2 (x z + w y),
+ *              R10 = 2 (x y + w z), R11 = ((w w - x x) + y y) - z z, R12 = 2 (y z - w x), R20 = 2 (x z - w y), R21 = 2 (y z + w x),
+ *              R22 = ((w w - x x) - y y) + z z.  scale = sqrt(sq / sp) with with_scale, else 1; A = scale R per entry; t_r = cq_r - ((A_r0 cp_x + A_r1 cp_y) +
+ *              A_r2 cp_z).  No model when sp or sq is 0 or sp, sq, scale or an entry of A or t is not finite.
+ *   inlier     d_r = (((A_r0 p_x + A_r1 p_y) + A_r2 p_z) + t_r) - q_r; an inlier has d . d <= threshold threshold, `threshold` in the depth's unit (a NaN is not
+ *              an inlier).  The score is the integer count.  All `trials` trials run (no early stop).  The winner has the largest count, the lower trial on
+ *              a tie: one 64-bit integer atomic maximum a pair of count << 32 | (0xFFFFFFFF - trial).  All trials rejected: no model.
+ *   refit      once, by `horn` over the winner's n inliers in two passes of lane sums: cp = L(p) / n, cq = L(q) / n; then S, sp, sq as lane sums of the centred
+ *              terms.  Re-scored; the refit's model and mask are kept when it solved and counts at least the winner's, else the winner's.
+ *   outputs    T = [A | t; 0 0 0 1] maps camera-i points onto camera-j points; scale; rms = sqrt(L(d . d over the final inliers) / final count).  Without a
+ *              model T, scale and rms are NaN and the mask is 0.
+ * No floating-point atomic; the same bits on every run, in every batch and at every place in it.  Nothing synchronises. */
+/* P pairs of correspondences as for hive_ransac_homography, row_words >= 6; `camera`: four doubles fx, fy, cx, cy on the HOST, read during the call, or NULL for
+ * the points layout -> d_T f64 [P][16], d_scale f64 [P], d_rms f64 [P], d_mask u8 [P][stride] (0 past the count), d_result i32 [P][3]: the winning trial (-1: no
+ * model, -2: count outside 0 .. stride), the winner's count, the final count. */
+int hive_ransac_rigid(hive_ctx *ctx, const float *d_rows, int row_words, const int32_t *d_counts, int count_stride, const int32_t *d_keys, int P, int stride,
+                      const double *camera, double threshold, int trials, unsigned seed, int min_count, int with_scale, double *d_T, double *d_scale, double *d_rms,
+                      uint8_t *d_mask, int32_t *d_result);
+
 /* ---- glTF 2.0 export: the meshes of a scene packed into the binary buffer of a .glb -- what Pipeline._write_mesh_to_disk (hive/pipeline.py:921-936) hands to
  * trimesh's exporter and Pipeline._compress_with_draco (:938-980) to draco_transcoder -- csrc/gltf.hip.  trimesh, pygltflib and draco_transcoder are absent: the
  * bytes below are stated from the glTF 2.0 specification and KHR_mesh_quantization and are not pinned against trimesh's exporter or against three.js's loader.
