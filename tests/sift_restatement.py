@@ -161,11 +161,19 @@ def _solve3(a):
     return x0, x1, x2
 
 
+def _tally(census, key, n=1):
+    """census[key] += n when a census is kept (the optional ``census`` dicts below count which branches of the rules a picture reaches; the results do not change)."""
+    if census is not None:
+        census[key] = census.get(key, 0) + int(n)
+
+
 CAND_DTYPE = np.dtype([("x", F), ("y", F), ("size", F), ("response", F), ("octave", np.int32), ("layer", np.int32), ("r", np.int32), ("c", np.int32)])
 
 
-def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10, sigma=1.6):
-    """The refined candidates of every octave (a CAND_DTYPE array, in octave, layer, row, column order of their starting extremum)."""
+def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10, sigma=1.6, census=None):
+    """The refined candidates of every octave (a CAND_DTYPE array, in octave, layer, row, column order of their starting extremum).  ``census`` counts:
+    ``extrema`` (starting extrema), ``moves_0`` .. ``moves_4`` (refinements that ended after so many moves), ``layer_moves`` (moves that changed the layer) and
+    the ways out ``out_zero_pivot``, ``out_overrun``, ``out_left``, ``out_guard``, ``out_contrast``, ``out_edge``, ``out_mask``."""
     L = n_octave_layers
     ct, et, sg = F(contrast_threshold), F(edge_threshold), F(sigma)
     threshold = F(np.floor(0.5 * float(ct) / L * 255.0))
@@ -192,7 +200,8 @@ def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_t
                     layer, r, c = layer0, int(r0) + BORDER, int(c0) + BORDER
                     Dv = lambda l, y, x: dog[l, y, x]
                     ok = False
-                    for _ in range(STEPS):
+                    _tally(census, "extrema")
+                    for moves in range(STEPS):
                         v2 = Dv(layer, r, c) * F(2.0)
                         dxx = (Dv(layer, r, c + 1) + Dv(layer, r, c - 1) - v2) * s
                         dyy = (Dv(layer, r + 1, c) + Dv(layer, r - 1, c) - v2) * s
@@ -204,17 +213,24 @@ def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_t
                                      [dxy, dyy, dys, (Dv(layer, r + 1, c) - Dv(layer, r - 1, c)) * ds],
                                      [dxs, dys, dss, (Dv(layer + 1, r, c) - Dv(layer - 1, r, c)) * ds]])
                         if X is None:
+                            _tally(census, "out_zero_pivot")
                             break
                         xc, xr, xi = -X[0], -X[1], -X[2]
                         if abs(xi) < 0.5 and abs(xr) < 0.5 and abs(xc) < 0.5:
                             ok = True
+                            _tally(census, f"moves_{moves}")
                             break
                         big = F(536870912.0)
                         if not (abs(xi) <= big and abs(xr) <= big and abs(xc) <= big):
+                            _tally(census, "out_guard")
                             break
                         c, r, layer = c + int(np.rint(xc)), r + int(np.rint(xr)), layer + int(np.rint(xi))
+                        _tally(census, "layer_moves", int(np.rint(xi)) != 0)
                         if layer < 1 or layer > L or c < BORDER or c >= w - BORDER or r < BORDER or r >= h - BORDER:
+                            _tally(census, "out_left")
                             break
+                    else:
+                        _tally(census, "out_overrun")
                     if not ok:
                         continue
                     d0 = (Dv(layer, r, c + 1) - Dv(layer, r, c - 1)) * ds
@@ -223,6 +239,7 @@ def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_t
                     tdot = d0 * xc + d1 * xr + d2 * xi
                     contr = Dv(layer, r, c) * s + tdot * F(0.5)
                     if abs(contr) * F(L) < ct:
+                        _tally(census, "out_contrast")
                         continue
                     v2 = Dv(layer, r, c) * F(2.0)
                     dxx = (Dv(layer, r, c + 1) + Dv(layer, r, c - 1) - v2) * s
@@ -230,6 +247,7 @@ def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_t
                     dxy = (Dv(layer, r + 1, c + 1) - Dv(layer, r + 1, c - 1) - Dv(layer, r - 1, c + 1) + Dv(layer, r - 1, c - 1)) * cs
                     tr, det = dxx + dyy, dxx * dyy - dxy * dxy
                     if det <= 0 or tr * tr * et >= (et + F(1.0)) * (et + F(1.0)) * det:
+                        _tally(census, "out_edge")
                         continue
                     scale = F(1 << o)
                     x, y = (F(c) + xc) * scale, (F(r) + xr) * scale
@@ -240,6 +258,7 @@ def candidates(pyr, mask=None, picture_shape=None, n_octave_layers=3, contrast_t
                         mx = min(max(int(x * F(0.5) + F(0.5)), 0), W - 1)
                         my = min(max(int(y * F(0.5) + F(0.5)), 0), H - 1)
                         if mask[my, mx] == 0:
+                            _tally(census, "out_mask")
                             continue
                     out.append((x, y, size, abs(contr), packed, layer, r, c))
     return np.array(out, dtype=CAND_DTYPE)
@@ -282,8 +301,9 @@ def _window(radius):
     return p, p // length - radius, p % length - radius
 
 
-def orientations(pyr, cand, n_octave_layers=3):
-    """float32 (K, 6): the keypoints of every candidate, unsorted."""
+def orientations(pyr, cand, n_octave_layers=3, census=None):
+    """float32 (K, 6): the keypoints of every candidate, unsorted.  ``census`` counts ``ori_multi_peak`` (candidates with more than one peak), ``ori_window_cut``
+    (candidates whose window loses samples to the layer's border) and ``ori_angle_folded`` (angles within FLT_EPSILON of 360 set to 0)."""
     out = []
     with np.errstate(all="ignore"):
         for k in cand:
@@ -297,6 +317,7 @@ def orientations(pyr, cand, n_octave_layers=3):
             p, i, j = _window(radius)
             y, x = r + i, c + j
             ok = (y > 0) & (y < h - 1) & (x > 0) & (x < w - 1)
+            _tally(census, "ori_window_cut", not ok.all())
             p, i, j, y, x = p[ok], i[ok], j[ok], y[ok], x[ok]
             dx = img[y, x + 1] - img[y, x - 1]
             dy = img[y - 1, x] - img[y + 1, x]
@@ -309,6 +330,7 @@ def orientations(pyr, cand, n_octave_layers=3):
             t = _lane_sum(wgt * mag, b, ORI_BINS, p)
             hist = (np.roll(t, 2) + np.roll(t, -2)) * F(1.0 / 16.0) + (np.roll(t, 1) + np.roll(t, -1)) * F(4.0 / 16.0) + t * F(6.0 / 16.0)
             thr = hist.max() * F(0.8)
+            peaks = 0
             for jb in range(ORI_BINS):
                 l, r2 = (jb - 1) % ORI_BINS, (jb + 1) % ORI_BINS
                 if not (hist[jb] > hist[l] and hist[jb] > hist[r2] and hist[jb] >= thr):
@@ -318,8 +340,11 @@ def orientations(pyr, cand, n_octave_layers=3):
                 angle = F(360.0) - F(360.0 / ORI_BINS) * b_
                 if abs(angle - F(360.0)) < FLT_EPSILON:
                     angle = F(0.0)
+                    _tally(census, "ori_angle_folded")
+                peaks += 1
                 packed = int(k["octave"])
                 out.append((k["x"] * F(0.5), k["y"] * F(0.5), k["size"] * F(0.5), angle, k["response"], F((packed & ~255) | ((packed - 1) & 255))))
+            _tally(census, "ori_multi_peak", peaks > 1)
     return np.array(out, dtype=F).reshape(-1, 6)
 
 
@@ -332,8 +357,9 @@ def sort_unique(kps):
     return kps[keep]
 
 
-def descriptors(pyr, kps):
-    """uint8 (K, 128)."""
+def descriptors(pyr, kps, census=None):
+    """uint8 (K, 128).  ``census`` counts ``desc_window_cut`` (keypoints whose window loses samples of its 4 x 4 cells to the layer's border),
+    ``desc_radius_clamp`` (radius cut to the layer's diagonal), ``desc_clipped`` (values cut at 0.2 of the norm) and ``desc_saturated`` (bytes at 255)."""
     out = np.zeros((len(kps), D * D * NB), dtype=np.uint8)
     with np.errstate(all="ignore"):
         for n, kp in enumerate(kps):
@@ -351,6 +377,7 @@ def descriptors(pyr, kps):
             cos_t, sin_t = sift_sincos_deg(ori)
             bins_per_deg, exp_scale, hist_width = F(NB / 360.0), F(-1.0) / (F(D * D) * F(0.5)), F(3.0) * scl
             radius = int(np.rint(hist_width * F(1.4142135623730951) * F(D + 1) * F(0.5)))
+            _tally(census, "desc_radius_clamp", radius > int(np.sqrt(float(h) * h + float(w) * w)))
             radius = min(radius, int(np.sqrt(float(h) * h + float(w) * w)))
             cos_t, sin_t = cos_t / hist_width, sin_t / hist_width
             p, i, j = _window(radius)
@@ -358,7 +385,9 @@ def descriptors(pyr, kps):
             c_rot, r_rot = fj * cos_t - fi * sin_t, fj * sin_t + fi * cos_t
             rbin, cbin = r_rot + F(D // 2) - F(0.5), c_rot + F(D // 2) - F(0.5)
             r, c = pty + i, ptx + j
-            ok = (rbin > -1) & (rbin < D) & (cbin > -1) & (cbin < D) & (r > 0) & (r < h - 1) & (c > 0) & (c < w - 1)
+            cells = (rbin > -1) & (rbin < D) & (cbin > -1) & (cbin < D)
+            ok = cells & (r > 0) & (r < h - 1) & (c > 0) & (c < w - 1)
+            _tally(census, "desc_window_cut", (cells & ~ok).any())
             p, c_rot, r_rot, rbin, cbin, r, c = p[ok], c_rot[ok], r_rot[ok], rbin[ok], cbin[ok], r[ok], c[ok]
             dx = img[r, c + 1] - img[r, c - 1]
             dy = img[r - 1, c] - img[r + 1, c]
@@ -396,26 +425,30 @@ def descriptors(pyr, kps):
             for v in dst:
                 nrm2 = nrm2 + v * v
             thr = np.sqrt(nrm2) * F(0.2)
+            _tally(census, "desc_clipped", (dst > thr).sum())
             dst = np.minimum(dst, thr)
             nrm2 = F(0.0)
             for v in dst:
                 nrm2 = nrm2 + v * v
             s = F(512.0) / max(np.sqrt(nrm2), FLT_EPSILON)
             out[n] = np.clip(np.rint(dst * s), 0, 255).astype(np.uint8)
+            _tally(census, "desc_saturated", (out[n] == 255).sum())
     return out
 
 
-def detect_and_compute(gray, mask=None, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6, stages=False):
-    """(keypoints float32 (K, 6), descriptors uint8 (K, 128)); with ``stages`` a dict that also holds the pyramid and the candidates."""
+def detect_and_compute(gray, mask=None, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6, stages=False, census=None):
+    """(keypoints float32 (K, 6), descriptors uint8 (K, 128)); with ``stages`` a dict that also holds the pyramid, the candidates and the number of keypoints
+    before the duplicates left (``raw``).  ``census``: a dict that receives the branch counts of ``candidates``, ``orientations`` and ``descriptors``."""
     gray = np.asarray(gray)
     assert gray.dtype == np.uint8 and gray.ndim == 2
     pyr = pyramid(gray, nOctaveLayers, sigma)
-    cand = candidates(pyr, mask, gray.shape, nOctaveLayers, contrastThreshold, edgeThreshold, sigma)
+    cand = candidates(pyr, mask, gray.shape, nOctaveLayers, contrastThreshold, edgeThreshold, sigma, census)
     kept = retain_best(cand, nfeatures)
-    kps = sort_unique(orientations(pyr, kept, nOctaveLayers))
-    desc = descriptors(pyr, kps)
+    raw = orientations(pyr, kept, nOctaveLayers, census)
+    kps = sort_unique(raw)
+    desc = descriptors(pyr, kps, census)
     if stages:
-        return dict(pyramid=pyr, candidates=cand, keypoints=kps, descriptors=desc)
+        return dict(pyramid=pyr, candidates=cand, keypoints=kps, descriptors=desc, raw=len(raw))
     return kps, desc
 
 

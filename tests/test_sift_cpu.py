@@ -1,6 +1,14 @@
 """The numpy restatement of SIFT, the exact matcher and MIFD (tests/sift_restatement.py) alone: that the committed cases of tests/sift_cases.py are not empty
 (so the GPU tests cannot pass on empty lists), what the score does on known pairs, and the pieces the kernels share with it: the polynomial exp / atan2 /
-sin / cos, the folded reflect-101 border, the matcher's tie rule."""
+sin / cos, the folded reflect-101 border, the matcher's tie rule.
+
+The second half proves the cases of tests/test_sift_edges_gpu.py: every parameter set, shape and built picture of tests/sift_cases.py holds what is recorded
+beside it, their union reaches every branch the restatement's census names (but the two stated as unreached), and a restatement with one rule deliberately wrong
+-- a `3` where nOctaveLayers belongs, a 33-tap blur without its last tap, a clamped border, a floored octave count -- differs from the right one on the named
+new case (and, for the `3`s, on no committed default case: the suite before these cases could not have seen them).  The host side of hive_amd.features that needs
+no GPU (octave_sizes, the refusal of 37 taps, SIFT._chunk) is here too."""
+import inspect
+import types
 import warnings
 
 import numpy as np
@@ -160,3 +168,218 @@ def test_mask_and_nfeatures_keep_what_they_should():
     resp = np.sort(full["candidates"]["response"])[::-1]
     assert len(few["candidates"]) == len(full["candidates"]) and 0 < len(few["keypoints"]) < len(full["keypoints"])
     assert (few["keypoints"][:, 4] >= resp[9]).all() and len(set(few["keypoints"][:, 4])) >= min(10, len(set(resp[:10])))
+
+
+# ---- the cases of tests/test_sift_edges_gpu.py ----
+@pytest.mark.parametrize("name", sift_cases.PARAMETER_SETS)
+def test_parameter_sets_are_not_empty(name):
+    """Both pictures of every parameter set have the recorded candidates and keypoints, candidates in every layer 1 .. nOctaveLayers, and blurs of the recorded
+    lengths (33 taps at "L1", "L2" and "L3"), by the restatement and by hive_amd.features alike."""
+    from hive_amd import features
+    kw = sift_cases.PARAMETER_SETS[name]
+    L, sigma = kw.get("nOctaveLayers", 3), kw.get("sigma", 1.6)
+    taps = sift_cases.PARAMETER_TAPS.get(name, sift_cases.DEFAULT_TAPS)
+    assert tuple(len(R.gaussian_taps(s)) for s in R.blur_sigmas(L, sigma)) == taps
+    assert tuple(len(features.gaussian_taps(s)) for s in features.blur_sigmas(L, sigma)) == taps
+    for which, (n_cand, n_kps) in zip(("ref", "est"), sift_cases.PARAMETER_COUNTS[name]):
+        s = sift_cases.restated(*sift_cases.PARAMETER_CASE, which, params=name)
+        print(f"{name} {which}: {len(s['candidates'])} candidates, {s['raw']} raw keypoints, {len(s['keypoints'])} keypoints")
+        assert (len(s["candidates"]), len(s["keypoints"])) == (n_cand, n_kps) and n_cand >= 7 and n_kps >= 17
+        assert set(s["candidates"]["layer"].tolist()) == set(range(1, L + 1))
+        assert all(octave.shape[0] == L + 3 for octave in s["pyramid"])
+    for third in ("L4", "L5"):
+        if name == third:
+            assert len(sift_cases.restated(*sift_cases.THIRD_CASE, "ref", params=name)["keypoints"]) >= 17
+
+
+@pytest.mark.parametrize("H,W", sift_cases.SHAPES)
+def test_shapes_hold_what_is_recorded(H, W):
+    """The octave planes, candidates, raw keypoints and keypoints of every shape; 6 x 70 and 7 x 9 have exactly one keypoint, 6 x 6 and 70 x 6 none."""
+    planes, n_cand, n_raw, n_kps = sift_cases.SHAPE_COUNTS[(H, W)]
+    s = sift_cases.restated(H, W, 0)
+    assert tuple(o.shape[1:] for o in s["pyramid"]) == planes and len(planes) == R.octave_count(H, W)
+    assert (len(s["candidates"]), s["raw"], len(s["keypoints"])) == (n_cand, n_raw, n_kps)
+    if (H, W) == (240, 320):
+        assert set((s["candidates"]["octave"] & 255).tolist()) == {0, 1, 2, 3}
+
+
+@pytest.mark.parametrize("name", sift_cases.BUILT)
+def test_built_pictures_reach_their_branch(name):
+    _, key, _ = sift_cases.BUILT[name]
+    n_cand, n_kps, octaves, reached = sift_cases.BUILT_COUNTS[name]
+    s = sift_cases.restated_built(name)
+    assert (len(s["candidates"]), len(s["keypoints"])) == (n_cand, n_kps)
+    assert tuple(sorted(set((s["candidates"]["octave"] & 255).tolist()))) == octaves
+    if key is not None:
+        assert s["census"][key] == reached >= 1
+    if name == "octave 4":
+        assert min(octaves) >= 4
+    if name == "byte 255":
+        assert s["descriptors"].max() == 255
+
+
+def test_the_new_cases_reach_every_branch_but_two():
+    """The census summed over every new case: each count that sift_cases.CENSUS records is >= 1 (refinements of 0 to 4 moves, a move between layers, every way out
+    -- the zero pivot among them, at contrastThreshold 0 -- several orientation peaks, cut windows of both kinds, the radius clamp, the 0.2 clip, a byte of 255),
+    candidates lie in octaves 0 to 4, and the two of sift_cases.UNREACHED are reached by none."""
+    total, octaves = {}, set()
+    for _, s in sift_cases.new_cases():
+        for key, count in s["census"].items():
+            total[key] = total.get(key, 0) + count
+        octaves |= set((s["candidates"]["octave"] & 255).tolist())
+    print(dict(sorted(total.items())), sorted(octaves))
+    for key in sift_cases.CENSUS:
+        assert total.get(key, 0) >= 1, key
+    assert {key: total[key] for key in sift_cases.CENSUS} == sift_cases.CENSUS  # the recorded figures are the measured ones
+    assert all(total.get(key, 0) == 0 for key in sift_cases.UNREACHED)
+    assert octaves == {0, 1, 2, 3, 4}
+
+
+# ---- a wrong rule must show ----
+def _wrong(*patches):
+    """tests/sift_restatement.py with pieces of its text replaced ((old, new, occurrences) each): a module of its own."""
+    source = inspect.getsource(R)
+    for old, new, count in patches:
+        assert source.count(old) == count, old
+        source = source.replace(old, new)
+    module = types.ModuleType("sift_restatement_wrong")
+    exec(compile(source, "sift_restatement_wrong", "exec"), module.__dict__)
+    return module
+
+
+# a `3` where nOctaveLayers belongs, one at a time: rule -> (the patch, the stage it is in)
+THREES = {
+    "contrast": (("abs(contr) * F(L) < ct", "abs(contr) * F(3) < ct", 1), "candidates"),
+    "size": (("(F(layer) + xi) / F(L))", "(F(layer) + xi) / F(3))", 1), "candidates"),
+    "layer bound": (("layer > L or c < BORDER", "layer > 3 or c < BORDER", 1), "candidates"),
+    "seed layer": (("octaves[-1][n_octave_layers][::2, ::2]", "octaves[-1][3][::2, ::2]", 1), "pyramid"),
+}
+THRESHOLD_THREE = ("0.5 * float(ct) / L * 255.0", "0.5 * float(ct) / 3 * 255.0", 1)
+
+
+def _stage_differs(wrong, rule_stage, picture, want, kw):
+    """Whether the wrong restatement's pyramid (a rule of the pyramid) or candidates on the right pyramid (a rule of the detection) differ from ``want``'s."""
+    L, sigma = kw.get("nOctaveLayers", 3), kw.get("sigma", 1.6)
+    if rule_stage == "pyramid":
+        got = wrong.pyramid(picture, L, sigma)
+        return len(got) != len(want["pyramid"]) or any(a.tobytes() != b.tobytes() for a, b in zip(got, want["pyramid"]))
+    got = wrong.candidates(want["pyramid"], None, picture.shape, L, kw.get("contrastThreshold", 0.04), kw.get("edgeThreshold", 10), sigma)
+    return got.tobytes() != want["candidates"].tobytes()
+
+
+@pytest.mark.parametrize("rule", THREES)
+def test_a_three_for_the_layer_count_shows_at_four_and_five_layers_only(rule):
+    """At "L4" and at "L5" the wrong rule changes the stage it is in: on both pictures of the pair for the contrast test, the size exponent and the seed layer; on
+    at least one of the pair and the third picture for the layer bound (a move into layer 4 or 5 is rare: at "L4" the pair has none and the third picture has
+    one, which is why it was chosen).  On every committed default case it changes nothing."""
+    patch, stage = THREES[rule]
+    wrong = _wrong(patch)
+    for name in ("L4", "L5"):
+        kw = sift_cases.PARAMETER_SETS[name]
+        shown = []
+        for case, which in ((sift_cases.PARAMETER_CASE, "ref"), (sift_cases.PARAMETER_CASE, "est"), (sift_cases.THIRD_CASE, "ref")):
+            picture = sift_cases.pair(*case)[0 if which == "ref" else 1]
+            shown.append(_stage_differs(wrong, stage, picture, sift_cases.restated(*case, which, params=name), kw))
+        print(f"{rule} at {name}: shows on {shown}")
+        assert any(shown) if rule == "layer bound" else all(shown[:2])
+    for case in sift_cases.CASES:
+        for k, which in enumerate(("ref", "est")):
+            assert not _stage_differs(wrong, stage, sift_cases.pair(*case)[k], sift_cases.restated(*case, which), {})
+
+
+def test_a_three_in_the_dog_threshold_cannot_show_in_any_stage():
+    """floor(0.5 * 0.04 / L * 255) is 1 for L = 3, 4 and 5 (1.7, 1.275, 1.02): at "L4" and "L5" a `3` there computes the same number, and no test could tell.
+    Where the number differs ("L1": 1 for 5, "L2": 1 for 2, "combined": 3 for 2) the wrong rule changes how many extrema start a refinement, so it is wrong,
+    but no stage output: the threshold is half the bound of the contrast test that every candidate passes later, |v| / 255 against |contr|, and no picture here
+    has an extremum between the two thresholds whose refined contrast passes.  (A search over thirteen pictures and twelve contrast thresholds from 0.1 to 0.7
+    at five layers, where the wrong threshold is the higher one, found none either.)  The rule is therefore pinned here on the census alone."""
+    wrong = _wrong(THRESHOLD_THREE)
+    for L in (3, 4, 5):
+        assert np.floor(0.5 * float(np.float32(0.04)) / L * 255.0) == 1.0
+    for name, differs in (("L1", True), ("L2", True), ("L4", False), ("L5", False), ("combined", True)):
+        kw = sift_cases.PARAMETER_SETS[name]
+        for k, which in enumerate(("ref", "est")):
+            want = sift_cases.restated(*sift_cases.PARAMETER_CASE, which, params=name)
+            picture = sift_cases.pair(*sift_cases.PARAMETER_CASE)[k]
+            census = {}
+            got = wrong.candidates(want["pyramid"], None, picture.shape, kw["nOctaveLayers"], kw.get("contrastThreshold", 0.04), kw.get("edgeThreshold", 10), kw["sigma"],
+                                   census=census)
+            print(f"{name} {which}: {want['census']['extrema']} starting extrema, {census['extrema']} with the wrong threshold")
+            assert (census["extrema"] != want["census"]["extrema"]) == differs
+            assert got.tobytes() == want["candidates"].tobytes()
+
+
+@pytest.mark.parametrize("name", ["L1", "L2", "L3"])
+def test_a_blur_without_its_33rd_tap_shows(name):
+    """A blur that stops after 32 taps (a halo one sample short at radius 16) changes the layers behind the 33-tap blur, and the candidates."""
+    wrong = _wrong(("for k in range(1, len(taps)):", "for k in range(1, min(len(taps), 32)):", 2))
+    kw = sift_cases.PARAMETER_SETS[name]
+    assert sift_cases.PARAMETER_TAPS[name][-1] == 33 and max(sift_cases.PARAMETER_TAPS[name][:-1]) < 33
+    picture = sift_cases.pair(*sift_cases.PARAMETER_CASE)[0]
+    want = sift_cases.restated(*sift_cases.PARAMETER_CASE, "ref", params=name)
+    got = wrong.detect_and_compute(picture, stages=True, **kw)
+    last = kw["nOctaveLayers"] + 2
+    for a, b in zip(got["pyramid"], want["pyramid"]):
+        assert a[:last].tobytes() == b[:last].tobytes() and a[last].tobytes() != b[last].tobytes()
+    assert got["candidates"].tobytes() != want["candidates"].tobytes()
+    default = sift_cases.CASES[0]
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(wrong.pyramid(sift_cases.pair(*default)[0]), sift_cases.restated(*default, "ref")["pyramid"]))
+
+
+@pytest.mark.parametrize("H,W", [(23, 40), (46, 50)])
+def test_a_clamped_border_shows_in_the_last_octave(H, W):
+    wrong = _wrong(("return np.where(m < n, m, period - m)", "return np.clip(i, 0, n - 1)", 1))
+    want = sift_cases.restated(H, W, 0)["pyramid"]
+    got = wrong.pyramid(sift_cases.pair(H, W, 0)[0])
+    assert len(got) == len(want) and min(want[-1].shape[1:]) == 2
+    assert got[-1].shape == want[-1].shape and got[-1].tobytes() != want[-1].tobytes()
+
+
+def test_a_floored_octave_count_shows_at_the_listed_sizes():
+    """The rule is round(log2(min(2H, 2W)) - 2) + 1; its count changes between smaller sides 11 | 12, 22 | 23 and 45 | 46.  With the floor in place of the
+    rounding the pyramid loses an octave at 12, 23 and 46 and keeps its length at 11, 22 and 45: over the shapes, exactly at the ones listed below."""
+    wrong = _wrong(("int(np.rint(np.log(float(2 * min(H, W))) / np.log(2.0) - 2.0)) + 1", "int(np.floor(np.log(float(2 * min(H, W))) / np.log(2.0) - 2.0)) + 1", 1))
+    changed = set()
+    for H, W in sift_cases.SHAPES:
+        want = len(sift_cases.SHAPE_COUNTS[(H, W)][0])
+        got = len(wrong.pyramid(sift_cases.pair(H, W, 0)[0]))
+        assert got in (want, want - 1)
+        if got != want:
+            changed.add((H, W))
+    assert changed == {(6, 6), (6, 70), (70, 6), (7, 9), (12, 40), (23, 40), (46, 50), (240, 320)}
+    assert [R.octave_count(m, 60) for m in (11, 12, 22, 23, 45, 46)] == [3, 4, 4, 5, 5, 6]
+
+
+# ---- the host side of hive_amd.features that needs no GPU ----
+def test_octave_sizes_follow_the_closed_form():
+    """For every smaller side m from 6 to 300: round(log2(2 m) - 2) is the largest k with 2^(2 k + 3) <= (2 m)^2 (log2(2 m) - 2 is never half an integer), so the
+    count is ((4 m^2).bit_length() - 4) // 2 + 1 in integers, and octave o is (2H >> o, 2W >> o).  The restatement's count is the same, and the planes of its
+    pyramids at the shapes of sift_cases.SHAPES are these sizes."""
+    from hive_amd import features
+    for m in range(6, 301):
+        count = ((4 * m * m).bit_length() - 4) // 2 + 1
+        for h, w in ((m, m), (m, m + 7), (m + 50, m)):
+            assert features.octave_sizes(h, w) == [(2 * h >> o, 2 * w >> o) for o in range(count)] and R.octave_count(h, w) == count
+    for (H, W), (planes, _, _, _) in sift_cases.SHAPE_COUNTS.items():
+        assert tuple(features.octave_sizes(H, W)) == planes
+
+
+def test_37_taps_are_refused_on_the_host():
+    from hive_amd import features
+    assert max(len(R.gaussian_taps(s)) for s in R.blur_sigmas(2, 1.6)) == 37
+    with pytest.raises(ValueError, match="37 taps"):
+        features.SIFT(nOctaveLayers=2, sigma=1.6)
+    for kw in sift_cases.PARAMETER_SETS.values():
+        features.SIFT(**kw)
+
+
+def test_chunk_sizes_of_the_small_workspace():
+    """What tests/test_sift_edges_gpu.py assumes: with sift_cases.CHUNK_WORKSPACE two 61 x 83 pictures fit, so five run as 2 + 2 + 1; the default holds all."""
+    from hive_amd import features
+    H, W = sift_cases.CHUNK_CASE
+    small = features.SIFT(capacity=512, workspace_bytes=sift_cases.CHUNK_WORKSPACE)
+    per_image = 4 * (4 * H * W) * 9 + 512 * 20 * 4
+    assert per_image == 770032 and 2 * per_image <= sift_cases.CHUNK_WORKSPACE < 3 * per_image
+    assert [small._chunk(H, W, n) for n in (1, 2, 3, 5)] == [1, 2, 2, 2]
+    assert [features.SIFT(capacity=512)._chunk(H, W, n) for n in (1, 3, 5)] == [1, 3, 5]
+    assert features.SIFT(capacity=512, workspace_bytes=1)._chunk(H, W, 5) == 1

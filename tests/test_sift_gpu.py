@@ -1,6 +1,14 @@
 """SIFT, the exact matcher and MIFD on the GPU (csrc/sift.hip behind hive_amd.features and hive_amd.evaluation) against the numpy float32 restatement of their
 rules (tests/sift_restatement.py), bit for bit at every stage: the Gaussian layers of every octave, the refined candidates, the oriented keypoints, the
-descriptors, the matches, the score.  The cases are those of tests/sift_cases.py, which tests/test_sift_cpu.py proves not to be empty."""
+descriptors, the matches, the score.  The cases are those of tests/sift_cases.py, which tests/test_sift_cpu.py proves not to be empty.
+
+This file runs the default parameters (nOctaveLayers 3, contrastThreshold 0.04, edgeThreshold 10, sigma 1.6: blurs of 11 to 27 taps) at 48 x 64, 61 x 83 and
+96 x 128.  tests/test_sift_edges_gpu.py compares the rest in the same way: nOctaveLayers 1 to 5 as (1, 0.58), (2, 1.4), (3, 2.0), (4, 1.6), (5, 1.6), the first three
+with a last blur of 33 taps; contrastThreshold 0, 0.09 and 6 / 255; edgeThreshold 2 and 50; a combined set; a mask and nfeatures at five layers; the shapes 6 x 6,
+6 x 70, 70 x 6, 7 x 9, 11 | 12 x 40, 22 | 23 x 40, 45 | 46 x 50 and 240 x 320; pictures built for the descriptor radius clamp, a candidate in octave 4 and a descriptor
+byte of 255; a capacity met exactly and missed by one, chunked batches, a remade native detector, one keypoint a side, the ratio test on an exact tie.  Stated as
+unreached by any case (sift_cases.UNREACHED): the refinement's 2^29 guard, and an angle folded from 360 to 0 (it needs bins 35 and 1 of the smoothed histogram
+equal to the bit).  A `3` for nOctaveLayers in the DoG threshold cannot show in any stage (tests/test_sift_cpu.py says why)."""
 import warnings
 
 import numpy as np
