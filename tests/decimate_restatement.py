@@ -76,7 +76,8 @@ def mix32(v):
 
 def cost_bits(cost):
     """The high word of a key: float32(cost) mapped to an order-preserving unsigned integer."""
-    bits = int(np.array(cost, np.float64).astype(np.float32).view(np.uint32))
+    with np.errstate(over="ignore"):  # a finite float64 cost past float32's range is +-inf, as the kernel's cast makes it
+        bits = int(np.array(cost, np.float64).astype(np.float32).view(np.uint32))
     return (~bits) & 0xffffffff if bits & 0x80000000 else bits | 0x80000000
 
 
@@ -119,7 +120,10 @@ def locked_vertices(n_vertices, faces):
 
 
 def collapse_check(m, q, pos, locked, v0, v1, max_error):
-    """(None, cost, faces removed) for a legal halfedge collapse v0 -> v1 on mesh m, else (the name of the first rule that rejects it, None, 0)."""
+    """(None, cost, faces removed) for a legal halfedge collapse v0 -> v1 on mesh m, else (the name of the first rule that rejects it, None, 0).
+    `edge faces` is never the first rule: v1 is a neighbour of v0, so the edge has a face, and the ends of an edge with more than two faces are locked
+    (and no collapse makes such an edge: the link condition forbids it).  `side edges` is the first only at a vertex like decimate_cases.flag's: on a
+    manifold boundary the other faces of v0 give it further boundary edges, so it is locked or rejected as `boundary` before."""
     if locked[v0] or locked[v1]:
         return "locked", None, 0
     if len(m.vf.get(v0, ())) < 2:

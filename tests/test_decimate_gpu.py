@@ -1,6 +1,5 @@
 """Quadric edge collapse on the GPU (csrc/decimate.hip hive_mesh_decimate, hive_fg_frame_mesh_dec) against the numpy restatement of the same parallel
 rounds (tests/decimate_restatement.py), bit for bit; the frame path, process_frame and Pipeline.run with decimation switched on."""
-import ctypes
 import functools
 import os
 
@@ -8,43 +7,17 @@ import numpy as np
 import pytest
 
 import decimate_restatement as D
+from decimate_cases import assert_same, gpu_decimate
 
 pytestmark = pytest.mark.gpu
 
 MESHES = D.test_meshes(12)
 
 
-def gpu_decimate(ctx, verts, faces, budget, max_error, on_device):
-    """hive_mesh_decimate directly: (faces, kept vertex ids, stats)."""
-    from hive_amd._lib import MEM_DEVICE, MEM_HOST, ptr
-    v = np.ascontiguousarray(verts, np.float64)
-    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
-    nf, nv = ctypes.c_int64(0), ctypes.c_int64(0)
-    stats = np.zeros(3, np.int64)
-    if on_device:
-        import torch
-        dv, df = torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda()
-        of, ovi = torch.empty((len(f), 3), dtype=torch.int32, device="cuda"), torch.empty(len(v), dtype=torch.int32, device="cuda")
-        ctx.follow_torch_stream()
-        ctx.check(ctx.lib.hive_mesh_decimate(ctx.handle, ptr(dv), len(v), ptr(df), len(f), budget, max_error, MEM_DEVICE, ptr(of), ptr(ovi), ctypes.byref(nf),
-                                             ctypes.byref(nv), ptr(stats)))
-        return of[:nf.value].cpu().numpy(), ovi[:nv.value].cpu().numpy(), tuple(stats.tolist())
-    of, ovi = np.empty((len(f), 3), np.int32), np.empty(len(v), np.int32)
-    ctx.check(ctx.lib.hive_mesh_decimate(ctx.handle, ptr(v), len(v), ptr(f), len(f), budget, max_error, MEM_HOST, ptr(of), ptr(ovi), ctypes.byref(nf),
-                                         ctypes.byref(nv), ptr(stats)))
-    return of[:nf.value], ovi[:nv.value], tuple(stats.tolist())
-
-
 @functools.lru_cache(maxsize=None)
 def restated(name, budget, max_error):
     verts, faces = MESHES[name]
     return D.decimate(verts, faces, budget, max_error)
-
-
-def assert_same(got, want):
-    assert got[2] == want[2], (got[2], want[2])
-    assert np.array_equal(got[1], want[1])
-    assert np.array_equal(got[0], want[0])
 
 
 @pytest.mark.parametrize("name", sorted(MESHES))
@@ -147,7 +120,9 @@ def test_deterministic(gpu_ctx):
 
 
 def test_full_frame_1080p_invariants(gpu_ctx):
-    """A whole 1080p frame as one object (~4 M faces): too large for the restatement; topology, a clean output, the budget and determinism."""
+    """A whole 1080p frame as one object (~4 M faces): too large for the restatement; topology, a clean output, the budget and determinism.
+    This is the only cover of the kernels' grid-stride loops: they take a second turn only above num_cus * 8 * 256 items (about 524 k), where the
+    restatement needs minutes per round; tests/test_decimate_edges_gpu.py stops at 79 k faces."""
     import torch
     from hive_amd import foreground
     from hive_amd.options import MeshDecimationOptions
