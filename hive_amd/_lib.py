@@ -18,7 +18,7 @@ OK, ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_EMPTY, ERR_STATE = 0, -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
 ROUND_HALF_EVEN, ROUND_HALF_AWAY = 0, 1
 F32, F16, BF16 = 0, 1, 2
-ABI_VERSION = 9  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step; 7 = hive_dpt_plan_arena, hive_gn_gram_preferred; 8 = hive_sift_*, hive_knn_match, hive_mifd; 9 = hive_pairs_match, hive_ransac_homography, hive_pairs_compact (hive_pose_optimise and hive_pose_project joined without a new number: additions only, and a library without them fails to load by name; hive_gltf_layout and hive_gltf_pack likewise; hive_ransac_rigid likewise)
+ABI_VERSION = 9  # include/hive_mi355x.h HIVE_ABI_VERSION: 2 = the network entry points take the 16-bit dtype (HIVE_F16 / HIVE_BF16); 3 = hive_similarity_*; 4 = hive_lpips_*; 5 = the sparse merge (hive_*_segments); 6 = hive_tsdf_raycast, hive_frame_maps, hive_icp_step; 7 = hive_dpt_plan_arena, hive_gn_gram_preferred; 8 = hive_sift_*, hive_knn_match, hive_mifd; 9 = hive_pairs_match, hive_ransac_homography, hive_pairs_compact (hive_pose_optimise and hive_pose_project joined without a new number: additions only, and a library without them fails to load by name; hive_gltf_layout and hive_gltf_pack likewise; hive_ransac_rigid likewise; hive_motion_mask, hive_mask_open, hive_label_components and hive_motion_segment likewise)
 
 c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 P = ctypes.POINTER
@@ -144,6 +144,10 @@ SIGNATURES = {
     "hive_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "hive_png_layout": (c_int, [c_void_p, c_int, c_void_p, P(c_int64)]),
     "hive_png_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "hive_motion_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p]),
+    "hive_mask_open": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "hive_label_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    "hive_motion_segment": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hive_depth_apply_mask_se": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "hive_vit_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, P(c_void_p)]),
     "hive_vit_weights_modified": (c_int, [c_void_p]),

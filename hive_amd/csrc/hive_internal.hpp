@@ -87,6 +87,7 @@ constexpr int SC_TSDF_COUNTERS = 128, SC_TSDF_COUNTERS_WORDS = COUNT_SLOTS * COU
 constexpr int MS_BASE = 2304;                          // tsdf.hip: the two alternating blocks of the fused sweep, MS_STRIDE words each
 constexpr int CC_SCALARS = 3584, CC_SCALARS_WORDS = 14;            // fgmesh.hip: the clean-up's / the frame mesh runner's block, [0..13]
 constexpr int DEC_SCALARS = 3712, DEC_SCALARS_WORDS = 20;          // decimate.hip: [0..15] hive_decimate_run, [16..19] hive_mesh_decimate's counts
+constexpr int SEG_SCALARS = 3744, SEG_SCALARS_WORDS = 1;           // segment.hip: the first frame with more components than a uint8 label holds
 struct hive_scalar_region {
     int at, words;
 };
@@ -95,7 +96,7 @@ constexpr hive_scalar_region HIVE_SCALAR_MAP[] = {
     {SC_PROJECT_BBOX, SC_PROJECT_BBOX_WORDS},        {SC_GRID_TOTALS, SC_GRID_TOTALS_WORDS},   {SC_FILTER_TOTAL, SC_FILTER_TOTAL_WORDS},
     {SC_WINDOW_BOX, SC_WINDOW_BOX_WORDS},            {SC_TSDF_FRAME_B, SC_TSDF_FRAME_WORDS},   {SC_TSDF_COUNTERS, SC_TSDF_COUNTERS_WORDS},
     {MS_BASE, MS_STRIDE},                            {MS_BASE + MS_STRIDE, MS_STRIDE},         {CC_SCALARS, CC_SCALARS_WORDS},
-    {DEC_SCALARS, DEC_SCALARS_WORDS},
+    {DEC_SCALARS, DEC_SCALARS_WORDS},                {SEG_SCALARS, SEG_SCALARS_WORDS},
 };
 constexpr bool hive_scalar_map_ok() {
     int end = 0;

@@ -126,9 +126,11 @@ class TUMAdaptor(DatasetAdaptor):
         return (1000 * depth_map).astype(np.uint16)  # convert to mm from metres.
 
     def convert(self, estimate_pose=False, estimate_depth=False, inpainting_mode=InpaintingMode.Off, static_camera=False, no_cache=False,
-                profiling=None, png_encoder="host") -> HiveDataset:
+                profiling=None, png_encoder="host", segment_motion=False) -> HiveDataset:
         """Write the HIVE-format folder and return it as a ``HiveDataset`` (dataset_adaptors.py:176-266).
-        Instance masks need detectron2 (out of scope): empty masks are written, i.e. a static scene.
+        The reference's instance masks come from detectron2 (out of scope).  By default empty masks are written, i.e. a static scene.  ``segment_motion=True``
+        (or a ``segmentation.MotionSegmentationOptions``) replaces them, once the trajectory is final and before any inpainting, by
+        ``segmentation.segment_dataset``'s: what moved against the fused static model -- a rule of this project, not Mask R-CNN; it needs the sensor depth.
         ``estimate_depth=True`` replaces the sensor depth by DPT-Hybrid estimates (needs the weights file).  ``png_encoder`` ("host" | "gpu") goes to
         ``estimate_depth_dpt`` and ``inpaint_frame_data``; the frames copied here are always written by the host encoder.
         ``estimate_pose=True`` (with the sensor depth): the reference runs COLMAP, which is absent; here the folder is written as usual and
@@ -140,6 +142,9 @@ class TUMAdaptor(DatasetAdaptor):
                                       "COLMAP, which the reference runs here, is outside the dense-compute scope")
         if static_camera:
             raise NotImplementedError("the static-camera override is outside the dense-compute scope")
+        if segment_motion and estimate_depth:
+            raise NotImplementedError("motion segmentation on estimated depth: the per-frame scale of an estimated depth map makes its difference to the model "
+                                      "meaningless; use the sensor depth")
         _check_inpainting_mode(inpainting_mode)
         out = self.output_path
         if no_cache and os.path.isdir(out):
@@ -168,6 +173,11 @@ class TUMAdaptor(DatasetAdaptor):
             if estimate.lost:
                 warnings.warn(f"pose estimation: no chain of frame pairs reached the frames {estimate.lost}; each copies the pose of a neighbour")
             estimate.trajectory.save(pjoin(out, HiveDataset.camera_trajectory_filename))
+        if segment_motion:
+            from hive_amd import segmentation
+            logging.info("Segmenting what moved against the static model...")
+            options = segment_motion if isinstance(segment_motion, segmentation.MotionSegmentationOptions) else None
+            segmentation.segment_dataset(HiveDataset(out), options, png_encoder=png_encoder)
         with timed_block("Inpainted the frame data in", profiling, ('timing', 'load_dataset', 'inpainting')):  # (dataset_adaptors.py:261-262)
             self._inpaint_frame_data(mode=inpainting_mode, png_encoder=png_encoder)
         return HiveDataset(out)

@@ -437,6 +437,35 @@ int hive_pose_optimise(hive_ctx *ctx, double *params, double *scale, double *shi
 /* Steps 1 and 2 of an epoch of hive_pose_optimise alone, on params f64 [n][7] in / out (host), n >= 1: what the tests hold against the stated order. */
 int hive_pose_project(hive_ctx *ctx, double *params, int n_frames, double max_frame_distance);
 
+/* ---- motion segmentation: instance masks from the static model (hive_amd/segmentation.py).  The reference takes its masks from detectron2's Mask R-CNN
+ * (hive/io.py:163-230), which is absent here; these are rules of this project: they find what moved against the fused model, not persons.  The format is the
+ * reference's: u8, 0 = background, 1 .. k = objects, ids per frame and not tracked over time (io.py:214-218).  Everything is batched over n frames
+ * [n][H][W] in device memory, 1 <= n <= 65535, H * W < 2^30; nothing synchronises except where it says so.
+ * Rule `motion`.  live, model f32, metres, 0 = invalid.  In float32, each operation rounded once, no fused multiply-add:
+ *     rel = relative_difference * model;  thr = min_difference > rel ? min_difference : rel;  diff = model - live;
+ *     mask = live > 0 && model > 0 && diff > thr            (written 0 / 1)
+ *   i.e. the live surface lies more than max(min_difference, relative_difference * model) in front of the model's along the same ray.  A pixel whose ray
+ *   found no model surface is not set: unknown, not moving.  Both parameters finite and not negative.
+ * Rule `open`.  The set is mask != 0.  `iterations` erosions and then `iterations` dilations with the 3 x 3 square = one (2 it + 1)^2 box minimum and then one
+ *   box maximum, each over the pixels of the picture alone: pixels outside take no part (cv2's default border; for the dilation hive_dilate_mask's
+ *   convention).  Output 0 / 1.  iterations = 0: out = mask byte for byte.  0 <= iterations <= 16.  d_out may be d_mask.
+ * Rule `label`.  The set is mask != 0; two set pixels are neighbours when they differ by one in u or in v (connectivity 4) or by at most one in both
+ *   (connectivity 8); a component is a class of the closure of that relation.  A component's root is the smallest raster index v * W + u among its pixels, its
+ *   area the number of its pixels.  Components with area < min_area are removed (area == min_area stays); the others are numbered 1 .. k in ascending order of
+ *   their roots (the order scipy.ndimage.label numbers them in).  labels = the number of the pixel's component, 0 for clear pixels and removed components;
+ *   d_counts[frame] = k; d_areas (may be NULL with area_capacity 0) i32 [n][area_capacity]: the area of component j at j - 1, zeros behind k, components past
+ *   the capacity not written.  The result is a function of the mask alone: the order in which workgroups run, and which of two racing unions wins, changes
+ *   no bit of it.  label_bytes 4: d_labels i32, any k, no synchronisation.  label_bytes 1: d_labels u8; the call waits for the device and fails with
+ *   HIVE_ERR_INVALID, naming the first such frame and its count, when a frame has more than 255 components left (labels and counts are written all the same).
+ * hive_motion_segment: `motion`, `open` in place, `label` into u8 ids, in one call; one read-back at its end (the 255 limit). */
+int hive_motion_mask(hive_ctx *ctx, const float *d_live, const float *d_model, int n, int H, int W, float min_difference, float relative_difference,
+                     uint8_t *d_mask);
+int hive_mask_open(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, int iterations, uint8_t *d_out);
+int hive_label_components(hive_ctx *ctx, const uint8_t *d_mask, int n, int H, int W, int connectivity, int min_area, int label_bytes, void *d_labels,
+                          int32_t *d_counts, int32_t *d_areas, int area_capacity);
+int hive_motion_segment(hive_ctx *ctx, const float *d_live, const float *d_model, int n, int H, int W, float min_difference, float relative_difference,
+                        int opening_iterations, int connectivity, int min_area, uint8_t *d_ids, int32_t *d_counts);
+
 /* ---- dilate_mask(mask, MaskDilationOptions(num_iterations)) -- hive/image_processing.py:30-45 */
 /* 3x3 rectangular structuring element applied `iterations` times == one (2*it+1)^2 box max
  * (cv2.dilate border = no contribution from outside).  mask/out u8 [H][W], non-zero = set; out is written as 0 / 1 and must not
