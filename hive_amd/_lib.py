@@ -116,6 +116,9 @@ SIGNATURES = {
     "hive_frame_maps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_icp_step": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,
                               P(c_int64), c_void_p]),
+    "hive_gray_pyramid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "hive_rgbd_icp_step": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_similarity_ssim_psnr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_similarity_msssim_level": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hive_similarity_finish": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p]),

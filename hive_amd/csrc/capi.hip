@@ -34,7 +34,7 @@ int hive_reserve_device(hive_ctx *ctx, void **ptr, size_t *cur, size_t bytes) {
 }
 
 int hive_pinned_small(hive_ctx *ctx, void **out) {
-    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 256, hipHostMallocDefault));
+    if (!ctx->h_pinned_small) HIVE_CHECK_HIP(ctx, hipHostMalloc(&ctx->h_pinned_small, 512, hipHostMallocDefault));
     *out = ctx->h_pinned_small;
     return HIVE_OK;
 }

@@ -46,7 +46,7 @@ struct hive_ctx {
     int tsdf_scalars = 0;           // which of the two TSDF scalar blocks the frame in flight uses (tsdf.hip prepare_frame)
     int tsdf_multi_scalars = 0;     // the same for the fused sweep's blocks (SC_TSDF_SWEEP_A / _B)
     unsigned *d_scalars = nullptr;  // HIVE_SCALAR_WORDS words of small results and counters: the map of its regions is below (SC_*)
-    void *h_pinned_small = nullptr;  // 256 bytes of pinned host memory for small read-backs (mesh totals), allocated on first use: hive_pinned_small
+    void *h_pinned_small = nullptr;  // 512 bytes of pinned host memory for small read-backs (mesh totals, the tracker's 58 sums), allocated on first use: hive_pinned_small
     void *d_zeros = nullptr;        // 256 bytes of zeros: the source of padding taps in the implicit-GEMM convolutions
     // split-K of the MFMA tile kernels at small batches (mfma_pipe.hpp splitk_*): f32 partial tiles + one arrival counter per tile (zero between launches)
     void *d_splitk = nullptr;
@@ -155,7 +155,7 @@ struct hive_device_latch {
 
 // grows *ptr to at least `bytes` of device memory
 int hive_reserve_device(hive_ctx *ctx, void **ptr, size_t *cur, size_t bytes);
-// the context's 256 bytes of pinned host memory for small read-backs (allocated on first use)
+// the context's 512 bytes of pinned host memory for small read-backs (allocated on first use)
 int hive_pinned_small(hive_ctx *ctx, void **out);
 // copies `bytes` from host memory to device memory `dst` through the pinned ring; returns once the
 // host buffer may be reused by the caller

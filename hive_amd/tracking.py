@@ -3,7 +3,9 @@
 The reference takes its poses from COLMAP, or from BundleFusion for the alternative background method -- external binaries, absent here
 (``TUMAdaptor.convert(estimate_pose=True)`` keeps raising).  This module is the RGB-D alternative, KinectFusion-style: the volume is ray cast from the last
 good pose (csrc/raycast.hip), the live depth frame is aligned to those model maps by point-to-plane ICP with projective association (csrc/track.hip: one
-launch and one copy of 29 numbers per iteration, the 6 x 6 solve on the host in float64), and the frame is integrated at the pose found.
+launch and one copy of 29 numbers per iteration, the 6 x 6 solve on the host in float64), and the frame is integrated at the pose found.  With
+``photometric_weight`` > 0 the frame's colour is aligned to the model's ray-cast colour in the same launch (the photometric term of RGB-D odometry, 58 numbers
+per iteration), which keeps a view of one or two planes with texture on them tracked; the rules are restated in tests/photometric_restatement.py.
 
 The rules of the kernels are stated in include/hive_mi355x.h above ``hive_tsdf_raycast`` and restated in numpy in tests/raycast_restatement.py and
 tests/tracking_restatement.py.  Poses are camera-to-world 4 x 4 float64, as ``TSDFVolume.integrate`` takes them; the trajectories returned are in HIVE's
@@ -91,6 +93,58 @@ def icp_step(ctx, K, live_vertex, live_normal, model_vertex, model_normal, model
     return sums, int(pairs.value)
 
 
+def _device_color(color, device):
+    import torch
+    if not hasattr(color, "data_ptr"):
+        color = torch.from_numpy(np.ascontiguousarray(color))
+    if color.dtype != torch.uint8 or color.dim() != 3 or color.shape[2] != 3:
+        raise ValueError(f"color: a uint8 (H, W, 3) picture, got {tuple(color.shape)} {color.dtype}")
+    return color.to(device).contiguous()
+
+
+def intensity_pyramid(color, levels=3, ctx=None):
+    """The intensity pyramid of a colour frame (``hive_gray_pyramid``) -> per level a float32 (H_l, W_l) device view of one packed buffer: level 0 is the
+    integer luma / 255, level l + 1 the plain 2 x 2 means of level l, with the sizes of ``frame_maps``."""
+    import torch
+    ctx = (ctx or _lib.default_context()).follow_torch_stream()
+    color = _device_color(color, f"cuda:{ctx.device}")
+    h, w = (int(v) for v in color.shape[:2])
+    levels = int(levels)
+    if levels < 1 or (h >> (levels - 1)) == 0 or (w >> (levels - 1)) == 0:
+        raise ValueError(f"{h} x {w} has no {levels} pyramid levels")
+    sizes = [(h >> l, w >> l) for l in range(levels)]
+    gray = torch.empty(sum(a * b for a, b in sizes), dtype=torch.float32, device=color.device)
+    ctx.check(ctx.lib.hive_gray_pyramid(ctx.handle, ptr(color), h, w, levels, ptr(gray)))
+    out, at = [], 0
+    for a, b in sizes:
+        out.append(gray[at:at + a * b].view(a, b))
+        at += a * b
+    return out
+
+
+def rgbd_icp_step(ctx, K, live_vertex, live_normal, live_gray, model_vertex, model_normal, model_depth, model_color, model_pose, est_pose, dist_thresh,
+                  cos_thresh, pair_mask=None, photo_mask=None):
+    """``hive_rgbd_icp_step``: (sums float64 [56], (geometric pairs, photometric pairs)) of one Gauss-Newton step at one level -- ``icp_step``'s 28 sums, then
+    the photometric term's 28; synchronises (one copy of 58 numbers)."""
+    h, w = (int(v) for v in live_vertex.shape[:2])
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
+    model_pose = np.ascontiguousarray(model_pose, dtype=np.float64).reshape(4, 4)
+    est_pose = np.ascontiguousarray(est_pose, dtype=np.float64).reshape(4, 4)
+    sums = np.zeros(56, np.float64)
+    pairs = np.zeros(2, np.int64)
+    ctx.check(ctx.lib.hive_rgbd_icp_step(ctx.handle, h, w, ptr(K), ptr(live_vertex), ptr(live_normal), ptr(live_gray), ptr(model_vertex), ptr(model_normal),
+                                         ptr(model_depth), ptr(model_color), ptr(model_pose), ptr(est_pose), float(dist_thresh), float(cos_thresh), ptr(sums),
+                                         ptr(pairs), ptr(pair_mask), ptr(photo_mask)))
+    return sums, (int(pairs[0]), int(pairs[1]))
+
+
+def combined_sums(sums, photometric_weight):
+    """The 28 sums of A = A_geo + w^2 A_photo and b = b_geo + w^2 b_photo from the 56 of ``hive_rgbd_icp_step``; sum r^2 stays the geometric one."""
+    out = np.array(sums[:28], np.float64)
+    out[:27] = out[:27] + (float(photometric_weight) * float(photometric_weight)) * np.asarray(sums[28:55], np.float64)
+    return out
+
+
 def normal_equations(sums):
     """(A 6 x 6 symmetric, b 6, sum r^2) from the 28 sums of ``hive_icp_step``."""
     A = np.zeros((6, 6), np.float64)
@@ -135,28 +189,46 @@ def level_iterations(iterations, levels):
 
 
 def icp_align(volume, depth, cam_intr, model_pose, init_pose=None, levels=3, iterations=(10, 5, 4), dist_thresh=None, angle_deg=20.0, min_pair_share=0.1,
-              max_cond=DEFAULT_MAX_COND, pyr_delta=0.05, ctx=None) -> TrackResult:
+              max_cond=DEFAULT_MAX_COND, pyr_delta=0.05, ctx=None, color=None, photometric_weight=0.0) -> TrackResult:
     """Align a depth frame to the volume: frame-to-model point-to-plane ICP, coarse to fine.
 
     The volume is ray cast once per level at ``model_pose`` (the last good pose) with that level's size and intrinsics; the estimate starts at ``init_pose``
     (default: ``model_pose``).  Per iteration one ``hive_icp_step`` and one 6 x 6 Cholesky solve on the host; the estimate moves by T <- [exp(omega) | v] T.
     ``dist_thresh`` (metres, default twice the truncation distance) and ``angle_deg`` gate the pairs.  Tracking is lost -- ``ok=False``, the pose returned is
     the initial one, nothing raises -- when a step has fewer pairs than ``min_pair_share`` of its level's pixels or cond(A) above ``max_cond`` (a scene that
-    does not constrain all six degrees of freedom: one or two planes)."""
+    does not constrain all six degrees of freedom: one or two planes).
+
+    With the frame's ``color`` (uint8 (H, W, 3)) and a ``photometric_weight`` w > 0 the photometric term of RGB-D odometry is added: each level's ray cast
+    returns the model's colour too, each iteration is one ``hive_rgbd_icp_step``, and the step solves A = A_geo + w^2 A_photo, b = b_geo + w^2 b_photo.  w is
+    in metres per unit of intensity (intensity in [0, 1]): texture then fixes the directions that one or two planes leave free.  The pair-share gate stays on
+    the geometric pairs, ``max_cond`` applies to the combined A, ``rmse`` stays the geometric one.  Off by default: the model's colour is the nearest voxel's,
+    and where geometry already fixes the pose a heavy colour term costs accuracy.  Without a colour or with a weight of 0 the launches
+    and the result are those of the geometric alignment."""
     ctx = ctx or volume._ctx
+    weight = float(photometric_weight)
+    if not np.isfinite(weight) or weight < 0:
+        raise ValueError(f"photometric_weight: a finite number >= 0, got {photometric_weight}")
     model_pose = np.ascontiguousarray(model_pose, dtype=np.float64).reshape(4, 4)
     init = model_pose.copy() if init_pose is None else np.array(init_pose, dtype=np.float64).reshape(4, 4)
     levels = int(levels)
+    if color is not None and tuple(color.shape[:2]) != tuple(depth.shape[:2]):
+        raise ValueError(f"color is {tuple(color.shape[:2])}, depth is {tuple(depth.shape[:2])}")
     maps = frame_maps(depth, cam_intr, levels, pyr_delta, ctx)
+    gray = intensity_pyramid(color, levels, ctx) if color is not None and weight > 0 else None
     dist = float(2.0 * volume._trunc_margin if dist_thresh is None else dist_thresh)
     cos_min = float(np.cos(np.deg2rad(angle_deg)))
     counts = level_iterations(iterations, levels)
     est, pairs, rmse, cond, done = init.copy(), 0, 0.0, float("inf"), 0
     for l in range(levels - 1, -1, -1):
         h, w = maps.sizes[l]
-        _, model_v, model_n = volume.raycast(maps.K[l], model_pose, (h, w), return_vertex=True, return_normal=True)
+        model_d, model_v, model_n, *model_c = volume.raycast(maps.K[l], model_pose, (h, w), return_vertex=True, return_normal=True, return_color=gray is not None)
         for _ in range(counts[l]):
-            sums, pairs = icp_step(ctx, maps.K[l], maps.vertex[l], maps.normal[l], model_v, model_n, model_pose, est, dist, cos_min)
+            if gray is None:
+                sums, pairs = icp_step(ctx, maps.K[l], maps.vertex[l], maps.normal[l], model_v, model_n, model_pose, est, dist, cos_min)
+            else:
+                both, (pairs, _) = rgbd_icp_step(ctx, maps.K[l], maps.vertex[l], maps.normal[l], gray[l], model_v, model_n, model_d, model_c[0], model_pose, est,
+                                                 dist, cos_min)
+                sums = combined_sums(both, weight)
             done += 1
             rmse = float(np.sqrt(sums[27] / pairs)) if pairs else 0.0
             xi, cond = (None, float("inf")) if pairs < min_pair_share * h * w else solve_step(sums)
@@ -168,7 +240,8 @@ def icp_align(volume, depth, cam_intr, model_pose, init_pose=None, levels=3, ite
 
 class Tracker:
     """Tracks a camera through a depth sequence and fuses what it sees: the first frame is integrated at ``first_pose``; every later frame is aligned against
-    the volume from the last good pose (``icp_align``) and integrated with ``TSDFVolume.integrate`` only when the alignment held."""
+    the volume from the last good pose (``icp_align``) and integrated with ``TSDFVolume.integrate`` only when the alignment held.  ``icp_options`` go to
+    ``icp_align``; with a ``photometric_weight`` > 0 among them every frame's colour goes there too."""
 
     def __init__(self, volume, cam_intr, first_pose=np.eye(4), **icp_options):
         self.volume = volume
@@ -182,7 +255,8 @@ class Tracker:
         if self.frames == 0:
             result = TrackResult(self.pose.copy(), True, 0, 0.0, 0.0, 0)
         else:
-            result = icp_align(self.volume, depth, self.cam_intr, self.pose, **self.icp_options)
+            with_color = float(self.icp_options.get("photometric_weight", 0.0)) > 0  # (a negative weight goes on to icp_align, which raises)
+            result = icp_align(self.volume, depth, self.cam_intr, self.pose, **self.icp_options, color=color if with_color else None)
         self.frames += 1
         if result.ok:
             self.volume.integrate(color, depth, self.cam_intr, result.pose)

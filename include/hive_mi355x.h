@@ -633,6 +633,32 @@ int hive_frame_maps(hive_ctx *ctx, const float *d_depth, int H, int W, const flo
 int hive_icp_step(hive_ctx *ctx, int H, int W, const float K[9], const float *d_live_vertex, const float *d_live_normal, const float *d_model_vertex,
                   const float *d_model_normal, const double model_pose[16], const double est_pose[16], float dist_thresh, float cos_thresh, double *h_sums,
                   int64_t *h_pairs, uint8_t *d_pair_mask);
+/* The intensity pyramid of a live colour frame, for the photometric term below.  d_color u8 [H][W][3] (r, g, b).  Level 0 is Y / 255 in float32 with the
+ * integer luma Y = (19595 R + 38470 G + 7471 B + 32768) >> 16 (hive_jpeg_encode's); level l + 1 has hive_frame_maps' sizes (floor(H_l / 2), floor(W_l / 2))
+ * and its pixel (u, v) is ((a + b) + (c + d)) * 0.25f over the samples (2v, 2u), (2v, 2u + 1), (2v + 1, 2u), (2v + 1, 2u + 1) of level l.  The levels are
+ * packed back to back: d_gray_pyr f32 [sum H_l W_l].  1 <= levels <= 8 and the last level must not be empty.  Nothing synchronises. */
+int hive_gray_pyramid(hive_ctx *ctx, const uint8_t *d_color, int H, int W, int levels, float *d_gray_pyr);
+/* hive_icp_step with the photometric term of RGB-D odometry (Steinbruecker et al. 2011, Kerl et al. 2013; Open3D's "hybrid" odometry) beside it, in one pass
+ * and with one copy back.  h_sums (host, 56) and h_pairs (host, 2): the first 28 sums and the first count are hive_icp_step's for the same inputs, bit for
+ * bit; the second 28 and the second count are the photometric term's.  Further inputs: d_live_gray f32 [H][W], this level of hive_gray_pyramid; d_model_depth
+ * f32 [H][W] and d_model_color u8 [H][W][3], the depth and colour planes of the ray cast that gave d_model_vertex.  The model's intensity I at a pixel is
+ * Y / 255 (float32) of its colour, as above.  Per live pixel with V_z > 0 (its normal is not needed), in float64 from the float32 maps:
+ *   project    q and c = M q as in hive_icp_step; kept iff c_z > 0; pu = fx (c_x / c_z) + cx, pv = fy (c_y / c_z) + cy, not rounded
+ *   cell       x0 = floor(pu), y0 = floor(pv); kept iff 1 <= x0 <= W - 3 and 1 <= y0 <= H - 3 (so a picture with H < 4 or W < 4 has no photometric pairs);
+ *              a = pu - x0, b = pv - y0
+ *   gradients  at an integer model pixel gx = 0.5 (I(x + 1, y) - I(x - 1, y)), gy = 0.5 (I(x, y + 1) - I(x, y - 1)); the pixel is usable iff its ray-cast depth
+ *              and that of its four neighbours are > 0; kept iff the cell's corners (x0 + {0, 1}, y0 + {0, 1}) are all usable
+ *   sampling   for each of I, gx, gy with A_ji its value at (x0 + i, y0 + j): top = A00 + a (A01 - A00), bot = A10 + a (A11 - A10), value = top + b (bot - top)
+ *   occlusion  xn = x0 + (a >= 0.5), yn = y0 + (b >= 0.5); kept iff |D_m(yn, xn) - c_z| <= dist_thresh
+ *   r = I_live(u, v) - I;  g_c = ((gx fx) / c_z, (gy fy) / c_z, -(((gx fx) c_x + (gy fy) c_y) / (c_z c_z)));  g_w = R_m g_c, row r in the order
+ *   (R_m[r][0] g_c0 + R_m[r][1] g_c1) + R_m[r][2] g_c2 (R_m the rotation of model_pose);  J = [q x g_w, g_w], written out like hive_icp_step's J
+ * -J is the derivative of r by xi, as for the geometric term, so the two sets of normal equations add: A = A_geo + w^2 A_photo, b = b_geo + w^2 b_photo with
+ * w in metres per unit of intensity (the caller's; hive_amd.tracking.icp_align).  The 21 + 6 + 1 sums and the count are added in hive_icp_step's order.
+ * d_photo_mask u8 [H][W] (device, may be NULL): 1 where the live pixel was kept for this term.  Synchronises the stream (one copy of 58 numbers). */
+int hive_rgbd_icp_step(hive_ctx *ctx, int H, int W, const float K[9], const float *d_live_vertex, const float *d_live_normal, const float *d_live_gray,
+                       const float *d_model_vertex, const float *d_model_normal, const float *d_model_depth, const uint8_t *d_model_color,
+                       const double model_pose[16], const double est_pose[16], float dist_thresh, float cos_thresh, double *h_sums, int64_t *h_pairs,
+                       uint8_t *d_pair_mask, uint8_t *d_photo_mask);
 
 /* ---- scoring a render against a held-out frame -- compare_images(ref_image, est_image), scripts/compare_image_pair.py:110-133, and ms_ssim as called at
  * scripts/experiments.py:1627-1635; the loops that use them are experiments.py:775-858 (LLFF) and :1554-1637 (HyperNeRF).  Pictures are u8 [N][H][W][3] in
