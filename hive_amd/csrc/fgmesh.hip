@@ -102,47 +102,19 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const float *__restrict
                                                          unsigned *__restrict__ blk_valid, unsigned *__restrict__ blk_faces) {
     __shared__ unsigned lds[8];
     const int n = p.H * p.W;
-    unsigned cv = 0, cf = 0;
+    unsigned c[2] = {0, 0};  // valid pixels, faces
     for (int j = 0; j < TILE / 256; ++j) {
         const int i = blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
         if (i < n) {
-            cv += px_valid(depth, mask, i);
+            c[0] += px_valid(depth, mask, i);
             int tri[MAX_PIXEL_FACES][3];
-            cf += (unsigned)pixel_faces(p, depth, mask, i, tri);
+            c[1] += (unsigned)pixel_faces(p, depth, mask, i, tri);
         }
     }
-    block_sum2(cv, cf, lds);
+    block_sum(c, lds);
     if (threadIdx.x == 0) {
-        blk_valid[blockIdx.x] = cv;
-        blk_faces[blockIdx.x] = cf;
-    }
-}
-
-// exclusive scan of up to a few thousand block counts by one workgroup; totals[which] = sum
-__global__ __launch_bounds__(1024) void scan_blocks_kernel(unsigned *__restrict__ a, int nb, unsigned *total) {
-    __shared__ unsigned part[1024];
-    const int t = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    unsigned s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        unsigned r = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const unsigned v = part[i];
-            part[i] = r;
-            r += v;
-        }
-        *total = r;
-    }
-    __syncthreads();
-    unsigned r = part[t];
-    for (int i = lo; i < hi; ++i) {
-        const unsigned v = a[i];
-        a[i] = r;
-        r += v;
+        blk_valid[blockIdx.x] = c[0];
+        blk_faces[blockIdx.x] = c[1];
     }
 }
 
@@ -230,15 +202,13 @@ __device__ __forceinline__ bool face_ok(const FilterParams &p, long long f) {
 
 __global__ __launch_bounds__(256) void filter_count_kernel(FilterParams p, unsigned *__restrict__ blk) {
     __shared__ unsigned lds[4];
-    unsigned c = 0;
+    unsigned c[1] = {0};
     for (int j = 0; j < TILE / 256; ++j) {
         const long long f = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
-        if (f < p.F) c += face_ok(p, f);
+        if (f < p.F) c[0] += face_ok(p, f);
     }
-    for (int off = 32; off > 0; off >>= 1) c += (unsigned)__shfl_xor((int)c, off);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+    block_sum(c, lds);
+    if (threadIdx.x == 0) blk[blockIdx.x] = c[0];
 }
 
 __global__ __launch_bounds__(256) void filter_write_kernel(FilterParams p, const unsigned *__restrict__ blk, int32_t *__restrict__ out) {
@@ -655,7 +625,7 @@ int frame_mesh_run(hive_ctx *ctx, const FrameMeshJob &j) {
     hipStream_t st = ctx->stream;
     // 1. the triangulation + face filter of the valid pixels (hive_grid_mesh's kernels; the scan also empties the texture window's box)
     hipLaunchKernelGGL(grid_count_kernel, tiles, blk, 0, st, j.depth, j.mask, gp, s.bv, s.bf);
-    scan_blocks2(ctx, s.bv, s.bf, nb, grid_counts, d_box);
+    scan_counts_box(ctx, s.bv, s.bf, nb, grid_counts, d_box);
     hipLaunchKernelGGL(grid_vid_kernel, tiles, blk, 0, st, j.depth, j.mask, n, (const unsigned *)s.bv, s.vid);
     hipLaunchKernelGGL(grid_faces_kernel, tiles, blk, 0, st, j.depth, j.mask, gp, (const unsigned *)s.bf, (const int *)s.vid, grid_faces, grid_face_cap);
     // 2. the decimation (hive_mesh_decimate) of the grid's mesh in scratch; without the clean-up its faces are the result
@@ -772,8 +742,7 @@ int hive_grid_mesh(hive_ctx *ctx, const float *depth, const uint8_t *mask, int H
     unsigned *d_tot = ctx->d_scalars + SC_GRID_TOTALS;  // [0] = vertices, [1] = faces
     GridParams p{H, W, max_pixel_distance, (float)max_depth_distance};
     hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, p, bv, bf);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, ctx->stream, bv, nb, d_tot);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, ctx->stream, bf, nb, d_tot + 1);
+    hive_scan_counts(ctx, nb, d_tot, bv, bf);
     hipLaunchKernelGGL(grid_vid_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, n, (const unsigned *)bv, vid);
     if (capacity > 0)
         hipLaunchKernelGGL(grid_faces_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_depth, d_mask, p, (const unsigned *)bf, (const int *)vid, d_faces,
@@ -940,7 +909,7 @@ int hive_filter_faces(hive_ctx *ctx, const int32_t *points2d, const float *depth
     }
     unsigned *d_tot = ctx->d_scalars + SC_FILTER_TOTAL;
     hipLaunchKernelGGL(filter_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, blk);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, d_tot);
+    hive_scan_counts(ctx, nb, d_tot, blk);
     hipLaunchKernelGGL(filter_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)blk, d_out);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     unsigned tot = 0;

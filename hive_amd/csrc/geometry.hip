@@ -41,40 +41,11 @@ __global__ __launch_bounds__(256) void unproject_count_kernel(const float *__res
                                                               int n, unsigned *__restrict__ blk) {
     __shared__ unsigned lds[4];
     const int base = blockIdx.x * UP_TILE + threadIdx.x * UP_VPT;
-    unsigned c = 0;
+    unsigned c[1] = {0};
     for (int j = 0; j < UP_VPT; ++j)
-        if (base + j < n && px_valid(depth, mask, base + j)) ++c;
-    for (int off = 32; off > 0; off >>= 1) c += (unsigned)__shfl_xor((int)c, off);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
-}
-
-__global__ __launch_bounds__(1024) void scan1_kernel(unsigned *__restrict__ a, int nb, unsigned long long *total) {
-    __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    unsigned long long s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long r = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const unsigned long long v = part[i];
-            part[i] = r;
-            r += v;
-        }
-        *total = r;
-    }
-    __syncthreads();
-    unsigned long long r = part[t];
-    for (int i = lo; i < hi; ++i) {
-        const unsigned v = a[i];
-        a[i] = (unsigned)r;
-        r += v;
-    }
+        if (base + j < n && px_valid(depth, mask, base + j)) ++c[0];
+    block_sum(c, lds);
+    if (threadIdx.x == 0) blk[blockIdx.x] = c[0];
 }
 
 struct UnprojectParams {
@@ -606,7 +577,7 @@ int hive_unproject(hive_ctx *ctx, const float *depth, const uint8_t *mask, const
     uint8_t *d_rgba = !out_rgba ? nullptr : (mem == HIVE_MEM_HOST ? (uint8_t *)ctx->d_in + off_rgba : out_rgba);
     unsigned long long *d_total = (unsigned long long *)(ctx->d_scalars + SC_UNPROJECT_TOTAL);
     hipLaunchKernelGGL(unproject_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)d_depth, (const uint8_t *)d_mask, n, blk);
-    hipLaunchKernelGGL(scan1_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, d_total);
+    hive_scan_counts(ctx, nb, d_total, blk);
     UnprojectParams p;
     memcpy(p.Kinv, Kinv, sizeof(p.Kinv));
     memcpy(p.R, R, sizeof(p.R));

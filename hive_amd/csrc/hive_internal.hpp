@@ -260,6 +260,73 @@ __device__ __forceinline__ unsigned block_scan_chunks(unsigned count, unsigned *
     }
     return carry;
 }
+// ---- the order-preserving compactions (geometry, fgmesh, mesh_compact, merge, mcubes): count per workgroup, scan the block counts, place ----
+// The count step.  Sums of N per-thread counts over a 256-thread workgroup: the butterfly in every wave, then the four waves; the sums are in c[] of thread 0
+// alone.  `lds` holds 4 N words; no barrier behind the sum, as in block_butterfly_sum
+template <int N>
+__device__ __forceinline__ void block_sum(unsigned (&c)[N], unsigned *lds) {
+    for (int off = 32; off > 0; off >>= 1)
+        for (int k = 0; k < N; ++k) c[k] += (unsigned)__shfl_xor((int)c[k], off);
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < N; ++k) lds[4 * k + (threadIdx.x >> 6)] = c[k];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 0; k < N; ++k) c[k] = lds[4 * k] + lds[4 * k + 1] + lds[4 * k + 2] + lds[4 * k + 3];
+}
+// The scan step.  ONE workgroup of SCAN_THREADS scans (exclusive, in place) N arrays of nb block counts each; total[k] = the sum of array k.  Thread t sums
+// its run [t per, t per + per), per = ceil(nb / SCAN_THREADS), of every array; the first lane of wave k walks array k's partials serially, so the N walks run
+// side by side and two arrays cost what one costs (the walk ends behind the last thread that has a run); then every thread rewrites its runs.  Partials and
+// totals are of type Total (unsigned or unsigned long long; an offset is what fits the array's 32 bits).  The arrays must not overlap
+constexpr int SCAN_THREADS = 1024;
+template <int N, class Total>
+__device__ __forceinline__ void block_scan_counts(unsigned *const (&a)[N], int nb, Total *total) {
+    static_assert(N <= SCAN_THREADS / 64, "a wave walks each array");
+    __shared__ Total part[N][SCAN_THREADS];
+    const int t = threadIdx.x;
+    const int per = max((nb + SCAN_THREADS - 1) / SCAN_THREADS, 1);
+    const int lo = min(t * per, nb), hi = min(lo + per, nb);
+    const int used = (nb + per - 1) / per;  // threads with a run: the ones behind them add zeros and read no offset
+    Total r[N] = {};
+    for (int i = lo; i < hi; ++i) {
+        unsigned v[N];
+        for (int k = 0; k < N; ++k) v[k] = a[k][i];
+        for (int k = 0; k < N; ++k) r[k] += v[k];
+    }
+    for (int k = 0; k < N; ++k) part[k][t] = r[k];
+    __syncthreads();
+    if ((t & 63) == 0 && (t >> 6) < N) {
+        Total *p = part[t >> 6], sum = 0;
+        // over the partials of the threads with a run, in whole chunks of 32 (the loads of a chunk are issued together)
+        for (int i = 0; i < used; i += 32)
+#pragma unroll
+            for (int j = i; j < i + 32; ++j) {
+                const Total v = p[j];
+                p[j] = sum;
+                sum += v;
+            }
+        total[t >> 6] = sum;
+    }
+    __syncthreads();
+    for (int k = 0; k < N; ++k) r[k] = part[k][t];
+    for (int i = lo; i < hi; ++i) {
+        unsigned v[N];
+        for (int k = 0; k < N; ++k) v[k] = a[k][i];
+        for (int k = 0; k < N; ++k) {
+            a[k][i] = (unsigned)r[k];
+            r[k] += v[k];
+        }
+    }
+}
+// (one parameter per array: __restrict__ on each lets a run's loads pass the stores of the count before)
+template <class Total, class... Counts>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_counts_kernel(int nb, Total *total, Counts *__restrict__... a) {
+    unsigned *const arrays[] = {a...};
+    block_scan_counts(arrays, nb, total);
+}
+template <class Total, class... Counts>
+inline void hive_scan_counts(hive_ctx *ctx, int nb, Total *total, Counts *... a) {
+    hipLaunchKernelGGL((scan_counts_kernel<Total, Counts...>), dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, nb, total, a...);
+}
 // the last of n >= 1 table rows whose first element first_of(row) is not after `at` (rows ascend; row 0 starts at or before every `at` asked for)
 template <class At, class FirstOf>
 __device__ __forceinline__ int last_not_after(int n, At at, FirstOf first_of) {

@@ -128,87 +128,20 @@ __device__ __forceinline__ int cell_case(const WordClass &k, int b) {
     return cs;
 }
 
-// exclusive scan of one unsigned per thread over the 256-thread block; returns the block total in `total`
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned *lds4, unsigned &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = (unsigned)__shfl_up((int)inc, off);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) lds4[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-    total = 0;
-    for (int w = 0; w < MC_BLOCK / 64; ++w) {
-        if (w < wave) before += lds4[w];
-        total += lds4[w];
-    }
-    __syncthreads();
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(McParams p, long long n_words, unsigned *__restrict__ blk_v,
                                                             unsigned *__restrict__ blk_t) {
     __shared__ unsigned lds[8];
     const long long w = (long long)blockIdx.x * MC_BLOCK + threadIdx.x;
-    unsigned nv = 0, nt = 0;
+    unsigned c[2] = {0, 0};  // vertices, triangles
     if (w < n_words) {
         const WordClass k = classify_word(p, w, true);
-        nv = __popc(k.xe) + __popc(k.ye) + __popc(k.ze);
-        for (unsigned m = k.act; m; m &= m - 1u) nt += c_num_tris[cell_case(k, __ffs((int)m) - 1)];
+        c[0] = __popc(k.xe) + __popc(k.ye) + __popc(k.ze);
+        for (unsigned m = k.act; m; m &= m - 1u) c[1] += c_num_tris[cell_case(k, __ffs((int)m) - 1)];
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        nv += (unsigned)__shfl_xor((int)nv, off);
-        nt += (unsigned)__shfl_xor((int)nt, off);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        lds[wave] = nv;
-        lds[4 + wave] = nt;
-    }
-    __syncthreads();
+    block_sum(c, lds);
     if (threadIdx.x == 0) {
-        blk_v[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
-        blk_t[blockIdx.x] = lds[4] + lds[5] + lds[6] + lds[7];
-    }
-}
-
-// exclusive scan of two arrays of nb counts in place; totals (u64) to totals[0], totals[1]
-__global__ __launch_bounds__(1024) void mc_scan_kernel(unsigned *__restrict__ a, unsigned *__restrict__ b, int nb,
-                                                       unsigned long long *totals) {
-    __shared__ unsigned long long part[2][1024];
-    const int t = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    unsigned long long sa = 0, sb = 0;
-    for (int i = lo; i < hi; ++i) {
-        sa += a[i];
-        sb += b[i];
-    }
-    part[0][t] = sa;
-    part[1][t] = sb;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long ra = 0, rb = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const unsigned long long ta = part[0][i], tb = part[1][i];
-            part[0][i] = ra;
-            part[1][i] = rb;
-            ra += ta;
-            rb += tb;
-        }
-        totals[0] = ra;
-        totals[1] = rb;
-    }
-    __syncthreads();
-    unsigned long long ra = part[0][t], rb = part[1][t];
-    for (int i = lo; i < hi; ++i) {
-        const unsigned va = a[i], vb = b[i];
-        a[i] = (unsigned)ra;
-        b[i] = (unsigned)rb;
-        ra += va;
-        rb += vb;
+        blk_v[blockIdx.x] = c[0];
+        blk_t[blockIdx.x] = c[1];
     }
 }
 
@@ -235,7 +168,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_verts_kernel(McParams p, long lon
     if (w < n_words) k = classify_word(p, w, false);
     const unsigned cnt = __popc(k.xe) + __popc(k.ye) + __popc(k.ze);
     unsigned total;
-    unsigned id = blk_v[blockIdx.x] + block_exclusive_scan(cnt, lds, total);
+    unsigned id = blk_v[blockIdx.x] + block_exclusive_total(cnt, lds, &total);
     for (unsigned m = k.xe | k.ye | k.ze; m; m &= m - 1u) {  // voxels in ascending z, axes in x, y, z order
         const int b = __ffs((int)m) - 1;
         const unsigned mask = ((k.xe >> b) & 1u) | (((k.ye >> b) & 1u) << 1) | (((k.ze >> b) & 1u) << 2);
@@ -287,7 +220,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_faces_kernel(McParams p, long lon
     unsigned cnt = 0;
     for (unsigned m = k.act; m; m &= m - 1u) cnt += c_num_tris[cell_case(k, __ffs((int)m) - 1)];
     unsigned total;
-    unsigned long long fid = blk_t[blockIdx.x] + block_exclusive_scan(cnt, lds, total);
+    unsigned long long fid = blk_t[blockIdx.x] + block_exclusive_total(cnt, lds, &total);
     for (unsigned m = k.act; m; m &= m - 1u) {  // cells in ascending z
         const int b = __ffs((int)m) - 1;
         const int cs = cell_case(k, b);
@@ -388,7 +321,7 @@ int hive_tsdf_extract_mesh(hive_tsdf *v, int64_t *n_verts, int64_t *n_faces) {
     unsigned *blk_v = v->d_blk, *blk_t = v->d_blk + nb;
     unsigned long long *d_tot = (unsigned long long *)(ctx->d_scalars + SC_MC_TOTALS);
     hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nb), dim3(MC_BLOCK), 0, ctx->stream, p, n_words, blk_v, blk_t);
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk_v, blk_t, (int)nb, d_tot);
+    hive_scan_counts(ctx, (int)nb, d_tot, blk_v, blk_t);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     // the ONE read-back of an extraction: vertex and face totals, through pinned memory (a copy into pageable memory is staged by the runtime)
     void *pinned;

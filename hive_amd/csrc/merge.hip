@@ -52,39 +52,11 @@ constexpr int SL_TILE = 256 * SL_VPT;  // flags per workgroup; a thread takes SL
 __global__ __launch_bounds__(256) void segment_count_kernel(const uint8_t *__restrict__ flags, long long n_segments, unsigned *__restrict__ blk) {
     __shared__ unsigned lds[4];
     const long long base = (long long)blockIdx.x * SL_TILE + threadIdx.x * SL_VPT;
-    unsigned c = 0;
+    unsigned c[1] = {0};
     for (int j = 0; j < SL_VPT; ++j)
-        if (base + j < n_segments && flags[base + j]) ++c;
-    const unsigned before = block_exclusive(c, lds);
-    if (threadIdx.x == 255) blk[blockIdx.x] = before + c;
-}
-
-// exclusive scan of the nb block counts in place by ONE workgroup (any nb: every thread scans a contiguous run); the total as i64
-__global__ __launch_bounds__(1024) void segment_scan_kernel(unsigned *__restrict__ a, int nb, long long *total) {
-    __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    unsigned long long s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long r = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const unsigned long long v = part[i];
-            part[i] = r;
-            r += v;
-        }
-        *total = (long long)r;
-    }
-    __syncthreads();
-    unsigned long long r = part[t];
-    for (int i = lo; i < hi; ++i) {
-        const unsigned v = a[i];
-        a[i] = (unsigned)r;
-        r += v;
-    }
+        if (base + j < n_segments && flags[base + j]) ++c[0];
+    block_sum(c, lds);
+    if (threadIdx.x == 0) blk[blockIdx.x] = c[0];
 }
 
 __global__ __launch_bounds__(256) void segment_write_kernel(const uint8_t *__restrict__ flags, long long n_segments, const unsigned *__restrict__ blk,
@@ -233,7 +205,7 @@ int hive_segment_list(hive_ctx *ctx, const uint8_t *d_flags, int64_t n_segments,
     if (rc) return rc;
     unsigned *blk = (unsigned *)ctx->d_scratch;
     hipLaunchKernelGGL(segment_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_flags, (long long)n_segments, blk);
-    hipLaunchKernelGGL(segment_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, (long long *)d_count);
+    hive_scan_counts(ctx, nb, (unsigned long long *)d_count, blk);  // (the total is below 2^31: the same bits as i64)
     hipLaunchKernelGGL(segment_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_flags, (long long)n_segments, (const unsigned *)blk, d_list);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;

@@ -1,5 +1,6 @@
 // Order-preserving compaction of a mesh on the device, shared by the clean-up (fgmesh.hip) and the decimation (decimate.hip): the kept vertices get
-// consecutive rows in input order, the kept faces follow in input order and index those rows.  Four launches: count, scan, vertex map, faces.
+// consecutive rows in input order, the kept faces follow in input order and index those rows.  Four launches: count, scan, vertex map, faces; the scan is
+// block_scan_counts of hive_internal.hpp, the one scan of every compaction.
 //
 // The params struct P says what is kept:
 //   nv(), nf()            vertices / faces of the input (device counts, bounded by the capacities the scratch was laid out for)
@@ -16,59 +17,16 @@ namespace {
 
 constexpr int TILE = 1024;  // items per workgroup of 256 (4 consecutive items per thread keep the input order)
 
-// sums of two per-thread counts over a workgroup of 256; the sums are in (a, b) of thread 0 on return (lds: 8 words)
-__device__ __forceinline__ void block_sum2(unsigned &a, unsigned &b, unsigned *lds) {
-    for (int off = 32; off > 0; off >>= 1) {
-        a += (unsigned)__shfl_xor((int)a, off);
-        b += (unsigned)__shfl_xor((int)b, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        lds[threadIdx.x >> 6] = a;
-        lds[4 + (threadIdx.x >> 6)] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = lds[0] + lds[1] + lds[2] + lds[3];
-        b = lds[4] + lds[5] + lds[6] + lds[7];
-    }
+// scan_counts_kernel of the two block-count arrays (totals[0..1] = their sums), and box = the texture window's empty box (INT_MAX, INT_MAX, INT_MIN,
+// INT_MIN) for the atomics of window_project_kernel (no host-to-device copy in the call)
+__global__ __launch_bounds__(SCAN_THREADS) void scan_counts_box_kernel(unsigned *__restrict__ a, unsigned *__restrict__ b, int nb, unsigned *totals, int *box) {
+    unsigned *const arrays[] = {a, b};
+    block_scan_counts(arrays, nb, totals);
+    if (threadIdx.x < 4) box[threadIdx.x] = threadIdx.x < 2 ? 0x7fffffff : (int)0x80000000;
 }
 
-// both block-count arrays scanned (exclusive) by ONE workgroup (threads 0..511: a, 512..1023: b), totals[0..1] = their sums, and bbox = the texture
-// window's empty box (INT_MAX, INT_MAX, INT_MIN, INT_MIN) for the atomics of window_project_kernel (no host-to-device copy in the call)
-__global__ __launch_bounds__(1024) void scan_blocks2_kernel(unsigned *__restrict__ a, unsigned *__restrict__ b, int nb, unsigned *totals, int *bbox) {
-    __shared__ unsigned part[1024];
-    const int half = threadIdx.x >> 9, t = threadIdx.x & 511;
-    unsigned *arr = half ? b : a;
-    const int per = (nb + 511) / 512;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    unsigned s = 0;
-    for (int i = lo; i < hi; ++i) s += arr[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (t == 0) {
-        unsigned r = 0;
-        for (int i = 0; i < 512; ++i) {
-            const unsigned v = part[half * 512 + i];
-            part[half * 512 + i] = r;
-            r += v;
-        }
-        totals[half] = r;
-    }
-    if (threadIdx.x == 1) {
-        bbox[0] = bbox[1] = 0x7fffffff;
-        bbox[2] = bbox[3] = (int)0x80000000;
-    }
-    __syncthreads();
-    unsigned r = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) {
-        const unsigned v = arr[i];
-        arr[i] = r;
-        r += v;
-    }
-}
-
-inline void scan_blocks2(hive_ctx *ctx, unsigned *a, unsigned *b, int nb, unsigned *totals, int *bbox) {
-    hipLaunchKernelGGL(scan_blocks2_kernel, dim3(1), dim3(1024), 0, ctx->stream, a, b, nb, totals, bbox);
+inline void scan_counts_box(hive_ctx *ctx, unsigned *a, unsigned *b, int nb, unsigned *totals, int *box) {
+    hipLaunchKernelGGL(scan_counts_box_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, a, b, nb, totals, box);
 }
 
 // per block of TILE: kept vertices -> bv, kept faces -> bf (both arrays cover max(face blocks, vertex blocks))
@@ -76,16 +34,16 @@ template <class P>
 __global__ __launch_bounds__(256) void compact_count_kernel(P p, unsigned *__restrict__ bv, unsigned *__restrict__ bf) {
     __shared__ unsigned lds[8];
     const long long nf = p.nf(), nv = p.nv();
-    unsigned cv = 0, cf = 0;
+    unsigned c[2] = {0, 0};  // kept vertices, kept faces
     for (int j = 0; j < TILE / 256; ++j) {
         const long long i = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
-        if (i < nf) cf += p.keep_face(i);
-        if (i < nv) cv += p.keep_vertex(i);
+        if (i < nf) c[1] += p.keep_face(i);
+        if (i < nv) c[0] += p.keep_vertex(i);
     }
-    block_sum2(cv, cf, lds);
+    block_sum(c, lds);
     if (threadIdx.x == 0) {
-        bv[blockIdx.x] = cv;
-        bf[blockIdx.x] = cf;
+        bv[blockIdx.x] = c[0];
+        bf[blockIdx.x] = c[1];
     }
 }
 
@@ -142,7 +100,7 @@ template <class P>
 void launch_compaction(hive_ctx *ctx, const P &p, unsigned *bv, unsigned *bf, int nb, unsigned *out_counts, int *box, int32_t *out_faces, long long out_cap,
                        int32_t *out_vertex_index) {
     hipLaunchKernelGGL(compact_count_kernel<P>, dim3(nb), dim3(256), 0, ctx->stream, p, bv, bf);
-    scan_blocks2(ctx, bv, bf, nb, out_counts, box);
+    scan_counts_box(ctx, bv, bf, nb, out_counts, box);
     hipLaunchKernelGGL(compact_vmap_kernel<P>, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)bv, out_vertex_index);
     hipLaunchKernelGGL(compact_faces_kernel<P>, dim3(nb), dim3(256), 0, ctx->stream, p, (const unsigned *)bf, out_faces, out_cap);
 }

@@ -418,3 +418,71 @@ def test_frame_mesh_buffers_too_small(gpu_ctx, variant):
     assert err.value.code == _lib.ERR_INVALID and "do not fit" in str(err.value), str(err.value)
     torch.cuda.synchronize()
     assert bool((big.vertices[cap:] == -7.0).all()) and bool((big.faces[cap:] == -7).all()) and bool((big.uv[cap:] == -7).all())
+
+
+# ---- more than 1024 block counts: every thread of the one scan workgroup takes a run of two, and the last run is ragged (tests/test_fgmesh_cases_cpu.py) ----
+@pytest.fixture(scope="module")
+def long_grid(gpu_ctx):
+    """The 1025 x 1025 picture of fgmesh_cases, its unfiltered grid mesh from hive_grid_mesh in device memory, and the rule's face list; computed once."""
+    import torch
+    import fgmesh_cases as fc
+    from hive_amd import foreground
+    from hive_amd.options import MeshFilteringOptions
+    depth, mask = fc.banded_scene(fc.GRID_SIZE, fc.GRID_ROW_BAND, fc.GRID_COL_BAND, fc.GRID_STEP_COLUMN)
+    opts = MeshFilteringOptions(max_pixel_distance=fc.PASS_ALL_LIMITS[0], max_depth_distance=fc.PASS_ALL_LIMITS[1])
+    got, n_vert = foreground.grid_faces(torch.from_numpy(depth).cuda(), torch.from_numpy(mask).cuda(), opts, ctx=gpu_ctx, return_vertex_count=True)
+    valid = mask & (depth > 0)
+    return {"depth": depth, "valid": valid, "got": got.cpu().numpy(), "n_vert": n_vert, "want": fc.full_block_faces(valid)}
+
+
+def test_grid_mesh_scans_more_than_1024_tiles(long_grid):
+    """hive_grid_mesh (device memory) at 1025 x 1025: 1027 pixel tiles, two per scan thread, one pixel in the last.  Vertices and the face LIST against the
+    implicit rule where only fully valid 2 x 2 blocks give faces, vectorised -- which is the loop restatement of this file at a small picture with the same bands."""
+    import fgmesh_cases as fc
+    depth, mask = fc.banded_scene(fc.SMALL_SIZE, fc.SMALL_ROW_BAND, fc.SMALL_COL_BAND, fc.SMALL_STEP_COLUMN)
+    loops, valid = _numpy_grid_faces(depth, mask)
+    assert np.array_equal(fc.full_block_faces(valid), loops) and len(loops) == 2 * (22 - 3) * (30 - 4)
+    got, want = long_grid["got"], long_grid["want"]
+    print(got.shape, want.shape, long_grid["n_vert"], int(long_grid["valid"].sum()))
+    assert long_grid["n_vert"] == int(long_grid["valid"].sum()) == 1022 * 1023
+    assert got.dtype == np.int32 and got.shape == want.shape == (2 * 1020 * 1021, 3)
+    assert np.array_equal(got, want)
+    assert want.max() == long_grid["n_vert"] - 1, "the last tile's one pixel is the last vertex, and a face reaches it"
+
+
+def test_filter_faces_scans_more_than_1024_tiles(gpu_ctx, long_grid):
+    """hive_filter_faces on that face list (2035 tiles, the last of 24 faces) with limits that drop every face across the depth step: the reference's
+    filter in numpy, face for face."""
+    import fgmesh_cases as fc
+    from hive_amd import foreground
+    from hive_amd.options import MeshFilteringOptions
+    valid, faces = long_grid["valid"], long_grid["want"]
+    vv, uu = valid.nonzero()
+    points2d = np.vstack((uu, vv)).T
+    d = long_grid["depth"][valid]
+    expect = _numpy_filter_faces(points2d, d, faces, *fc.STEP_LIMITS)
+    got = foreground.filter_faces(points2d, d, faces, MeshFilteringOptions(max_pixel_distance=fc.STEP_LIMITS[0], max_depth_distance=fc.STEP_LIMITS[1]), ctx=gpu_ctx)
+    print(got.shape, expect.shape, faces.shape)
+    assert len(expect) == len(faces) - 2 * 1020, "the two faces of the block left of the step, in every row of blocks"
+    assert got.shape == expect.shape and np.array_equal(got, expect)
+
+
+def test_mesh_compaction_scans_more_than_1024_tiles(gpu_ctx):
+    """The compaction of mesh_compact.hpp through hive_mesh_cleanup_cc (device memory): 1 051 170 faces (1027 tiles) over 527 076 vertices (515 tiles), a
+    component of 18 faces in the middle of the list below the size limit and 20 unreferenced vertices around it -- against the numpy + scipy restatement
+    of tests/test_fgclean_gpu.py."""
+    import torch
+    import fgmesh_cases as fc
+    from hive_amd import foreground
+    from test_fgclean_gpu import reference_cleanup
+    valid = fc.cleanup_valid()
+    n_vertices = valid.size
+    faces = fc.full_block_faces(valid, pixel_ids=True)
+    vertices = torch.arange(3 * n_vertices, dtype=torch.float64, device="cuda").reshape(n_vertices, 3)  # row i = (3 i, 3 i + 1, 3 i + 2): names its input id
+    want_vi, want_f = reference_cleanup(n_vertices, faces, False, fc.CLEANUP_MIN_FACES)
+    got_v, got_f = foreground.cleanup_with_connected_components(vertices, torch.from_numpy(faces).cuda(), False, fc.CLEANUP_MIN_FACES, ctx=gpu_ctx)
+    got_vi, got_f = (got_v[:, 0] / 3).long().cpu().numpy(), got_f.cpu().numpy()
+    print(got_f.shape, want_f.shape, got_vi.shape, want_vi.shape)
+    assert len(want_f) == len(faces) - 18 and len(want_vi) == n_vertices - 20, "the patch's faces go; its vertices stay (an input face references them)"
+    assert got_f.shape == want_f.shape and np.array_equal(got_f, want_f)
+    assert got_vi.shape == want_vi.shape and np.array_equal(got_vi, want_vi)

@@ -9,7 +9,7 @@ import tracking_restatement as tr
 
 UP_TILE = 1024        # unproject_count_kernel / unproject_write_kernel: pixels per workgroup (256 threads x UP_VPT)
 UP_VPT = 4            # the same kernels: consecutive pixels per thread
-SCAN_THREADS = 1024   # scan1_kernel: one workgroup of 1024 threads, thread t scans blocks [t per, t per + per)
+SCAN_THREADS = 1024   # scan_counts_kernel: one workgroup of 1024 threads, thread t scans blocks [t per, t per + per)
 LANES = 256           # max_depth_batch_kernel, depth_quantize_kernel, project_kernel, image2world_kernel: threads per workgroup
 WAVE = 64             # max_depth_batch_kernel: the shuffle reduction is per wave of 64
 FRUSTUM_GROUPS = 1024       # hive_view_frustum: at most 1024 workgroups for one frame

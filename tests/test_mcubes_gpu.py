@@ -374,7 +374,7 @@ def test_both_sign_kernels(gpu_ctx, oracle_lib, dims, field):
 
 @pytest.mark.parametrize("dims,field", [((300, 301, 70), "random"), ((257, 257, 257), "torus")], ids=["300x301x70", "257cubed"])
 def test_multi_chunk_block_scan(gpu_ctx, oracle_lib, dims, field):
-    """mc_scan_kernel gives each of its 1024 threads ceil(nb / 1024) block counts; here nb > 1024 and the last chunk is ragged."""
+    """scan_counts_kernel gives each of its 1024 threads ceil(nb / 1024) block counts; here nb > 1024 and the last chunk is ragged."""
     X, Y, Z = dims
     nb = (X * Y * ((Z + 31) // 32) + MC_BLOCK - 1) // MC_BLOCK
     assert nb > 1024 and nb % 1024 != 0 and nb == {"random": 1059, "torus": 2323}[field]

@@ -103,7 +103,7 @@ obj_d = torch.from_numpy((obj > 0).astype(np.uint8)).cuda()
 ms, (faces, nvert) = timed(lambda: foreground.grid_faces(d0, obj_d, ctx=ctx, return_vertex_count=True))
 b = 5.0 * H * W + 12.0 * faces.shape[0]
 res["grid_mesh_vga"] = {"ms": ms, "faces": int(faces.shape[0]), "vertices": int(nvert), "algorithmic_bytes": b, "gbs": b / ms / 1e6, "bytes_formula": "5 H W + 12 F",
-                        "note": "sizing call + fill call, 5 launches each, 2 read-backs: latency-bound"}
+                        "note": "sizing call (3 launches) + fill call (4 launches), 2 read-backs: latency-bound"}
 
 # depth_apply_mask over the frame set: (4 + 1) H W in, 4 H W out per frame
 masks = torch.from_numpy(synthetic.ellipse_masks(args.frames, H, W)).cuda()
