@@ -444,12 +444,20 @@ class PipelineOptions(Options):
                     ('png', 'jpeg')),
               _Flag('jpeg_quality', 'jpeg_quality', int, 90, 'quality (1 .. 100) of --texture_format jpeg'),
               _Flag('png_encoder', 'png_encoder', str, 'host', 'who compresses the PNG files of depth estimation, frame inpainting and --texture_format png: host (Pillow / zlib) '
-                    'or gpu (the same pixels, the device encoder\'s bytes)', ('host', 'gpu')))
+                    'or gpu (the same pixels, the device encoder\'s bytes)', ('host', 'gpu')),
+              _Flag('texture_background', 'texture_background', bool, False, 'with --export_gltf: texture the background mesh of bg.glb from the key frames (an atlas) '
+                    'instead of writing the volume\'s vertex colours'),
+              _Flag('texture_cell', 'texture_cell', int, 8, 'texels on a side of an atlas block (two faces) of --texture_background, 6 .. 64'),
+              _Flag('texture_max_views', 'texture_max_views', int, 32, 'at most this many key frames texture the background (every ceil(k / max)-th is kept)'))
 
     def __init__(self, num_frames=-1, frame_step=15, estimate_pose=False, estimate_depth=False, background_only=False, static_camera=False,
                  align_scene=False, inpainting_mode=InpaintingMode.Off, billboard=False, disable_scaling=False, disable_coverage_constraint=False,
-                 log_file='logs.log', export_gltf=False, texture_format='png', jpeg_quality=90, png_encoder='host'):
+                 log_file='logs.log', export_gltf=False, texture_format='png', jpeg_quality=90, png_encoder='host', texture_background=False, texture_cell=8,
+                 texture_max_views=32):
         self.export_gltf = export_gltf
+        self.texture_background = texture_background
+        self.texture_cell = texture_cell
+        self.texture_max_views = texture_max_views
         self.texture_format = texture_format
         self.jpeg_quality = jpeg_quality
         self.png_encoder = png_encoder

@@ -189,18 +189,47 @@ class Pipeline:
         K = np.asarray(dataset.camera_matrix)
         return gltf.Scene(camera=dict(resolution=(dataset.frame_width, dataset.frame_height), focal=(float(K[0, 0]), float(K[1, 1]))))
 
-    def _create_background_scene(self, dataset: HiveDataset, static_mesh=None):
+    def _create_background_scene(self, dataset: HiveDataset, static_mesh=None, num_frames: Optional[int] = None):
         """pipeline.py:258-286 for TSDFFusion: the static mesh under the node ``000000``.  Where the reference rewrites the vertex colours with
         ``(255 * (c / 255) ** 2.2).astype(int)`` (:281-282) the mesh stays as it is and the same table is returned as the ``lut`` the packer applies on the
-        device.  Returns (scene, lut)."""
+        device.  Returns (scene, lut).  With ``options.texture_background`` the node is the mesh textured from the key frames (``_texture_background``) and
+        there is no ``lut``: the 2.2-power table is for vertex colours, frames go in as they are, as the foreground's do."""
         if self.background_mesh_options.reconstruction_method != MeshReconstructionMethod.TSDFFusion:
             raise NotImplementedError(f"{self.background_mesh_options.reconstruction_method.name}: only TSDFFusion is part of the dense-compute path")
         scene = self._create_empty_scene(dataset)
+        n = self.num_frames if num_frames is None else num_frames
         if static_mesh is None:
-            static_mesh = self.create_static_mesh(dataset, num_frames=self.num_frames, options=self.background_mesh_options)
+            static_mesh = self.create_static_mesh(dataset, num_frames=n, options=self.background_mesh_options)
+        if self.options.texture_background:
+            scene.add_geometry(self._texture_background(dataset, static_mesh, n), node_name="000000")
+            return scene, None
         lut = (255 * np.power(np.arange(256) / 255, 2.2)).astype(np.uint8)
         scene.add_geometry(static_mesh, node_name="000000")
         return scene, lut
+
+    def _texture_background(self, dataset: HiveDataset, static_mesh, num_frames: int) -> dict:
+        """The static mesh with an atlas (``texturing.texture_mesh``) from the key frames the fusion used (``create_static_mesh``'s set; beyond
+        ``options.texture_max_views`` every ceil(k / max)-th of them): the stored frames as they are (not the inpainted ones), without the pixels of the stored
+        instance masks (non-zero), dilated with the run's ``MaskDilationOptions`` as the foreground's are.  ``profiling['background_texturing']`` gets the
+        counts."""
+        from hive_amd import texturing
+        from hive_amd.image_processing import dilate_mask
+        if num_frames is None or num_frames < 1:
+            num_frames = dataset.num_frames
+        options = self.background_mesh_options
+        frame_set = [f for f in dataset.select_key_frames(threshold=options.key_frame_threshold, frame_step=options.key_frame_step) if f < num_frames]
+        step = -(-len(frame_set) // max(1, int(self.options.texture_max_views)))
+        frame_set = frame_set[::max(1, step)]
+        with timed_block("Textured the background mesh in", self.profiling, ("timing", "background_reconstruction", "texturing")):
+            frames = np.stack([np.asarray(dataset.rgb_dataset[i])[:, :, :3] for i in frame_set])
+            masks = np.stack([dilate_mask(np.asarray(dataset.mask_dataset[i]) != 0, self.dilation_options) for i in frame_set])
+            poses = np.asarray(dataset.camera_trajectory.to_homogenous_transforms(), np.float64)[frame_set]
+            mesh = texturing.texture_mesh(static_mesh, frames, np.asarray(dataset.camera_matrix), poses, masks=masks, cell=self.options.texture_cell,
+                                          return_views=True)
+        views = mesh.pop("views")
+        self.profiling["background_texturing"] = {"key_frames": [int(f) for f in frame_set], "faces": int(views.shape[0]), "faces_with_a_view": int((views >= 0).sum()),
+                                                  "atlas": [int(mesh["texture"].shape[1]), int(mesh["texture"].shape[0])]}
+        return mesh
 
     def _create_foreground_scene(self, dataset: HiveDataset, num_frames: Optional[int] = None, folder: Optional[str] = None) -> gltf.Scene:
         """pipeline.py:288-307: an empty scene for ``background_only``, else every frame's mesh (``create_foreground_meshes``, which smooths the trajectory
@@ -281,11 +310,12 @@ class Pipeline:
         return Path(dataset.base_path).name
 
     def _get_webxr_metadata(self, dataset: HiveDataset, num_frames: Optional[int] = None) -> dict:
-        """pipeline.py:1111-1125: the six keys of the player's metadata.json."""
+        """pipeline.py:1111-1125: the six keys of the player's metadata.json (a textured background, ``options.texture_background``, is not vertex-coloured)."""
         fy = float(np.asarray(dataset.camera_matrix)[1, 1])
         fov_y = float(np.rad2deg(2 * np.arctan2(dataset.frame_height, 2 * fy)))  # io.py:1025-1027
         return dict(fps=dataset.fps, fov_y=int(fov_y), num_frames=self.num_frames if num_frames is None else num_frames,
-                    use_vertex_colour_for_bg=self.background_mesh_options.reconstruction_method != MeshReconstructionMethod.RGBD,
+                    use_vertex_colour_for_bg=self.background_mesh_options.reconstruction_method != MeshReconstructionMethod.RGBD and
+                    not self.options.texture_background,
                     add_ground_plane=self.webxr_options.webxr_add_ground_plane, add_sky_box=self.webxr_options.webxr_add_sky_box)
 
     def _export_video_webxr(self, mesh_path: str, fg_scene_name: str, bg_scene_name: str, metadata: dict, export_name: str) -> str:
@@ -352,7 +382,7 @@ class Pipeline:
         """The reference's last four stages (pipeline.py:213-237) under its timing keys (``mesh_export`` is the sum of the PLY and the glTF writing)."""
         if self.storage_options is None:
             self.storage_options = StorageOptions(dataset_path=dataset.base_path, output_path=os.path.dirname(mesh_path))
-        background_scene, lut = self._create_background_scene(dataset, static_mesh)
+        background_scene, lut = self._create_background_scene(dataset, static_mesh, num_frames)
         with timed_block("Centred the scenes in", self.profiling, ("timing", "scene_centering")):
             foreground_scene, background_scene = self._center_scenes(dataset, foreground_scene, background_scene)
         ply_seconds = self.profiling.get("timing", {}).get("mesh_export", 0.0)

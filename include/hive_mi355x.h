@@ -583,6 +583,47 @@ int hive_render_shade(hive_ctx *ctx, int64_t nv, const int32_t *d_faces, int64_t
  * where empty (an index of 2^31 or more does not fit: keep the total below 2^31 when the face plane is wanted). */
 int hive_render_resolve(hive_ctx *ctx, const uint64_t *d_key, int H, int W, const uint8_t background[3], uint8_t *d_color, float *d_depth, int32_t *d_face);
 
+/* ---- texturing a mesh from posed frames (no counterpart in the reference, whose background mesh keeps the volume's vertex colours: pipeline.py:258-286).  Per
+ * face the ONE view that sees it best, an atlas with two faces per block, one gather per texel.  The rules (float64, no fused multiply-add, in the order written):
+ *   select     once per view, after that view's hive_render_clear / hive_render_draw / hive_render_resolve(depth), on the d_xy and d_z the draw filled (the snap
+ *              and the projection are the rasteriser's).  Face f is a candidate iff its three vertices were kept (d_z > 0), its snapped area A (as above) is
+ *              not 0, and for every vertex k the nearest pixel (i, j) = ((Y_k + 128) >> 8, (X_k + 128) >> 8) (arithmetic shifts) lies on the screen, has
+ *              mask[i][j] == 0, and has depth[i][j] == 0 || z_k <= (double)depth[i][j] + depth_tolerance (a pixel nothing covers hides nothing).
+ *              key = |A| << 16 | (65535 - view_index); d_best[f] = max(d_best[f], key): the largest exact snapped area -- the nearest, least oblique view --,
+ *              on equal area the lower view index, whatever the order of the calls; 0 = no view.  (|A| < 2^47: the vertices lie within half a pixel of a screen
+ *              with (H + 1)(W + 1) <= 2^31.)  LIMITATION: there is no back-face test; a face seen from behind through nothing nearer is a candidate.
+ *   layout     faces 2k and 2k + 1 share block k of S x S texels, S = cell in [6, 64].  blocks = ceil(nf / 2), per_row = ceil(sqrt(blocks)),
+ *              Wt = per_row S, Ht = ceil(blocks / per_row) S (neither above 16384); block k at column (k % per_row) S, row (k / per_row) S.  Texel (x, y) of a
+ *              block belongs to the even face iff x + y <= S - 1, else to the odd one.  Corner texels: even (1, 1), (S - 4, 1), (1, S - 4); odd (S - 2, S - 2),
+ *              (3, S - 2), (S - 2, 3).  The hypotenuses x + y = S - 3 and x + y = S + 1 keep a bilinear fetch inside either triangle on its owner's texels.
+ *   unweld     vertices' [3 f + k] = vertex k of face f, faces' [f] = (3 f, 3 f + 1, 3 f + 2), uv at the corner texel (col, row) of the atlas:
+ *              u = (double)col / Wt, v = 1.0 - (double)row / Ht (hive_render_shade's nearest-texel rule lands on that texel).
+ *   fill       texel (x, y) of a block, owner f: even b1 = (x - 1) / (S - 5), b2 = (y - 1) / (S - 5); odd b1 = (S - 2 - x) / (S - 5), b2 = (S - 2 - y) / (S - 5);
+ *              b0 = (1 - b1) - b2 (the gutter extrapolates the same map).  With a view: P_r = (b0 V0_r + b1 V1_r) + b2 V2_r; cam and c in hive_project's order
+ *              (above, "vertex") with the view's R, t; when !(c_2 >= near) -- only a gutter point can be -- P is replaced by V0, which the draw kept.  Sample
+ *              point u = min(max(c_0 / c_2, 0), W - 1), v = min(max(c_1 / c_2, 0), H - 1) (pixel centres at integers; this clamps the four taps to the image);
+ *              j0 = floor(u), i0 = floor(v), j1 = min(j0 + 1, W - 1), i1 = min(i0 + 1, H - 1), ax = u - j0, ay = v - i0; per channel
+ *              top = c00 + ax (c01 - c00), bottom = c10 + ax (c11 - c10), c = top + ay (bottom - top); texel = (uint8)min(255, max(0, floor(c + 0.5))).
+ *              Without a view: c = (b0 a0 + b1 a1) + b2 a2 of the three vertex colours, the same rounding.  Texels whose owner is >= nf are 0.
+ * All pointers named d_ are device memory; K is a host array.  Nothing synchronises. */
+/* One view's vote.  d_faces i32 [nf][3] with ids in [0, nv) (a face with another id is skipped), d_xy i32 [nv][2] and d_z f64 [nv] of that view's hive_render_draw,
+ * d_depth f32 [H][W] of its hive_render_resolve, d_mask u8 [H][W] (may be NULL: nothing masked; non-zero = do not use), 0 <= view_index < 65535,
+ * depth_tolerance >= 0, d_best u64 [nf] in / out (zeroed by the caller before the first view). */
+int hive_texture_select(hive_ctx *ctx, const int32_t *d_faces, int64_t nf, int64_t nv, const int32_t *d_xy, const double *d_z, const float *d_depth,
+                        const uint8_t *d_mask, int H, int W, int view_index, double depth_tolerance, uint64_t *d_best);
+/* The atlas of nf faces (host arithmetic, no launch, no context): *Wt, *Ht, *per_row (each may be NULL).  HIVE_ERR_INVALID: nf outside [1, 2^31), cell outside
+ * [6, 64], a side above 16384. */
+int hive_texture_layout(int64_t nf, int cell, int *Wt, int *Ht, int *per_row);
+/* d_vertices f64 [nv][3], d_faces i32 [nf][3] -> d_vertices_out f64 [3 nf][3], d_faces_out i32 [nf][3], d_uv f64 [3 nf][2]; with d_views i32 [nf] (may be NULL)
+ * also the winning view of d_best u64 [nf] (may be NULL), 65535 - (key & 65535), or -1 for none.  3 nf < 2^31. */
+int hive_texture_unweld(hive_ctx *ctx, const double *d_vertices, int64_t nv, const int32_t *d_faces, int64_t nf, int cell, const uint64_t *d_best,
+                        double *d_vertices_out, int32_t *d_faces_out, double *d_uv, int32_t *d_views);
+/* The atlas d_texture u8 [Ht][Wt][3] of hive_texture_layout(nf, cell): the welded mesh (d_vertices, d_vertex_colors u8 [nv][3], d_faces), d_best of the selects,
+ * the n <= 65535 frames d_frames u8 [n][H][W][3], K and d_poses f64 [n][12] = per view R row-major then t (world-to-camera).  A key naming a view >= n counts as
+ * no view.  near > 0. */
+int hive_texture_fill(hive_ctx *ctx, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf, const uint64_t *d_best,
+                      const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell, uint8_t *d_texture);
+
 /* ---- ray casting the volume and tracking the camera against it (KinectFusion-style frame-to-model ICP; no counterpart in the reference, which takes its
  * poses from COLMAP or BundleFusion).  Float32 where stated, every operation rounded once (no fused multiply-add), in the order written here; pixel (u, v) =
  * (column, row), pixel centres at integers.
