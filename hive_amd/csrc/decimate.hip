@@ -74,13 +74,6 @@ __device__ __forceinline__ bool dec_applying(const DecParams &p) {
     return !sc[1] && !sc[2];
 }
 
-__device__ __forceinline__ unsigned mix32(unsigned x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    return x ^ (x >> 16);
-}
 __device__ __forceinline__ unsigned cost_bits(double cost) {
     const unsigned b = __float_as_uint((float)cost);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);

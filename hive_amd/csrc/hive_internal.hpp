@@ -88,6 +88,7 @@ constexpr int MS_BASE = 2304;                          // tsdf.hip: the two alte
 constexpr int CC_SCALARS = 3584, CC_SCALARS_WORDS = 14;            // fgmesh.hip: the clean-up's / the frame mesh runner's block, [0..13]
 constexpr int DEC_SCALARS = 3712, DEC_SCALARS_WORDS = 20;          // decimate.hip: [0..15] hive_decimate_run, [16..19] hive_mesh_decimate's counts
 constexpr int SEG_SCALARS = 3744, SEG_SCALARS_WORDS = 1;           // segment.hip: the first frame with more components than a uint8 label holds
+constexpr int TXS_SCALARS = 3752, TXS_SCALARS_WORDS = 24;         // texture_smooth.hip: 9 x u64 of hive_texture_smooth, behind them 2 x u64 of hive_mesh_face_neighbours
 struct hive_scalar_region {
     int at, words;
 };
@@ -96,7 +97,7 @@ constexpr hive_scalar_region HIVE_SCALAR_MAP[] = {
     {SC_PROJECT_BBOX, SC_PROJECT_BBOX_WORDS},        {SC_GRID_TOTALS, SC_GRID_TOTALS_WORDS},   {SC_FILTER_TOTAL, SC_FILTER_TOTAL_WORDS},
     {SC_WINDOW_BOX, SC_WINDOW_BOX_WORDS},            {SC_TSDF_FRAME_B, SC_TSDF_FRAME_WORDS},   {SC_TSDF_COUNTERS, SC_TSDF_COUNTERS_WORDS},
     {MS_BASE, MS_STRIDE},                            {MS_BASE + MS_STRIDE, MS_STRIDE},         {CC_SCALARS, CC_SCALARS_WORDS},
-    {DEC_SCALARS, DEC_SCALARS_WORDS},                {SEG_SCALARS, SEG_SCALARS_WORDS},
+    {DEC_SCALARS, DEC_SCALARS_WORDS},                {SEG_SCALARS, SEG_SCALARS_WORDS},         {TXS_SCALARS, TXS_SCALARS_WORDS},
 };
 constexpr bool hive_scalar_map_ok() {
     int end = 0;
@@ -243,6 +244,15 @@ __device__ __forceinline__ void block_butterfly_sum(double *s, double (*lds)[WID
     __syncthreads();
     if (threadIdx.x == 0)
         for (int j = 0; j < COUNT; ++j) s[j] = ((lds[0][j] + lds[1][j]) + lds[2][j]) + lds[3][j];
+}
+// a bijection of the 32-bit integers that scatters neighbouring ids: the tie-break of the decimation's collapse keys (decimate.hip) and of the label smoothing's
+// appliers (texture_smooth.hip), neither of which may follow the numbering of the mesh
+__device__ __forceinline__ unsigned mix32(unsigned x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    return x ^ (x >> 16);
 }
 // ceil(a / b) for launch grids
 inline int hive_div_up(long long a, int b) { return (int)((a + b - 1) / b); }

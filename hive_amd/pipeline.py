@@ -211,7 +211,8 @@ class Pipeline:
         """The static mesh with an atlas (``texturing.texture_mesh``) from the key frames the fusion used (``create_static_mesh``'s set; beyond
         ``options.texture_max_views`` every ceil(k / max)-th of them): the stored frames as they are (not the inpainted ones), without the pixels of the stored
         instance masks (non-zero), dilated with the run's ``MaskDilationOptions`` as the foreground's are.  ``profiling['background_texturing']`` gets the
-        counts."""
+        counts.  ``options.texture_smoothness`` and ``options.texture_cull_back_faces`` are passed on; when either is set the record gains ``smoothing``, the
+        stats of the label smoothing."""
         from hive_amd import texturing
         from hive_amd.image_processing import dilate_mask
         if num_frames is None or num_frames < 1:
@@ -225,10 +226,13 @@ class Pipeline:
             masks = np.stack([dilate_mask(np.asarray(dataset.mask_dataset[i]) != 0, self.dilation_options) for i in frame_set])
             poses = np.asarray(dataset.camera_trajectory.to_homogenous_transforms(), np.float64)[frame_set]
             mesh = texturing.texture_mesh(static_mesh, frames, np.asarray(dataset.camera_matrix), poses, masks=masks, cell=self.options.texture_cell,
-                                          return_views=True)
-        views = mesh.pop("views")
+                                          return_views=True, smoothness=float(self.options.texture_smoothness),
+                                          cull_back_faces=bool(self.options.texture_cull_back_faces), return_stats=True)
+        views, stats = mesh.pop("views"), mesh.pop("stats")
         self.profiling["background_texturing"] = {"key_frames": [int(f) for f in frame_set], "faces": int(views.shape[0]), "faces_with_a_view": int((views >= 0).sum()),
                                                   "atlas": [int(mesh["texture"].shape[1]), int(mesh["texture"].shape[0])]}
+        if stats is not None:
+            self.profiling["background_texturing"]["smoothing"] = stats
         return mesh
 
     def _create_foreground_scene(self, dataset: HiveDataset, num_frames: Optional[int] = None, folder: Optional[str] = None) -> gltf.Scene:

@@ -4,9 +4,14 @@ per voxel corner however sharp the frames are.
 
 The rules -- the candidate test on the rasteriser's own snapped vertices and depth plane, the 64-bit area | view key, the atlas layout, the barycentric map of a
 texel, the bilinear sample -- are stated in include/hive_mi355x.h above ``hive_texture_select`` and restated in numpy in tests/texturing_restatement.py; the
-kernels match that restatement bit for bit.  Not done here: seam levelling or label smoothing between neighbouring faces that chose different views, exposure
-compensation, blending of several views, a back-face test."""
+kernels match that restatement bit for bit.
+
+With ``smoothness`` or ``cull_back_faces`` the labels come from csrc/texture_smooth.hip instead (rules above ``hive_texture_vote``, restated in
+tests/texture_smoothing_restatement.py): every view's areas are kept in a table, the faces' edge adjacency is built, and labels move while that lowers
+-(area kept) + seam cost x (seam edges) -- iterated conditional modes, a local optimum, not a graph cut.  Not done here: a chart atlas (the layout stays three
+vertices per face and ``cell``^2 texels per face pair), seam levelling, exposure compensation, blending of several views."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -64,8 +69,64 @@ def _frames(frames):
     return frames
 
 
+AREA_UNITS_PER_PX2 = 131072  # the snapped area A is twice the area in 1/256-pixel units: 2 * 256 * 256 per square pixel
+STATS = ("rounds", "label_changes", "seam_entries_before", "seam_entries_after", "area_given_up_px2")
+
+
+def _context(ctx, dev):
+    ctx = ctx or _lib.default_context(dev.index or 0)
+    return ctx.follow_torch_stream()
+
+
+def face_neighbours(faces, num_vertices, ctx=None):
+    """The edge adjacency of a triangle list (``hive_mesh_face_neighbours``): ``(offsets int64 (F + 1,), neighbours int32 (total,))`` on the device; face f's
+    neighbour entries are ``neighbours[offsets[f]:offsets[f + 1]]``, ascending, one entry per edge shared.  A face with an id outside [0, num_vertices) or a
+    repeated id has none.  ``faces``: int (F, 3), numpy or device."""
+    import torch
+    dev = faces.device if _is_torch(faces) and faces.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    f = (faces if _is_torch(faces) else torch.from_numpy(np.ascontiguousarray(faces))).to(device=dev, dtype=torch.int32).contiguous()
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces (F, 3), got {tuple(f.shape)}")
+    nf = f.shape[0]
+    if 3 * nf >= 2 ** 31:
+        raise ValueError(f"{nf} faces: 3 F must stay below 2^31")
+    ctx = _context(ctx, dev)
+    offsets = torch.empty(nf + 1, dtype=torch.int64, device=dev)
+    capacity, total = 3 * nf, ctypes.c_int64(0)  # what a closed manifold has
+    for attempt in range(2):
+        neighbours = torch.empty(capacity, dtype=torch.int32, device=dev)
+        rc = ctx.lib.hive_mesh_face_neighbours(ctx.handle, ptr(f), nf, int(num_vertices), ptr(offsets), ptr(neighbours), capacity, ctypes.byref(total))
+        if rc == _lib.OK or attempt == 1 or total.value <= capacity:
+            break
+        capacity = total.value  # an edge with more than two faces: once more with what the call counted
+    ctx.check(rc)
+    return offsets, neighbours[:total.value]
+
+
+def smooth_labels(area, offsets, neighbours, seam_cost, ctx=None, rounds_per_poll=0):
+    """``hive_texture_smooth``: ``(best, stats)`` -- ``best`` int64 (F,) on the device holding the bits of the uint64 keys ``area << 16 | (65535 - view)`` (0 = no
+    view), ``stats`` the five integers {rounds, label changes, seam entries before, seam entries after, area given up} in the table's unit.  ``area``: int64
+    (n, F) (numpy or device), ``offsets`` / ``neighbours`` as ``face_neighbours`` returns them, ``seam_cost``: an integer in [0, 2^40) in the same unit;
+    ``rounds_per_poll``: rounds issued between two read-backs (0: the default; the result does not depend on it)."""
+    import torch
+    dev = next((a.device for a in (area, offsets, neighbours) if _is_torch(a) and a.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+    as_dev = lambda a, dt: (a if _is_torch(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
+    area, offsets, neighbours = as_dev(area, torch.int64), as_dev(offsets, torch.int64), as_dev(neighbours, torch.int32)
+    if area.dim() != 2 or offsets.dim() != 1 or neighbours.dim() != 1 or offsets.shape[0] != area.shape[1] + 1:
+        raise ValueError(f"area (n, F), offsets (F + 1,), neighbours (total,), got {tuple(area.shape)}, {tuple(offsets.shape)}, {tuple(neighbours.shape)}")
+    n, nf = (int(v) for v in area.shape)
+    if n * nf >= 2 ** 31:
+        raise ValueError(f"{n} views x {nf} faces: the table must stay below 2^31 entries")
+    ctx = _context(ctx, dev)
+    best = torch.zeros(nf, dtype=torch.int64, device=dev)
+    stats = np.zeros(5, np.int64)
+    ctx.check(ctx.lib.hive_texture_smooth(ctx.handle, ptr(area), n, nf, ptr(offsets), ptr(neighbours), int(neighbours.shape[0]), int(seam_cost), int(rounds_per_poll),
+                                          ptr(best), ptr(stats)))
+    return best, stats
+
+
 def texture_mesh(mesh, frames, camera_matrix, camera_poses, masks=None, cell=8, depth_tolerance=0.05, near=0.05, ctx=None, buffers: RenderBuffers = None,
-                 return_views=False):
+                 return_views=False, smoothness=0.0, cull_back_faces=False, return_stats=False):
     """The mesh with a texture atlas filled from the frames: a dict with ``vertices`` (3F, 3) float64, ``faces`` (F, 3) int32, ``uv`` (3F, 2) float64 and ``texture``
     (Ht, Wt, 3) uint8 as device tensors -- the keys of a ``foreground.process_frame`` mesh, so ``render_mesh``, ``gltf.Scene.add_geometry`` and ``write_glb`` take it
     as it is.  With ``return_views`` also ``views`` int32 (F,): the frame each face was textured from, -1 for none.
@@ -75,10 +136,16 @@ def texture_mesh(mesh, frames, camera_matrix, camera_poses, masks=None, cell=8, 
     ``CameraMatrix`` or a 3 x 3 array.  ``camera_poses``: (n, 7) rows (``pose_vec2mat``) or (n, 4, 4) world-to-camera matrices, as ``render_mesh`` takes one.
     ``masks``: (n, H, W), non-zero = do not use that pixel.  ``cell``: the side of an atlas block (two faces) in texels.  ``depth_tolerance``: how far behind the
     rendered surface a vertex may lie and still count as seen (a parameter default: 5 cm for a scene in metres); ``near``: ``render_mesh``'s.  Each face takes the
-    view in which its exact snapped area is largest; on equal area the lower index.  There is no back-face test and no blending.
+    view in which its exact snapped area is largest; on equal area the lower index.  There is no blending.
+
+    ``smoothness`` (px^2, default 0): the projected area a face may give up to remove one seam edge, i.e. an edge whose two faces are textured from different
+    views; the labels are then smoothed across edges (``hive_texture_smooth``) with ``seam_cost = llround(smoothness * 131072)``.  ``cull_back_faces``: a view
+    counts for a face only where it sees the face's front (snapped area A < 0, this project's marching-cubes winding).  With both at their defaults the
+    per-face selection above runs as it always did.  ``return_stats`` adds ``stats``: a dict of ``rounds``, ``label_changes``, ``seam_entries_before``,
+    ``seam_entries_after`` and ``area_given_up_px2`` (None on the default path).  The table of areas takes 8 n F bytes of device memory.
 
     ValueError: an empty mesh, no frame or more than 65535, frames of mixed size, ``cell`` outside [6, 64], an atlas side above 16384, a mesh without vertex
-    colours, face ids outside [0, V)."""
+    colours, face ids outside [0, V), a negative or non-finite ``smoothness`` (or one of 2^23 px^2 and more), n F >= 2^31 on the smoothing path."""
     import torch
     vertices, faces, colors = _mesh_parts(mesh)
     if vertices is None or faces is None or len(vertices) == 0 or len(faces) == 0:
@@ -105,6 +172,14 @@ def texture_mesh(mesh, frames, camera_matrix, camera_poses, masks=None, cell=8, 
     wt, ht, _ = atlas_layout(nf, cell)
     if 3 * nf >= 2 ** 31:
         raise ValueError(f"{nf} faces need {3 * nf} vertices: the indices are int32")
+    if not (math.isfinite(smoothness) and smoothness >= 0):
+        raise ValueError(f"smoothness must be finite and >= 0, got {smoothness}")
+    seam_cost = int(math.floor(float(smoothness) * AREA_UNITS_PER_PX2 + 0.5))  # llround of a non-negative number (the product by 2^17 is exact)
+    if seam_cost >= 2 ** 40:
+        raise ValueError(f"smoothness {smoothness} px^2 is 2^23 px^2 or more")
+    smoothing = seam_cost > 0 or bool(cull_back_faces)
+    if smoothing and n * nf >= 2 ** 31:
+        raise ValueError(f"{n} frames x {nf} faces: the table of areas must stay below 2^31 entries")
 
     dev = buffers.device if buffers is not None else next((a.device for a in (vertices, frames) if _is_torch(a) and a.is_cuda), None) or \
         torch.device("cuda", torch.cuda.current_device())
@@ -133,14 +208,25 @@ def texture_mesh(mesh, frames, camera_matrix, camera_poses, masks=None, cell=8, 
     xy, z, large, counts = buffers.slot(0, nv, nf)
     depth = torch.empty((h, w), dtype=torch.float32, device=dev)
     best = torch.zeros(nf, dtype=torch.int64, device=dev)  # (the bits of a uint64)
+    area = torch.empty((n, nf), dtype=torch.int64, device=dev) if smoothing else None
     for k in range(n):
         R, t = np.ascontiguousarray(poses[k, :3, :3]), np.ascontiguousarray(poses[k, :3, 3])
         ctx.check(lib.hive_render_clear(handle, ptr(buffers.key), h, w))
         ctx.check(lib.hive_render_draw(handle, ptr(v), nv, ptr(f), nf, 0, ptr(K), ptr(R), ptr(t), h, w, float(near), ptr(xy), ptr(z), ptr(large), ptr(counts),
                                        ptr(buffers.key)))
         ctx.check(lib.hive_render_resolve(handle, ptr(buffers.key), h, w, None, None, ptr(depth), None))
+        if smoothing:
+            ctx.check(lib.hive_texture_vote(handle, ptr(f), nf, nv, ptr(xy), ptr(z), ptr(depth), ptr(None if d_masks is None else d_masks[k]), h, w, k,
+                                            float(depth_tolerance), 1 if cull_back_faces else 0, ptr(area)))
+            continue
         ctx.check(lib.hive_texture_select(handle, ptr(f), nf, nv, ptr(xy), ptr(z), ptr(depth), ptr(None if d_masks is None else d_masks[k]), h, w, k,
                                           float(depth_tolerance), ptr(best)))
+    stats = None
+    if smoothing:
+        offsets, neighbours = face_neighbours(f, nv, ctx=ctx)
+        best, counts = smooth_labels(area, offsets, neighbours, seam_cost, ctx=ctx)
+        stats = {name: int(value) for name, value in zip(STATS, counts)}
+        stats["area_given_up_px2"] = stats["area_given_up_px2"] / AREA_UNITS_PER_PX2
     out = dict(vertices=torch.empty((3 * nf, 3), dtype=torch.float64, device=dev), faces=torch.empty((nf, 3), dtype=torch.int32, device=dev),
                uv=torch.empty((3 * nf, 2), dtype=torch.float64, device=dev), texture=torch.empty((ht, wt, 3), dtype=torch.uint8, device=dev))
     views = torch.empty(nf, dtype=torch.int32, device=dev) if return_views else None
@@ -149,4 +235,6 @@ def texture_mesh(mesh, frames, camera_matrix, camera_poses, masks=None, cell=8, 
                                     ptr(out["texture"])))
     if return_views:
         out["views"] = views
+    if return_stats:
+        out["stats"] = stats
     return out

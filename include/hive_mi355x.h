@@ -624,6 +624,51 @@ int hive_texture_unweld(hive_ctx *ctx, const double *d_vertices, int64_t nv, con
 int hive_texture_fill(hive_ctx *ctx, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf, const uint64_t *d_best,
                       const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell, uint8_t *d_texture);
 
+/* ---- smoothing the view labels across edges -- csrc/texture_smooth.hip.  hive_texture_select lets every face decide alone; where two views see a surface about
+ * equally well neighbouring faces flip between them, and every flip is a seam.  The three entry points below keep the areas in a table, build the edge
+ * adjacency of the mesh and move labels while that lowers E = -sum_f area[L[f]][f] + seam_cost * #seams.  Integers only; the result is the same whatever order
+ * workgroups run in and however many rounds the host issues between two polls.  This is iterated conditional modes: it ends in a LOCAL optimum of E, it is not
+ * a graph cut.  Out of scope: a chart atlas (unweld and fill are unchanged: 3 F vertices, cell^2 texels per face pair), seam levelling, exposure compensation,
+ * blending.  The rules:
+ *   vote        hive_texture_select's candidate test, on the same d_xy, d_z, d_depth and d_mask, and a filter on the sign of the snapped area A: facing 0 takes
+ *               either sign (as select does), 1 only A < 0, -1 only A > 0.  d_area[view_index nf + f] = |A| of a candidate, 0 otherwise; every entry of the row is
+ *               written.  Which sign is the front: measured on the marching-cubes mesh of the tests' fused room (2 052 faces, three views) under the
+ *               rasteriser's snap, 7 / 9 / 31 candidates have A > 0 (seen from behind) and 881 / 1 090 / 1 163 have A < 0: for this project's meshes
+ *               front-facing means A < 0, so facing = 1 is the back-face test hive_texture_select lacks.
+ *   neighbours  face g is an edge-neighbour of f (g != f) once for every unordered pair of vertex ids that is an edge of both: two faces sharing two edges list
+ *               each other twice, duplicates of a face three times, an edge with m faces gives each of them m - 1 entries.  A face with an id outside [0, nv)
+ *               or a repeated id has no entries and appears in none.  d_offsets[f] .. d_offsets[f + 1] are f's entries in d_neighbours, ascending.  Cost: per face
+ *               edge (a, b) a walk over the faces of a, and an insertion sort of the face's entries -- quadratic in a face's degree, fine for surfaces.
+ *   smooth      start: L[f] = the view v with the largest d_area[v][f] > 0, on equal area the lower v, -1 if there is none.  One round, read entirely from the
+ *               labels at its start: for every f with L[f] = cur >= 0, cnt(x) = the number of f's neighbour entries g with L[g] = x; for each label l != cur that
+ *               some neighbour entry holds, with d_area[l][f] != 0, gain(l) = (area[l][f] - area[cur][f]) + seam_cost (cnt(l) - cnt(cur)); f PROPOSES the l of
+ *               largest gain, on a tie the lower l, if that gain is > 0; f APPLIES its proposal iff for every neighbour entry g that proposes, gain_f > gain_g,
+ *               or the gains are equal and mix32(f) < mix32(g) (mix32: x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16 on 32 bits,
+ *               the decimation's bijection; with the plain index a tied 32 x 32 grid needs 32 rounds instead of 4).  An unlabelled neighbour counts for
+ *               nothing, and an unlabelled face stays so.  Appliers are pairwise non-adjacent, so a round lowers E by exactly the sum of their gains (a seam = a
+ *               neighbour entry (f, g), f < g, with both labels >= 0 and different; the adjacency is symmetric); E is a bounded integer, so the rounds end.
+ *               They stop at the first round without a proposal; `rounds` counts the rounds before it.  More than 4096: HIVE_ERR_STATE.
+ *               end: d_best[f] = 0 if L[f] < 0, else area[L[f]][f] << 16 | (65535 - L[f]): hive_texture_select's key format, which unweld and fill take as it is.
+ *               With seam_cost = 0 nothing can propose (a tie has gain 0), so with facing = 0 the keys are those n calls of hive_texture_select leave.
+ *               Magnitudes: areas < 2^47, seam_cost < 2^40, a face's degree < 2^16 (refused otherwise): gains stay below 2^47 + 2^56.
+ * Memory: the table is 8 n_views nf bytes (186 MB for 725 k faces and 32 views). */
+/* One view's row of the table: the arguments of hive_texture_select, facing in {-1, 0, 1}, d_area i64 [n_views][nf].  (view_index + 1) nf < 2^31, else
+ * HIVE_ERR_INVALID: a table has n_views nf < 2^31 entries. */
+int hive_texture_vote(hive_ctx *ctx, const int32_t *d_faces, int64_t nf, int64_t nv, const int32_t *d_xy, const double *d_z, const float *d_depth,
+                      const uint8_t *d_mask, int H, int W, int view_index, double depth_tolerance, int facing, int64_t *d_area);
+/* The edge adjacency of d_faces i32 [nf][3] (3 nf < 2^31) over nv vertices: d_offsets i64 [nf + 1], d_neighbours i32 [capacity] (may be NULL with capacity 0),
+ * *total = the number of entries.  One read-back; when capacity < *total the call fails with HIVE_ERR_INVALID and the total in its message, *total is set
+ * and nothing is written to d_neighbours: call again with that capacity.  A closed manifold has 3 nf entries. */
+int hive_mesh_face_neighbours(hive_ctx *ctx, const int32_t *d_faces, int64_t nf, int64_t nv, int64_t *d_offsets, int32_t *d_neighbours, int64_t capacity,
+                              int64_t *total);
+/* The labelling.  d_area i64 [n_views][nf] with entries in [0, 2^47), 1 <= n_views <= 65535, n_views nf < 2^31; d_offsets i64 [nf + 1] and d_neighbours i32
+ * [n_entries] as hive_mesh_face_neighbours writes them (checked on the device: offsets ascending from 0 to at most n_entries, ids in [0, nf), no face its own
+ * neighbour, a degree below 2^16; HIVE_ERR_INVALID otherwise); 0 <= seam_cost < 2^40 in the table's unit; rounds_per_poll: the rounds issued between two
+ * read-backs of the device's state, 0 = the default of 8 (the result does not depend on it).  d_best u64 [nf] out; stats (may be NULL) = {rounds, label
+ * changes, seam entries before, seam entries after, area given up = sum_f (max_v area[v][f] - area[L[f]][f])}.  Synchronises once per batch of rounds. */
+int hive_texture_smooth(hive_ctx *ctx, const int64_t *d_area, int n_views, int64_t nf, const int64_t *d_offsets, const int32_t *d_neighbours, int64_t n_entries,
+                        int64_t seam_cost, int rounds_per_poll, uint64_t *d_best, int64_t stats[5]);
+
 /* ---- ray casting the volume and tracking the camera against it (KinectFusion-style frame-to-model ICP; no counterpart in the reference, which takes its
  * poses from COLMAP or BundleFusion).  Float32 where stated, every operation rounded once (no fused multiply-add), in the order written here; pixel (u, v) =
  * (column, row), pixel centres at integers.
