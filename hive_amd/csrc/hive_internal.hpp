@@ -337,6 +337,38 @@ template <class Total, class... Counts>
 inline void hive_scan_counts(hive_ctx *ctx, int nb, Total *total, Counts *... a) {
     hipLaunchKernelGGL((scan_counts_kernel<Total, Counts...>), dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, nb, total, a...);
 }
+// ---- the exclusive scan of n counts behind the vertex -> faces lists (texture_smooth.hip, texture_level.hip): tile sums, hive_scan_counts over them, offsets ----
+constexpr int HIVE_SCAN_TILE = 1024;  // items per 256-thread workgroup (4 consecutive items per thread keep the order)
+// the sum of c[0 .. n) per tile; the grid covers item n as well (an empty item), so that tile_offsets_kernel writes out[n] = the total
+template <int TILE>
+__global__ __launch_bounds__(256) void tile_sums_kernel(const unsigned *__restrict__ c, long long n, unsigned *__restrict__ tiles) {
+    __shared__ unsigned lds[4];
+    unsigned s[1] = {0};
+    for (int j = 0; j < TILE / 256; ++j) {
+        const long long i = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256) + j;
+        if (i < n) s[0] += c[i];
+    }
+    block_sum(s, lds);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = s[0];
+}
+// out[i] = the sum of c[0 .. i) for i in [0, n]; tiles: the scanned tile sums
+template <int TILE, class Out>
+__global__ __launch_bounds__(256) void tile_offsets_kernel(const unsigned *__restrict__ c, long long n, const unsigned *__restrict__ tiles, Out *__restrict__ out) {
+    __shared__ unsigned lds[4];
+    const long long base = (long long)blockIdx.x * TILE + threadIdx.x * (TILE / 256);
+    unsigned v[TILE / 256], mine = 0;
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j) {
+        v[j] = base + j < n ? c[base + j] : 0u;
+        mine += v[j];
+    }
+    unsigned long long o = (unsigned long long)tiles[blockIdx.x] + block_exclusive(mine, lds);
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j) {
+        if (base + j <= n) out[base + j] = (Out)o;
+        o += v[j];
+    }
+}
 // the last of n >= 1 table rows whose first element first_of(row) is not after `at` (rows ascend; row 0 starts at or before every `at` asked for)
 template <class At, class FirstOf>
 __device__ __forceinline__ int last_not_after(int n, At at, FirstOf first_of) {

@@ -8,14 +8,14 @@
 //   unweld     three vertices of its own per face; uv at the corner texels (1, 1), (S - 4, 1), (1, S - 4) / (S - 2, S - 2), (3, S - 2), (S - 2, 3)
 //   fill       b1, b2 from the block-local texel, b0 = (1 - b1) - b2; P = (b0 V0 + b1 V1) + b2 V2; hive_project's order with the winning view; bilinear in float64;
 //              a face without a view: the same combination of its vertex colours.  One thread per texel.
+//   adjusted fill   the same kernel with texture_level.hip's Q16 gain per view and channel and offsets per face corner: byte((c q) 2^-16 + interpolated offset);
+//              exact, hence the plain atlas, at unit gains and zero offsets.  The projection and the bilinear sample are texture_core.hpp's, shared with the levelling.
 //
 // Float64 without contraction (the Makefile's EXACT flags).
 //
 // Kernels: texture_select_kernel and texture_unweld_kernel (one thread per face), texture_fill_kernel (one thread per texel, workgroups of TX_TILE x TX_TILE
 // texels: DESIGN.md, "Texturing the background").
-#include "hive_internal.hpp"
-
-#include <cmath>
+#include "texture_core.hpp"
 
 namespace {
 
@@ -41,10 +41,6 @@ bool tx_layout(long long nf, int cell, TextureLayout &l, const char *&why) {
     if (r * cell > TX_MAX_ATLAS || rows * cell > TX_MAX_ATLAS) return why = "texture_layout: the atlas would exceed 16384 texels on a side", false;
     l.per_row = (int)r, l.Wt = (int)(r * cell), l.Ht = (int)(rows * cell);
     return true;
-}
-
-__device__ __forceinline__ bool tx_ids_ok(int a, int b, int c, long long nv) {
-    return (unsigned long long)a < (unsigned long long)nv && (unsigned long long)b < (unsigned long long)nv && (unsigned long long)c < (unsigned long long)nv;
 }
 
 __global__ __launch_bounds__(TX_THREADS) void texture_select_kernel(const int32_t *__restrict__ faces, long long nf, long long nv, const int32_t *__restrict__ xy,
@@ -96,17 +92,13 @@ __global__ __launch_bounds__(TX_THREADS) void texture_unweld_kernel(const double
     if (views) views[f] = best && best[f] ? (int32_t)(65535u - (unsigned)(best[f] & 0xffffull)) : -1;
 }
 
-struct TextureCam {
-    double K[9];
-    double near;
-};
-
-__device__ __forceinline__ uint8_t tx_byte(double c) { return (uint8_t)fmin(255.0, fmax(0.0, floor(c + 0.5))); }
-
+// ADJUST: hive_texture_fill_adjusted's gains u32 [n][3] (Q16) and offsets f64 [nf][3][3] on a texel with a view; the plain fill passes neither
+template <bool ADJUST>
 __global__ __launch_bounds__(TX_TILE *TX_TILE) void texture_fill_kernel(const double *__restrict__ vertices, long long nv, const uint8_t *__restrict__ colors,
                                                                         const int32_t *__restrict__ faces, long long nf, const unsigned long long *__restrict__ best,
                                                                         const uint8_t *__restrict__ frames, int n, int H, int W, TextureCam cam,
-                                                                        const double *__restrict__ poses, TextureLayout l, uint8_t *__restrict__ texture) {
+                                                                        const double *__restrict__ poses, TextureLayout l, const unsigned *__restrict__ gains,
+                                                                        const double *__restrict__ offsets, uint8_t *__restrict__ texture) {
     const int col = blockIdx.x * TX_TILE + threadIdx.x, row = blockIdx.y * TX_TILE + threadIdx.y;
     if (col >= l.Wt || row >= l.Ht) return;
     uint8_t *o = texture + 3 * ((size_t)row * l.Wt + col);
@@ -129,32 +121,28 @@ __global__ __launch_bounds__(TX_TILE *TX_TILE) void texture_fill_kernel(const do
             o[ch] = tx_byte((b0 * (double)colors[3 * (long long)id[0] + ch] + b1 * (double)colors[3 * (long long)id[1] + ch]) + b2 * (double)colors[3 * (long long)id[2] + ch]);
         return;
     }
-    const double *R = poses + 12 * (long long)view, *t = R + 9;
+    const double *Rt = poses + 12 * (long long)view;
     double c[3];
     for (int attempt = 0; attempt < 2; ++attempt) {  // the second time: vertex 0, which the draw kept
-        double P[3], q[3];
+        double P[3];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const double v0 = vertices[3 * (long long)id[0] + r];
             P[r] = attempt ? v0 : (b0 * v0 + b1 * vertices[3 * (long long)id[1] + r]) + b2 * vertices[3 * (long long)id[2] + r];
         }
-#pragma unroll
-        for (int r = 0; r < 3; ++r) q[r] = R[3 * r + 0] * P[0] + R[3 * r + 1] * P[1] + R[3 * r + 2] * P[2] + t[r];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) c[r] = cam.K[3 * r + 0] * q[0] + cam.K[3 * r + 1] * q[1] + cam.K[3 * r + 2] * q[2];
+        tx_project(cam, Rt, P, c);
         if (c[2] >= cam.near) break;
     }
-    const double u = fmin(fmax(c[0] / c[2], 0.0), (double)(W - 1)), v = fmin(fmax(c[1] / c[2], 0.0), (double)(H - 1));
-    const double fu = floor(u), fv = floor(v), ax = u - fu, ay = v - fv;
-    const int j0 = (int)fu, i0 = (int)fv, j1 = min(j0 + 1, W - 1), i1 = min(i0 + 1, H - 1);
-    const uint8_t *frame = frames + 3 * (size_t)view * H * W;
-    const uint8_t *p00 = frame + 3 * ((size_t)i0 * W + j0), *p01 = frame + 3 * ((size_t)i0 * W + j1), *p10 = frame + 3 * ((size_t)i1 * W + j0),
-                  *p11 = frame + 3 * ((size_t)i1 * W + j1);
+    double s[3];
+    tx_bilinear(frames + 3 * (size_t)view * H * W, H, W, c, s);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const double c00 = (double)p00[ch], c01 = (double)p01[ch], c10 = (double)p10[ch], c11 = (double)p11[ch];
-        const double top = c00 + ax * (c01 - c00), bottom = c10 + ax * (c11 - c10);
-        o[ch] = tx_byte(top + ay * (bottom - top));
+        if (ADJUST) {
+            const double *h = offsets + 9 * f;
+            o[ch] = tx_byte(((s[ch] * (double)gains[3 * view + ch]) * 0x1p-16) + ((b0 * h[ch] + b1 * h[3 + ch]) + b2 * h[6 + ch]));
+        } else {
+            o[ch] = tx_byte(s[ch]);
+        }
     }
 }
 
@@ -205,26 +193,45 @@ int hive_texture_unweld(hive_ctx *ctx, const double *d_vertices, int64_t nv, con
     return HIVE_OK;
 }
 
-int hive_texture_fill(hive_ctx *ctx, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf, const uint64_t *d_best,
-                      const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell, uint8_t *d_texture) {
+// the two fills: d_gains == NULL is the plain one
+static int tx_fill(hive_ctx *ctx, const char *name, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf,
+                   const uint64_t *d_best, const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell,
+                   const uint32_t *d_gains, const double *d_offsets, uint8_t *d_texture) {
     HIVE_ENTER(ctx);
     if (!ctx) return hive_fail(nullptr, HIVE_ERR_INVALID, "ctx is NULL");
     TextureLayout l;
     const char *why = nullptr;
     HIVE_REQUIRE(ctx, tx_layout(nf, cell, l, why), "%s (%lld faces, cell %d)", why, (long long)nf, cell);
-    HIVE_REQUIRE(ctx, n > 0 && n <= TX_MAX_VIEWS, "texture_fill: %d views outside [1, 65535]", n);
-    HIVE_REQUIRE(ctx, H > 0 && W > 0 && (long long)H * W < (1ll << 31), "texture_fill: bad frame size %d x %d", H, W);
-    HIVE_REQUIRE(ctx, near > 0.0, "texture_fill: near must be > 0");
+    HIVE_REQUIRE(ctx, n > 0 && n <= TX_MAX_VIEWS, "%s: %d views outside [1, 65535]", name, n);
+    HIVE_REQUIRE(ctx, H > 0 && W > 0 && (long long)H * W < (1ll << 31), "%s: bad frame size %d x %d", name, H, W);
+    HIVE_REQUIRE(ctx, near > 0.0, "%s: near must be > 0", name);
     HIVE_REQUIRE(ctx, nv > 0 && nv < (1ll << 31) && d_vertices && d_vertex_colors && d_faces && d_best && d_frames && K && d_poses && d_texture,
-                 "texture_fill: NULL argument or no vertices");
+                 "%s: NULL argument or no vertices", name);
     TextureCam cam;
     memcpy(cam.K, K, sizeof(cam.K));
     cam.near = near;
     const dim3 grid((unsigned)((l.Wt + TX_TILE - 1) / TX_TILE), (unsigned)((l.Ht + TX_TILE - 1) / TX_TILE));
-    hipLaunchKernelGGL(texture_fill_kernel, grid, dim3(TX_TILE, TX_TILE), 0, ctx->stream, d_vertices, (long long)nv, d_vertex_colors, d_faces, (long long)nf,
-                       (const unsigned long long *)d_best, d_frames, n, H, W, cam, d_poses, l, d_texture);
+    if (d_gains)
+        hipLaunchKernelGGL(texture_fill_kernel<true>, grid, dim3(TX_TILE, TX_TILE), 0, ctx->stream, d_vertices, (long long)nv, d_vertex_colors, d_faces, (long long)nf,
+                           (const unsigned long long *)d_best, d_frames, n, H, W, cam, d_poses, l, (const unsigned *)d_gains, d_offsets, d_texture);
+    else
+        hipLaunchKernelGGL(texture_fill_kernel<false>, grid, dim3(TX_TILE, TX_TILE), 0, ctx->stream, d_vertices, (long long)nv, d_vertex_colors, d_faces, (long long)nf,
+                           (const unsigned long long *)d_best, d_frames, n, H, W, cam, d_poses, l, (const unsigned *)nullptr, (const double *)nullptr, d_texture);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;
+}
+
+int hive_texture_fill(hive_ctx *ctx, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf, const uint64_t *d_best,
+                      const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell, uint8_t *d_texture) {
+    return tx_fill(ctx, "texture_fill", d_vertices, nv, d_vertex_colors, d_faces, nf, d_best, d_frames, n, H, W, K, d_poses, near, cell, nullptr, nullptr, d_texture);
+}
+
+int hive_texture_fill_adjusted(hive_ctx *ctx, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf,
+                               const uint64_t *d_best, const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell,
+                               const uint32_t *d_gains_q16, const double *d_offsets, uint8_t *d_texture) {
+    if (ctx && !(d_gains_q16 && d_offsets)) return hive_fail(ctx, HIVE_ERR_INVALID, "texture_fill_adjusted: NULL gains or offsets");
+    return tx_fill(ctx, "texture_fill_adjusted", d_vertices, nv, d_vertex_colors, d_faces, nf, d_best, d_frames, n, H, W, K, d_poses, near, cell, d_gains_q16, d_offsets,
+                   d_texture);
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 namespace {
 
 constexpr int TS_THREADS = 256;
-constexpr int TS_TILE = 1024;  // items per workgroup of the two scans (4 consecutive items per thread keep the order)
+constexpr int TS_TILE = HIVE_SCAN_TILE;  // items per workgroup of the two scans
 constexpr int TS_MAX_VIEWS = 65535, TS_MAX_ROUNDS = 4096, TS_BATCH = 8, TS_MAX_DEGREE = 65535;
 constexpr long long TS_MAX_AREA = 1ll << 47, TS_MAX_SEAM_COST = 1ll << 40;
 constexpr unsigned long long TS_ERR_ADJACENCY = 1, TS_ERR_DEGREE = 2, TS_ERR_AREA = 4, TS_ERR_ROUNDS = 8;
@@ -96,37 +96,7 @@ __global__ __launch_bounds__(TS_THREADS) void nb_count_kernel(NbParams p) {
     for (int k = 0; k < 3; ++k) atomicAdd(p.vcount + id[k], 1u);
 }
 
-// the sum of c[0 .. n) per block of TS_TILE items; the grid covers item n as well (an empty item), so that the offsets kernel writes out[n] = the total
-__global__ __launch_bounds__(TS_THREADS) void nb_block_sums_kernel(const unsigned *__restrict__ c, long long n, unsigned *__restrict__ blocks) {
-    __shared__ unsigned lds[4];
-    unsigned s[1] = {0};
-    for (int j = 0; j < TS_TILE / TS_THREADS; ++j) {
-        const long long i = (long long)blockIdx.x * TS_TILE + threadIdx.x * (TS_TILE / TS_THREADS) + j;
-        if (i < n) s[0] += c[i];
-    }
-    block_sum(s, lds);
-    if (threadIdx.x == 0) blocks[blockIdx.x] = s[0];
-}
-
-// out[i] = the sum of c[0 .. i) for i in [0, n]; blocks: the scanned block sums
-template <class Out>
-__global__ __launch_bounds__(TS_THREADS) void nb_offsets_kernel(const unsigned *__restrict__ c, long long n, const unsigned *__restrict__ blocks, Out *__restrict__ out) {
-    __shared__ unsigned lds[4];
-    const long long base = (long long)blockIdx.x * TS_TILE + threadIdx.x * (TS_TILE / TS_THREADS);
-    unsigned v[TS_TILE / TS_THREADS], mine = 0;
-#pragma unroll
-    for (int j = 0; j < TS_TILE / TS_THREADS; ++j) {
-        v[j] = base + j < n ? c[base + j] : 0u;
-        mine += v[j];
-    }
-    unsigned long long o = (unsigned long long)blocks[blockIdx.x] + block_exclusive(mine, lds);
-#pragma unroll
-    for (int j = 0; j < TS_TILE / TS_THREADS; ++j) {
-        if (base + j <= n) out[base + j] = (Out)o;
-        o += v[j];
-    }
-}
-
+// (the two scans: tile_sums_kernel and tile_offsets_kernel of hive_internal.hpp, shared with texture_level.hip)
 __global__ __launch_bounds__(TS_THREADS) void nb_fill_kernel(NbParams p) {
     const long long f = (long long)blockIdx.x * TS_THREADS + threadIdx.x;
     int id[3];
@@ -372,12 +342,12 @@ int hive_mesh_face_neighbours(hive_ctx *ctx, const int32_t *d_faces, int64_t nf,
     const dim3 blk(TS_THREADS);
     HIVE_CHECK_HIP(ctx, hipMemsetAsync(p.vcount, 0, 2 * (size_t)nv * sizeof(unsigned), s));
     hipLaunchKernelGGL(nb_count_kernel, ts_grid(nf), blk, 0, s, p);
-    hipLaunchKernelGGL(nb_block_sums_kernel, dim3(nb_v), blk, 0, s, (const unsigned *)p.vcount, (long long)nv, p.blocks);
+    hipLaunchKernelGGL(tile_sums_kernel<TS_TILE>, dim3(nb_v), blk, 0, s, (const unsigned *)p.vcount, (long long)nv, p.blocks);
     hive_scan_counts(ctx, nb_v, d_total + 1, p.blocks);
-    hipLaunchKernelGGL(nb_offsets_kernel<unsigned>, dim3(nb_v), blk, 0, s, (const unsigned *)p.vcount, (long long)nv, (const unsigned *)p.blocks, p.vstart);
+    hipLaunchKernelGGL((tile_offsets_kernel<TS_TILE, unsigned>), dim3(nb_v), blk, 0, s, (const unsigned *)p.vcount, (long long)nv, (const unsigned *)p.blocks, p.vstart);
     hipLaunchKernelGGL(nb_fill_kernel, ts_grid(nf), blk, 0, s, p);
     hipLaunchKernelGGL(nb_degree_kernel, ts_grid(nf), blk, 0, s, p);
-    hipLaunchKernelGGL(nb_block_sums_kernel, dim3(nb_f), blk, 0, s, (const unsigned *)p.degree, (long long)nf, p.blocks);
+    hipLaunchKernelGGL(tile_sums_kernel<TS_TILE>, dim3(nb_f), blk, 0, s, (const unsigned *)p.degree, (long long)nf, p.blocks);
     hive_scan_counts(ctx, nb_f, d_total, p.blocks);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     void *pinned;
@@ -389,7 +359,7 @@ int hive_mesh_face_neighbours(hive_ctx *ctx, const int32_t *d_faces, int64_t nf,
     // (the scanned block sums are 32-bit words: a larger total would have wrapped in them)
     HIVE_REQUIRE(ctx, n < (1ull << 31), "mesh_face_neighbours: %llu entries: the adjacency holds fewer than 2^31", n);
     HIVE_REQUIRE(ctx, (unsigned long long)capacity >= n, "mesh_face_neighbours: capacity %lld is too small: the adjacency has %llu entries", (long long)capacity, n);
-    hipLaunchKernelGGL(nb_offsets_kernel<long long>, dim3(nb_f), blk, 0, s, (const unsigned *)p.degree, (long long)nf, (const unsigned *)p.blocks, (long long *)d_offsets);
+    hipLaunchKernelGGL((tile_offsets_kernel<TS_TILE, long long>), dim3(nb_f), blk, 0, s, (const unsigned *)p.degree, (long long)nf, (const unsigned *)p.blocks, (long long *)d_offsets);
     if (n) hipLaunchKernelGGL(nb_entries_kernel, ts_grid(nf), blk, 0, s, p, (const long long *)d_offsets, d_neighbours);
     HIVE_CHECK_HIP(ctx, hipGetLastError());
     return HIVE_OK;

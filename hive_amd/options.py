@@ -451,18 +451,28 @@ class PipelineOptions(Options):
               _Flag('texture_max_views', 'texture_max_views', int, 32, 'at most this many key frames texture the background (every ceil(k / max)-th is kept)'),
               _Flag('texture_smoothness', 'texture_smoothness', float, 0.0, 'with --texture_background: the projected area in square pixels a face may give up to remove '
                     'one seam edge between two key frames (0: every face takes the view that sees it best)'),
-              _Flag('texture_cull_back_faces', 'texture_cull_back_faces', bool, False, 'with --texture_background: texture a face only from key frames that see its front'))
+              _Flag('texture_cull_back_faces', 'texture_cull_back_faces', bool, False, 'with --texture_background: texture a face only from key frames that see its front'),
+              _Flag('texture_exposure', 'texture_exposure', bool, False, 'with --texture_background: one gain per key frame and channel, solved from the faces two key '
+                    'frames both see, so that frames of different exposure or white balance agree'),
+              _Flag('texture_levelling', 'texture_levelling', bool, False, 'with --texture_background: additive offsets that close the colour step where the texture '
+                    'changes from one key frame to another'),
+              _Flag('texture_levelling_sweeps', 'texture_levelling_sweeps', int, 64, 'Jacobi sweeps that spread the offsets of --texture_levelling into the patches, '
+                    '0 .. 4096 (a parameter default, not a measured optimum)'))
 
     def __init__(self, num_frames=-1, frame_step=15, estimate_pose=False, estimate_depth=False, background_only=False, static_camera=False,
                  align_scene=False, inpainting_mode=InpaintingMode.Off, billboard=False, disable_scaling=False, disable_coverage_constraint=False,
                  log_file='logs.log', export_gltf=False, texture_format='png', jpeg_quality=90, png_encoder='host', texture_background=False, texture_cell=8,
-                 texture_max_views=32, texture_smoothness=0.0, texture_cull_back_faces=False):
+                 texture_max_views=32, texture_smoothness=0.0, texture_cull_back_faces=False, texture_exposure=False, texture_levelling=False,
+                 texture_levelling_sweeps=64):
         self.export_gltf = export_gltf
         self.texture_background = texture_background
         self.texture_cell = texture_cell
         self.texture_max_views = texture_max_views
         self.texture_smoothness = texture_smoothness
         self.texture_cull_back_faces = texture_cull_back_faces
+        self.texture_exposure = texture_exposure
+        self.texture_levelling = texture_levelling
+        self.texture_levelling_sweeps = texture_levelling_sweeps
         self.texture_format = texture_format
         self.jpeg_quality = jpeg_quality
         self.png_encoder = png_encoder

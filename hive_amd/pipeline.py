@@ -212,7 +212,8 @@ class Pipeline:
         ``options.texture_max_views`` every ceil(k / max)-th of them): the stored frames as they are (not the inpainted ones), without the pixels of the stored
         instance masks (non-zero), dilated with the run's ``MaskDilationOptions`` as the foreground's are.  ``profiling['background_texturing']`` gets the
         counts.  ``options.texture_smoothness`` and ``options.texture_cull_back_faces`` are passed on; when either is set the record gains ``smoothing``, the
-        stats of the label smoothing."""
+        stats of the label smoothing.  ``options.texture_exposure``, ``options.texture_levelling`` and ``options.texture_levelling_sweeps`` are passed on too
+        (``_texturing_record``); with all of them off the call and the export are what they were."""
         from hive_amd import texturing
         from hive_amd.image_processing import dilate_mask
         if num_frames is None or num_frames < 1:
@@ -227,13 +228,31 @@ class Pipeline:
             poses = np.asarray(dataset.camera_trajectory.to_homogenous_transforms(), np.float64)[frame_set]
             mesh = texturing.texture_mesh(static_mesh, frames, np.asarray(dataset.camera_matrix), poses, masks=masks, cell=self.options.texture_cell,
                                           return_views=True, smoothness=float(self.options.texture_smoothness),
-                                          cull_back_faces=bool(self.options.texture_cull_back_faces), return_stats=True)
+                                          cull_back_faces=bool(self.options.texture_cull_back_faces), return_stats=True,
+                                          exposure=bool(self.options.texture_exposure), levelling=bool(self.options.texture_levelling),
+                                          levelling_sweeps=int(self.options.texture_levelling_sweeps))
         views, stats = mesh.pop("views"), mesh.pop("stats")
-        self.profiling["background_texturing"] = {"key_frames": [int(f) for f in frame_set], "faces": int(views.shape[0]), "faces_with_a_view": int((views >= 0).sum()),
-                                                  "atlas": [int(mesh["texture"].shape[1]), int(mesh["texture"].shape[0])]}
-        if stats is not None:
-            self.profiling["background_texturing"]["smoothing"] = stats
+        self.profiling["background_texturing"] = self._texturing_record(frame_set, int(views.shape[0]), int((views >= 0).sum()), mesh["texture"].shape, stats,
+                                                                        float(self.options.texture_smoothness) > 0 or bool(self.options.texture_cull_back_faces))
         return mesh
+
+    @staticmethod
+    def _texturing_record(frame_set, faces, faces_with_a_view, atlas_shape, stats, smoothing) -> dict:
+        """``profiling['background_texturing']``: the counts; ``smoothing`` (the five label-smoothing stats) when ``--texture_smoothness`` or
+        ``--texture_cull_back_faces`` is set; ``exposure`` (gains and pair counts as lists, fallback channels) with ``--texture_exposure``; ``levelling`` (seam
+        vertices, sweeps, largest offset) with ``--texture_levelling``.  With every switch off: the four counts alone."""
+        record = {"key_frames": [int(f) for f in frame_set], "faces": int(faces), "faces_with_a_view": int(faces_with_a_view),
+                  "atlas": [int(atlas_shape[1]), int(atlas_shape[0])]}
+        stats = dict(stats or {})
+        exposure, levelling = stats.pop("exposure", None), stats.pop("levelling", None)
+        if smoothing and stats:
+            record["smoothing"] = stats
+        if exposure is not None:
+            record["exposure"] = {"gains": np.asarray(exposure["gains"]).tolist(), "pair_counts": np.asarray(exposure["pair_counts"]).tolist(),
+                                  "fallback_channels": [int(c) for c in exposure["fallback_channels"]]}
+        if levelling is not None:
+            record["levelling"] = dict(levelling)
+        return record
 
     def _create_foreground_scene(self, dataset: HiveDataset, num_frames: Optional[int] = None, folder: Optional[str] = None) -> gltf.Scene:
         """pipeline.py:288-307: an empty scene for ``background_only``, else every frame's mesh (``create_foreground_meshes``, which smooths the trajectory

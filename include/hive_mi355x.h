@@ -628,8 +628,8 @@ int hive_texture_fill(hive_ctx *ctx, const double *d_vertices, int64_t nv, const
  * equally well neighbouring faces flip between them, and every flip is a seam.  The three entry points below keep the areas in a table, build the edge
  * adjacency of the mesh and move labels while that lowers E = -sum_f area[L[f]][f] + seam_cost * #seams.  Integers only; the result is the same whatever order
  * workgroups run in and however many rounds the host issues between two polls.  This is iterated conditional modes: it ends in a LOCAL optimum of E, it is not
- * a graph cut.  Out of scope: a chart atlas (unweld and fill are unchanged: 3 F vertices, cell^2 texels per face pair), seam levelling, exposure compensation,
- * blending.  The rules:
+ * a graph cut.  Out of scope: a chart atlas (unweld and fill are unchanged: 3 F vertices, cell^2 texels per face pair), blending; exposure gains and seam levelling are
+ * further down (hive_texture_samples).  The rules:
  *   vote        hive_texture_select's candidate test, on the same d_xy, d_z, d_depth and d_mask, and a filter on the sign of the snapped area A: facing 0 takes
  *               either sign (as select does), 1 only A < 0, -1 only A > 0.  d_area[view_index nf + f] = |A| of a candidate, 0 otherwise; every entry of the row is
  *               written.  Which sign is the front: measured on the marching-cubes mesh of the tests' fused room (2 052 faces, three views) under the
@@ -668,6 +668,54 @@ int hive_mesh_face_neighbours(hive_ctx *ctx, const int32_t *d_faces, int64_t nf,
  * changes, seam entries before, seam entries after, area given up = sum_f (max_v area[v][f] - area[L[f]][f])}.  Synchronises once per batch of rounds. */
 int hive_texture_smooth(hive_ctx *ctx, const int64_t *d_area, int n_views, int64_t nf, const int64_t *d_offsets, const int32_t *d_neighbours, int64_t n_entries,
                         int64_t seam_cost, int rounds_per_poll, uint64_t *d_best, int64_t stats[5]);
+
+/* ---- exposure gains and seam levelling -- csrc/texture_level.hip.  The labels above decide WHERE the texture changes from one key frame to another; key frames
+ * of a camera with auto-exposure or auto white balance disagree in brightness and tint, and every remaining label change then shows as a step.  Two corrections,
+ * both off unless asked for: one multiplicative gain per key frame and channel (samples, sums, a host solve), and additive offsets that close the step at every
+ * seam vertex and fade out harmonically inside each patch (level).  hive_texture_fill_adjusted applies both.  Restated in
+ * tests/texture_levelling_restatement.py.  Out of scope: a border between a textured and an untextured face is not levelled; blending of several views; a chart
+ * atlas.  The rules (float64, no fused multiply-add, in the order written; a sum written "in order" starts at 0.0 and adds term after term):
+ *   samples     once per view, right after that view's hive_texture_vote, on the same d_xy.  A face with d_area[view][f] != 0 takes its three vertices' nearest
+ *               pixels ((Y_k + 128) >> 8, (X_k + 128) >> 8), the ones the vote tested.  If all nine bytes lie in [1, 254] the sample is the per-channel sum of
+ *               the three pixels (3 .. 762); otherwise, and for every other face, it is (0, 0, 0) = invalid (a clipped pixel says nothing about gain).
+ *               d_samples u16 [n_views][nf][3]; every entry of the row is written.  6 n_views nf bytes.
+ *   sums        a face is valid in a view iff its three sums there are non-zero.  Over the faces valid in both a and b, a != b:
+ *               G[c][a][b] = sum s_af s_bf, D[c][a][b] = sum s_af^2 (a's energy inside its overlap with b), N[a][b] = their number; diagonals 0.  Integers
+ *               below 2^51: the order of addition does not matter.  n_views <= 256.
+ *   solve       (the host's, numpy float64, per channel; hive_amd.texturing.solve_gains) e_a = sum_b D[a][b] exactly; M_aa = (double)e_a + prior (double)e_a,
+ *               M_ab = -(double)G[a][b], rhs_a = prior (double)e_a; a view with e_a = 0: the identity row, rhs 1.  g = solve(M, rhs) -- Brown and Lowe's gain
+ *               compensation with the prior weighted by the data's own energy, so `prior` has no unit.  The prior shrinks every gain, so over the views with
+ *               e_a > 0, summed in ascending a: g <- g (sum e_a) / (sum e_a g_a).  q = clip(floor(g 65536 + 0.5), 16384, 262144), u32 Q16.  A channel whose
+ *               solve fails or gives a gain that is not finite or not positive keeps q = 65536 for every view.  The device sees only q.
+ *   level       a face PARTICIPATES iff it has a view (key != 0, view < n), its ids lie in [0, nv) and are distinct; label l = its view.  Every other face has
+ *               offsets 0 and is invisible to the rule.  A NODE is a pair (vertex v, label l) that some participating face has.  Its colour c(v, l), per
+ *               channel: fill's sample at P = V_v with view l (the same projection, clamp and bilinear, unrounded; no near test: the view's draw kept the
+ *               vertex), then (c (double)q[l][ch]) 2^-16.  A SEAM VERTEX has two or more distinct labels among its participating faces; there
+ *               m(v) = (the sum in order of c(v, l) over its labels ascending) / count, and node (v, l) is FIXED at h = m(v) - c(v, l).  Every other node
+ *               starts at 0.  Then `sweeps` Jacobi sweeps, each read entirely from the buffer before it: a node (v, l) that is not fixed becomes
+ *               (the sum in order, over the participating faces f with label l that hold v, ascending f, v at corner k, of h[f][(k + 1) % 3] then
+ *               h[f][(k + 2) % 3]) / (2 count), h[f][j] being the offset of node (faces[f][j], l).  d_offsets f64 [nf][3][3] = per face corner and channel the
+ *               offset of its node.  The vertex -> faces lists are sorted by insertion: quadratic in a vertex's degree, fine for surfaces.
+ *   adjusted fill  hive_texture_fill's rule; with a view: texel = byte(((c (double)q[view][ch]) 2^-16) + ((b0 h0 + b1 h1) + b2 h2)), h_k = d_offsets[f][k][ch]
+ *               (the gutter extrapolates the same affine map); without a view the vertex colours, as the plain fill.  With every q = 65536 and every h = 0
+ *               both extra operations are exact and the atlas is hive_texture_fill's bit for bit. */
+/* One view's row of d_samples u16 [n_views][nf][3]: d_faces, d_xy of that view's hive_render_draw, d_area i64 [n_views][nf] with that view's row written by
+ * hive_texture_vote, d_frame u8 [H][W][3] that view's frame.  (view_index + 1) nf < 2^31. */
+int hive_texture_samples(hive_ctx *ctx, const int32_t *d_faces, int64_t nf, int64_t nv, const int32_t *d_xy, const int64_t *d_area, const uint8_t *d_frame, int H,
+                         int W, int view_index, uint16_t *d_samples);
+/* The pair sums of a finished table into HOST arrays G i64 [3][n_views][n_views], D i64 [3][n_views][n_views], N i64 [n_views][n_views].  1 <= n_views <= 256
+ * (HIVE_ERR_INVALID above), n_views nf < 2^31.  Workgroups reduce before they add: one 64-bit atomic per workgroup, pair and word.  One read-back. */
+int hive_texture_exposure_sums(hive_ctx *ctx, const uint16_t *d_samples, int n_views, int64_t nf, int64_t *G, int64_t *D, int64_t *N);
+/* The offsets d_offsets f64 [nf][3][3] of `level`: the welded mesh, the final keys d_best, the frames, K and d_poses as hive_texture_fill takes them,
+ * d_gains_q16 u32 [n][3] (all 65536: no gains), 0 <= sweeps <= 4096 (one launch each; nothing waits).  3 nf < 2^31.  *seam_vertices and *max_offset (the
+ * largest |offset|; each may be NULL) cost one read-back. */
+int hive_texture_level(hive_ctx *ctx, const double *d_vertices, int64_t nv, const int32_t *d_faces, int64_t nf, const uint64_t *d_best, const uint8_t *d_frames, int n,
+                       int H, int W, const double K[9], const double *d_poses, const uint32_t *d_gains_q16, int sweeps, double *d_offsets, int64_t *seam_vertices,
+                       double *max_offset);
+/* hive_texture_fill with gains and offsets (neither NULL): see `adjusted fill`. */
+int hive_texture_fill_adjusted(hive_ctx *ctx, const double *d_vertices, int64_t nv, const uint8_t *d_vertex_colors, const int32_t *d_faces, int64_t nf,
+                               const uint64_t *d_best, const uint8_t *d_frames, int n, int H, int W, const double K[9], const double *d_poses, double near, int cell,
+                               const uint32_t *d_gains_q16, const double *d_offsets, uint8_t *d_texture);
 
 /* ---- ray casting the volume and tracking the camera against it (KinectFusion-style frame-to-model ICP; no counterpart in the reference, which takes its
  * poses from COLMAP or BundleFusion).  Float32 where stated, every operation rounded once (no fused multiply-add), in the order written here; pixel (u, v) =
